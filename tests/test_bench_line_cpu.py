@@ -80,3 +80,56 @@ def test_emit_prints_one_stdout_line_and_writes_the_detail(tmp_path, capsys, mon
     assert len(lines) == 1 and lines[0].startswith('{"metric"') and len(lines[0]) < 6000
     assert json.load(open(tmp_path / "bench_detail.json"))["configs_measured"] == res["configs_measured"]
     assert "[bench detail]" in err
+
+
+# ---- the plain run / --full / --dump-outputs surface (no GPU: parsing and the dump helper on host tensors) ------------------------------
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    b = bench.parse(["--full", "--dump-outputs", "out_dir", "--no-configs"])
+    assert b.full is True and b.dump_outputs == "out_dir" and b.no_configs is True
+
+
+def test_dump_outputs_writes_every_array_exactly_when_it_fits(tmp_path):
+    import numpy as np
+    import torch
+    order = torch.arange(12, dtype=torch.int32).reshape(3, 4).flip(1)
+    scores = torch.tensor([[0.5, 0.25, 0.125, 1 / 3]] * 3, dtype=torch.float64)
+    emb = torch.randn(3, 5, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "d"), {"final_order": order, "fused_scores": scores, "emb": emb})
+    o, s, e, rows = (np.load(tmp_path / "d" / f"{n}.npy") for n in ("final_order", "fused_scores", "emb", "rows"))
+    assert o.dtype == np.float64 and np.array_equal(o, order.numpy())          # integers: exact in float64
+    assert s.dtype == np.float64 and np.array_equal(s, scores.numpy())
+    assert e.dtype == np.float32 and np.array_equal(e, emb.numpy())
+    assert np.array_equal(rows, np.arange(3))
+
+
+def test_dump_outputs_samples_the_same_seeded_rows_within_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    R, C = 1000, 64
+    order = torch.arange(R * C, dtype=torch.int32).reshape(R, C)
+    scores = torch.rand((R, C), dtype=torch.float64)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 100 * C * 16)                       # room for 100 rows of both arrays
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"final_order": order, "fused_scores": scores})
+    rows = np.load(tmp_path / "a" / "rows.npy")
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0) and rows[-1] < R
+    o, s = np.load(tmp_path / "a" / "final_order.npy"), np.load(tmp_path / "a" / "fused_scores.npy")
+    assert o.nbytes + s.nbytes <= bench.DUMP_BUDGET
+    idx = rows.astype(np.int64)
+    assert np.array_equal(o, order.numpy()[idx]) and np.array_equal(s, scores.numpy()[idx])       # the same rows of both
+    for n in ("rows", "final_order", "fused_scores"):                                             # fixed seed: run to run identical
+        assert np.array_equal(np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy"))
+
+
+def test_dump_outputs_keeps_the_head_of_a_row_longer_than_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    order = torch.arange(4 * 1000, dtype=torch.int32).reshape(4, 1000)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 800)                                # 100 float64 values
+    bench.dump_outputs(str(tmp_path), {"final_order": order})
+    o = np.load(tmp_path / "final_order.npy")
+    assert o.shape == (1, 100) and o.nbytes <= 800
+    r = int(np.load(tmp_path / "rows.npy")[0])
+    assert np.array_equal(o[0], order.numpy()[r, :100])

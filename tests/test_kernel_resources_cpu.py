@@ -135,7 +135,7 @@ def test_where_the_scratch_accesses_sit(obj, name, tmp_path):
         assert span >= min_span, f"{name}: a scratch access inside a {span}-instruction loop (an inner loop; allowed: loops of >= {min_span})"
 
 
-def test_table_swap_waits_for_exactly_the_requests_it_counts():
+def test_table_swap_waits_for_exactly_the_requests_it_counts(tmp_path):
     """ADVICE r4 (tables.hip): the table swap's `s_waitcnt vmcnt(ILV)` is hand-counted -- it assumes that exactly ILV vector-memory
     requests (the step's last score prefetch) are issued after the last LDS-DMA piece and before the wait; one more (a hoisted load, a
     spill) and the wait would return with a DMA piece still in flight, one less and it would wait for nothing it needs to.  Checked on
@@ -145,7 +145,7 @@ def test_table_swap_waits_for_exactly_the_requests_it_counts():
     _need_tool("llvm-objdump")
     if not os.path.exists(os.path.join(ROOT, "fusion_amd", "csrc", "tables.o")):
         pytest.skip("fusion_amd/csrc/tables.o is not built here (run `make -C fusion_amd/csrc`)")
-    listing = spill_locator.disassemble(os.path.join(ROOT, "fusion_amd", "csrc", "tables.o"))
+    listing = spill_locator.disassemble(os.path.join(ROOT, "fusion_amd", "csrc", "tables.o"), str(tmp_path))   # a directory of its own
     bodies = spill_locator.kernels(listing)
     checked = 0
     for mangled, body in bodies.items():

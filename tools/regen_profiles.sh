@@ -5,8 +5,8 @@ set -o pipefail
 O=gpurun_out/regen
 mkdir -p $O
 step() { echo "== $1" >&2; shift; timeout -k 10 "$@"; rc=$?; if [ $rc -ne 0 ]; then echo "step failed rc=$rc" >&2; exit $rc; fi; }
-step "bench default"   420 python bench.py > $O/bench_default.json 2> $O/bench_default.err
-step "bench Q=195"     200 python bench.py --queries 195 --no-configs > $O/bench_q195.json 2> $O/bench_q195.err
+step "bench default"   420 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+step "bench Q=195"     200 python bench.py --full --queries 195 --no-configs > $O/bench_q195.json 2> $O/bench_q195.err
 step "kernel bench"    300 python tools/bench_kernels.py > $O/kernel_bench.jsonl 2> $O/kernel_bench.err
 step "sort pass cost"  120 python tools/sort_pass_cost.py > $O/sort_pass_cost.log 2>&1
 step "colbert amp"     200 python tools/bench_colbert_amp.py 1024 > $O/colbert_amp.jsonl 2> $O/colbert_amp.err

@@ -4,10 +4,10 @@ set -o pipefail
 O=gpurun_out/r05
 mkdir -p $O
 step() { echo "== $1 $(date +%T)" >&2; shift; timeout -k 10 "$@"; rc=$?; if [ $rc -ne 0 ]; then echo "step failed rc=$rc" >&2; exit $rc; fi; }
-step "bench default"   420 python bench.py > $O/bench_default.json 2> $O/bench_default.err; cp bench_detail.json $O/bench_default_detail.json
-step "bench Q=195"     200 python bench.py --queries 195 --no-configs > $O/bench_q195.json 2> $O/bench_q195.err; cp bench_detail.json $O/bench_q195_detail.json
-step "bench mmarco n1" 400 python bench.py --workload mmarco --steps 3 --warmup 1 > $O/bench_mmarco_n1.json 2> $O/bench_mmarco_n1.err; cp bench_detail.json $O/bench_mmarco_n1_detail.json
-step "launcher 2 gloo" 400 env FUSION_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --rehearsal --mmarco-docs 2000000 --steps 2 --warmup 1 > $O/bench_launcher_2ranks_1gpu_gloo.json 2> $O/bench_launcher.err
+step "bench default"   420 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; cp bench_detail.json $O/bench_default_detail.json
+step "bench Q=195"     200 python bench.py --full --queries 195 --no-configs > $O/bench_q195.json 2> $O/bench_q195.err; cp bench_detail.json $O/bench_q195_detail.json
+step "bench mmarco n1" 400 python bench.py --full --workload mmarco --steps 3 --warmup 1 > $O/bench_mmarco_n1.json 2> $O/bench_mmarco_n1.err; cp bench_detail.json $O/bench_mmarco_n1_detail.json
+step "launcher 2 gloo" 400 env FUSION_BENCH_BACKEND=gloo python3 bench.py --full --gpus 2 --rehearsal --mmarco-docs 2000000 --steps 2 --warmup 1 > $O/bench_launcher_2ranks_1gpu_gloo.json 2> $O/bench_launcher.err
 step "kernel bench"    300 python tools/bench_kernels.py > $O/kernel_bench.jsonl 2> $O/kernel_bench.err
 step "gemm query rows" 200 python tools/bench_gemm_q.py > $O/gemm_query_rows.jsonl 2> $O/gemm_query_rows.err
 step "profile bench"   600 bash tools/profile_bench.sh > $O/profile_bench.log 2>&1
