@@ -12,7 +12,7 @@ namespace fz {
 struct Bm25Args {
     const int64_t* toff; const int32_t* pdoc; const int32_t* ptf; const double* idf; const int32_t* doc_len;
     const double* doc_norm;   // nullable: k1*(1-b+b*|d|/avgdl) per document (fz_bm25_doc_norms_f64), same bits as inline
-    const int64_t* slice_off; // nullable: [V][NS + 1] first posting of term t whose document is >= s * BM25_SLICE (fz_bm25_slice_offsets):
+    const int64_t* slice_off; // nullable: [V][NS + 1] first posting of term t whose document is >= s * BM25_GRAIN (fz_bm25_slice_offsets):
                               //   without it every workgroup finds its posting sub-ranges by ~30 dependent loads per term
     double avgdl, k1, b;
     const int64_t* qoff; const int32_t* qterms;
@@ -24,13 +24,12 @@ struct Bm25Args {
                                   //   fz_bm25_posting_values_f64 -- the walk only adds (fz_bm25_scores_pv_f64_f32)
 };
 
-// LDS-resident accumulators AND length norms: one workgroup = (query, slice of BM25_SLICE documents).  The random read-modify-writes of
+// LDS-resident accumulators AND length norms: one workgroup = (query, slice of slice_docs<MODE>() documents).  The random read-modify-writes of
 // the posting walk hit LDS (ds_read_b64 / ds_write_b64) instead of HBM/L2, and so does the per-posting read of the document's length
 // norm k1 (1 - b + b |d| / avgdl) -- round 5: as a gather from the [N] table in L2 it was one 64-byte sector per posting, ~110 k of them
 // per query (the frequent terms of a Zipf vocabulary list most of the corpus); the slice's norms now come in once per workgroup,
 // coalesced.  The slice is written out once, coalesced.  Postings of a term are sorted by document, so the slice's sub-range is found by
 // two block-uniform binary searches (or read from the per-index table).
-constexpr int BM25_SLICE = 7168;    // 7168 fp64 accumulators + 7168 fp64 norms = 112 KiB of the CU's 160 KiB LDS
 constexpr int BM25_GRAIN = 3584;    // granularity of the per-index posting-offset table (fz_bm25_slice_offsets): a workgroup's slice is 1 or 2 of these
 constexpr int BM25_PV_GRAINS = 1, BM25_PV_THREADS = 512;   // the table-driven walk's workgroup (see bm25_kernel)
 
@@ -49,16 +48,23 @@ constexpr int BM25_TERMS = 256;     // query terms whose posting ranges are reso
 // float64 division (a dozen instructions at half rate: most of this kernel's time) is done once per index, like the idf table, not once
 // per (query, posting); the walk adds the same bits in the same order.
 enum { BM25_EXPR = 0, BM25_TFIDF = 1, BM25_PVAL = 2 };
+
+// Documents of one workgroup's slice, for the kernel's walk and the launcher's grid and LDS alike: table grains per slice x BM25_GRAIN.
+template <int MODE> constexpr int slice_grains() { return MODE == BM25_PVAL ? BM25_PV_GRAINS : 2; }
+template <int MODE> constexpr int slice_docs() { return BM25_GRAIN * slice_grains<MODE>(); }
+// LDS per workgroup: the slice's fp64 accumulators, plus its fp64 length norms for the per-posting expression (TFIDF reserves them too)
+template <int MODE> constexpr size_t slice_lds_bytes() { return (MODE == BM25_PVAL ? 1 : 2) * (size_t)slice_docs<MODE>() * sizeof(double); }
+static_assert(slice_docs<BM25_EXPR>() == 7168 && slice_docs<BM25_TFIDF>() == 7168 && slice_docs<BM25_PVAL>() == 3584,
+              "the measured slice sizes (see bm25_kernel)");
+static_assert(slice_lds_bytes<BM25_EXPR>() == 112 * 1024 && slice_lds_bytes<BM25_PVAL>() == 28 * 1024, "7168 accumulators + 7168 norms = 112 KiB of the CU's 160 KiB LDS");
 template <int MODE>
 __global__ __launch_bounds__(1024) void bm25_kernel(Bm25Args a) {
     constexpr bool TFIDF = MODE == BM25_TFIDF, PVAL = MODE == BM25_PVAL;
-    // PVAL needs no length norms in LDS: its workgroup takes TWO slices' worth of documents (14,336 accumulators = 112 KiB) -- half the
-    // workgroups, and a term's posting sub-range is twice as long against the same per-term barrier
     // PVAL needs no length norms in LDS and little else: 3,584 accumulators (28 KiB) and 512 threads per workgroup, four workgroups per CU
     // -- a posting walk is a chain of (load, LDS add) round trips with a barrier per query term, and independent workgroups fill each
     // other's waits.  Measured per 1024 x 27,942 (bench step): 7,168 documents x 1024 threads 0.165 ms, 14,336 x 1024 0.198, 3,584 x 1024
     // 0.210, 3,584 x 256 0.162, 3,584 x 512 0.146 (the per-posting expression: 0.326).
-    constexpr int SL = PVAL ? BM25_PV_GRAINS : 2, BM25_SLICE = fz::BM25_GRAIN * SL;      // table grains per workgroup slice
+    constexpr int SL = slice_grains<MODE>(), BM25_SLICE = slice_docs<MODE>();   // table grains / documents per workgroup slice
     extern __shared__ __attribute__((aligned(16))) double acc[];          // [BM25_SLICE] accumulators | [BM25_SLICE] length norms
     double* nrm = acc + BM25_SLICE;
     __shared__ int64_t s_e0[BM25_TERMS], s_e1[BM25_TERMS];
@@ -247,20 +253,22 @@ extern "C" int fz_bm25_scores_pv_f64_f32(const int64_t* toff, const int32_t* pdo
 
 static int bm25_launch(const Bm25Args& a, int Q, void* stream) {
     const int N = a.N;
-    constexpr size_t lds_bytes = 2 * (size_t)BM25_SLICE * sizeof(double);
     static unsigned long long lds_set[3] = {0ull, 0ull, 0ull};
-    dim3 grid((unsigned)((N + BM25_SLICE - 1) / BM25_SLICE), (unsigned)Q);
     if (a.pval) {
-        constexpr size_t lds_pv = (size_t)BM25_PV_GRAINS * BM25_GRAIN * sizeof(double);   // accumulators only
-        grid.x = (unsigned)((N + BM25_PV_GRAINS * BM25_GRAIN - 1) / (BM25_PV_GRAINS * BM25_GRAIN));
-        if (int rc = raise_lds_limit((const void*)bm25_kernel<BM25_PVAL>, lds_pv, lds_set[2])) return rc;
-        bm25_kernel<BM25_PVAL><<<grid, BM25_PV_THREADS, lds_pv, as_stream(stream)>>>(a);
+        constexpr int S = slice_docs<BM25_PVAL>();
+        constexpr size_t lds = slice_lds_bytes<BM25_PVAL>();
+        if (int rc = raise_lds_limit((const void*)bm25_kernel<BM25_PVAL>, lds, lds_set[2])) return rc;
+        bm25_kernel<BM25_PVAL><<<dim3((unsigned)((N + S - 1) / S), (unsigned)Q), BM25_PV_THREADS, lds, as_stream(stream)>>>(a);
     } else if (a.tfidf) {
-        if (int rc = raise_lds_limit((const void*)bm25_kernel<BM25_TFIDF>, lds_bytes, lds_set[1])) return rc;
-        bm25_kernel<BM25_TFIDF><<<grid, 1024, lds_bytes, as_stream(stream)>>>(a);
+        constexpr int S = slice_docs<BM25_TFIDF>();
+        constexpr size_t lds = slice_lds_bytes<BM25_TFIDF>();
+        if (int rc = raise_lds_limit((const void*)bm25_kernel<BM25_TFIDF>, lds, lds_set[1])) return rc;
+        bm25_kernel<BM25_TFIDF><<<dim3((unsigned)((N + S - 1) / S), (unsigned)Q), 1024, lds, as_stream(stream)>>>(a);
     } else {
-        if (int rc = raise_lds_limit((const void*)bm25_kernel<BM25_EXPR>, lds_bytes, lds_set[0])) return rc;
-        bm25_kernel<BM25_EXPR><<<grid, 1024, lds_bytes, as_stream(stream)>>>(a);
+        constexpr int S = slice_docs<BM25_EXPR>();
+        constexpr size_t lds = slice_lds_bytes<BM25_EXPR>();
+        if (int rc = raise_lds_limit((const void*)bm25_kernel<BM25_EXPR>, lds, lds_set[0])) return rc;
+        bm25_kernel<BM25_EXPR><<<dim3((unsigned)((N + S - 1) / S), (unsigned)Q), 1024, lds, as_stream(stream)>>>(a);
     }
     FZ_LAUNCH_CHECK();
     return FZ_OK;

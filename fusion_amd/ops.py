@@ -1001,6 +1001,12 @@ def bm25_doc_norms(doc_len: torch.Tensor, avgdl: float, k1: float, b: float) -> 
     return out
 
 
+def bm25_slice_table_bytes(V: int, N: int) -> int:
+    """Device bytes of bm25_slice_offsets' table for V terms over N documents: V x (NS + 1) int64."""
+    NS = max(1, -(-int(N) // int(_lib.lib().fz_bm25_slice_docs())))
+    return int(V) * (NS + 1) * 8
+
+
 def bm25_slice_offsets(toff: torch.Tensor, pdoc: torch.Tensor, N: int) -> torch.Tensor:
     """Per-index table [V, NS + 1] int64 for bm25_scores(slice_off=...): where every term's postings cross the document slices one
     workgroup scores (fz_bm25_slice_offsets; built once per index, like the idf table)."""

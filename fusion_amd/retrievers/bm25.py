@@ -39,6 +39,27 @@ from ..planes import RankedSystem
 
 
 LEXICAL_MIN_ZERO_SHARE = 0.3   # expected share of exact zeros per row from which the ranking sort's zero-compacting instantiation is asked for
+SLICE_TABLE_MAX_BYTES = 1 << 30   # the per-index slice-offset table (V x (N / 3,584 + 1) int64) is built only below this size; above it the
+                                  # scoring kernel finds every term's slice sub-range by binary search (same bits, no table)
+DEVICE_BUDGET_BYTES = 48 << 30    # device memory the planes of one chunk of queries may take (ranked_positions, BM25.tune)
+
+
+def _cut_widths(n: int, k: int, W: int) -> list[int]:
+    """Row widths of the hierarchical top-k cut of an n-wide score row (TFIDF.ranked_positions): each level sorts every W-wide stretch of
+    the row and keeps its first min(k, W) entries, so the next row is ceil(n / W) * min(k, W) wide.  With min(k, W) > W / 2 the widths can
+    stop falling (and with k >= W nothing is cut), or fall by a few columns a level (k = W - 1 over 8.8 M documents: 157 levels), so a level
+    is taken only while it keeps at most three quarters of the row it comes from -- strictly narrower, at most log4/3(n / W) + 2 levels --
+    and the last row is sorted whole (sort_rows_desc: chunk-sort + merge for rows of any length).  The last width is the row sorted whole."""
+    if n <= 0 or k <= 0 or W <= 0:
+        return [max(n, 0)]
+    widths, kk = [n], min(k, W)
+    while n > W:
+        nxt = -(-n // W) * kk
+        if 4 * nxt > 3 * n:
+            break
+        widths.append(nxt)
+        n = nxt
+    return widths
 
 
 def expected_zero_share(df: np.ndarray, n_docs: int, query_terms: list[list[int]]) -> float:
@@ -65,7 +86,7 @@ def expected_zero_share(df: np.ndarray, n_docs: int, query_terms: list[list[int]
 class TFIDF:
     """bm25.py:33-127: score(q, d) = sum over q.split(), in order, of tf(t, d) * idf(t), idf = log10((N + 1) / (df + 1))."""
 
-    def __init__(self, corpus: list[str], device="cuda"):
+    def __init__(self, corpus: list[str], device="cuda", slice_table_max_bytes: int | None = None):
         self.corpus = corpus
         self.corpus_size = len(corpus)
         self.device = torch.device(device)
@@ -93,8 +114,13 @@ class TFIDF:
         self.ptf = torch.from_numpy(self._ptf_host).to(d)
         self.idf = torch.from_numpy(self.idf_host).to(d)
         self.doc_len = torch.from_numpy(self.doc_len_host).to(d)
-        # where every term's postings cross the document slices one workgroup scores: per index, like the idf table
-        self.slice_off = ops.bm25_slice_offsets(self.toff, self.pdoc, self.corpus_size) if self.device.type == "cuda" and V > 0 else None
+        # where every term's postings cross the document slices one workgroup scores: per index, like the idf table -- when it fits the cap
+        # (a multi-million-term vocabulary over millions of documents would make it tens of GB; without it the kernel binary-searches)
+        self.slice_off = None
+        if self.device.type == "cuda" and V > 0:
+            cap = SLICE_TABLE_MAX_BYTES if slice_table_max_bytes is None else slice_table_max_bytes
+            if ops.bm25_slice_table_bytes(V, self.corpus_size) < cap:
+                self.slice_off = ops.bm25_slice_offsets(self.toff, self.pdoc, self.corpus_size)
         self._qcache = None
         self.zero_share_estimate = 0.0   # of the last list of queries (set by _query_csr)
 
@@ -145,51 +171,61 @@ class TFIDF:
                             ids=np.arange(N, dtype=np.int64) if ids is None else ids, full=True,
                             scores64=sc64, score_sorted=True, stats4=stats4)
 
-    def ranked_positions(self, queries: list[str], top_k: int, budget_bytes: int = 48 << 30) -> np.ndarray:
+    def ranked_positions(self, queries: list[str], top_k: int, budget_bytes: int = DEVICE_BUDGET_BYTES) -> np.ndarray:
         """[Q, min(top_k, N)] corpus positions of the first top_k entries of every ranked list (what the driver keeps of search_all,
         bm25.py:248-249), the queries taken in chunks whose planes fit the budget.  A corpus that fits one workgroup's row (28,672 documents)
-        is ranked in full (search_device); a longer one -- mMARCO's 8.8 M passages -- is CUT, not ranked: every 28,672-document stretch of the
-        float64 score row is sorted on its own, its first top_k entries survive, and the survivors (kept in corpus order, so that the stable
-        sort breaks ties by ascending index as the full sort does) go round again until one row holds them -- the same first top_k entries as
-        the full ranking, without its cross-chunk ranking of all N documents."""
-        N, k = self.corpus_size, min(top_k, self.corpus_size)
-        W = ops.sort_max_n(torch.float64)
-        per_pair = 20 if N <= W else 12 + 24 * min(1.0, (k + 1) / W)      # planes alive per (query, document)
-        step = max(1, int(budget_bytes // max(1, int(per_pair * ops.round_up(max(N, 1), 64)))))
+        is ranked in full (search_device); a longer one -- mMARCO's 8.8 M passages -- is CUT, not ranked (_top_positions)."""
+        N, k = self.corpus_size, max(0, min(top_k, self.corpus_size))
         out = np.empty((len(queries), k), dtype=np.int64)
+        if k == 0:
+            return out
+        W = ops.sort_max_n(torch.float64)
+        step = self._query_step(k, budget_bytes)
         for lo in range(0, len(queries), step):
             chunk = queries[lo:lo + step]
             if N <= W:
                 out[lo:lo + len(chunk)] = self.search_device(chunk).order[:, :k].cpu().numpy()
-                continue
-            sc = self.scores(chunk)                                        # [q, N] float64
-            q = sc.shape[0]
-            ids = None                                                     # [q, n] corpus positions of the surviving columns (None: the identity)
-            while True:
-                n = sc.shape[1]
-                C = -(-n // W)
-                if C > 1:                                                  # pad to whole stretches: -inf never survives a real score, NaN sorts first as everywhere
-                    pad = C * W - n
-                    if pad:
-                        sc = torch.cat([sc, torch.full((q, pad), float("-inf"), dtype=sc.dtype, device=sc.device)], 1)
-                        if ids is not None:
-                            ids = torch.cat([ids, torch.full((q, pad), -1, dtype=torch.int64, device=sc.device)], 1)
-                    rows = sc.reshape(q * C, W)
-                else:
-                    rows = sc
-                order, keys, _ = ops.sort_rows_desc(ops.as_plane(rows.contiguous()), want_keys=True)
-                kk = min(k, rows.shape[1])
-                order, keys = order[:, :kk].long(), keys[:, :kk]
-                if C > 1:
-                    base = (torch.arange(C, device=sc.device) * W).repeat(q)[:, None]
-                    cols = (order + base).reshape(q, C * kk)               # columns of this level's row, stretch by stretch: corpus order is kept
-                    ids = cols if ids is None else torch.gather(ids, 1, cols)
-                    sc = keys.reshape(q, C * kk)
-                    continue
-                pos = order if ids is None else torch.gather(ids, 1, order)
-                out[lo:lo + q] = pos[:, :k].cpu().numpy()
-                break
+            else:
+                out[lo:lo + len(chunk)] = self._top_positions(self.scores(chunk), k).cpu().numpy()
         return out
+
+    def _query_step(self, k: int, budget_bytes: int) -> int:
+        """Queries per chunk whose planes fit budget_bytes (at least one)."""
+        N, W = self.corpus_size, ops.sort_max_n(torch.float64)
+        per_pair = 20 if N <= W else 12 + 24 * min(1.0, (k + 1) / W)      # planes alive per (query, document)
+        if N > W and _cut_widths(N, k, W)[-1] > W:
+            per_pair = 36                                                  # a row longer than W sorted whole: scores, order, 24 B of merge workspace
+        return max(1, int(budget_bytes // max(1, int(per_pair * ops.round_up(max(N, 1), 64)))))
+
+    @staticmethod
+    def _top_positions(sc: torch.Tensor, k: int) -> torch.Tensor:
+        """[q, k] int64 corpus positions of the first k entries of the stable descending ranking of every row of the float64 plane sc [q, n]
+        (0 < k <= n), by the hierarchical cut (_cut_widths): every W-wide stretch of the row is sorted on its own, its first k entries survive,
+        and the survivors (stretch by stretch, so that the stable sort breaks ties by ascending index as the full sort does) go round again
+        while that narrows the row; the last row is sorted whole.  The same first k entries as the full ranking, without its cross-chunk
+        ranking of all n documents."""
+        W = ops.sort_max_n(torch.float64)
+        q = sc.shape[0]
+        widths = _cut_widths(sc.shape[1], k, W)
+        ids = None                                                         # [q, n] corpus positions of the surviving columns (None: the identity)
+        for n, nxt in zip(widths[:-1], widths[1:]):
+            C = -(-n // W)
+            pad = C * W - n                                                # pad to whole stretches: -inf never survives a real score, NaN sorts first as everywhere
+            if pad:
+                sc = torch.cat([sc, torch.full((q, pad), float("-inf"), dtype=sc.dtype, device=sc.device)], 1)
+                if ids is not None:
+                    ids = torch.cat([ids, torch.full((q, pad), -1, dtype=torch.int64, device=sc.device)], 1)
+            order, keys, _ = ops.sort_rows_desc(ops.as_plane(sc.reshape(q * C, W).contiguous()), want_keys=True)
+            kk = min(k, W)
+            base = (torch.arange(C, device=sc.device) * W).repeat(q)[:, None]
+            cols = (order[:, :kk].long() + base).reshape(q, C * kk)       # columns of this level's row, stretch by stretch: corpus order is kept
+            if cols.shape[1] != nxt or 4 * nxt > 3 * n:                    # (_cut_widths takes only levels that narrow the row)
+                raise RuntimeError(f"ranked_positions: the cut of a {n}-wide row to {cols.shape[1]} columns makes no progress (planned {nxt})")
+            ids = cols if ids is None else torch.gather(ids, 1, cols)
+            sc = keys[:, :kk].reshape(q, C * kk)
+        order, _, _ = ops.sort_rows_desc(ops.as_plane(sc.contiguous()), want_keys=False)
+        order = order[:, :k].long()
+        return order if ids is None else torch.gather(ids, 1, order)
 
     def search_all(self, queries: list[str], top_k: int) -> list:
         """bm25.py:90-106: every document scored (zero scores included), stable sort desc, [:top_k]."""
@@ -223,10 +259,10 @@ class BM25(TFIDF):
 
     USE_POSTING_VALUES = True   # False: the per-posting expression (fz_bm25_scores_f64_f32): A/B runs and tests of the two forms
 
-    def __init__(self, corpus: list[str], k1: float, b: float, device="cuda"):
+    def __init__(self, corpus: list[str], k1: float, b: float, device="cuda", slice_table_max_bytes: int | None = None):
         self.k1, self.b = k1, b
         self._pval = None
-        super().__init__(corpus, device=device)
+        super().__init__(corpus, device=device, slice_table_max_bytes=slice_table_max_bytes)
         self.avgdl = float(mean(self.doc_len_host.tolist())) if self.corpus_size else 0.0   # bm25.py:138
         self._norm_key, self._norm = None, None
 
@@ -257,12 +293,14 @@ class BM25(TFIDF):
 
     # -- the grid search of bm25.py:221-237 on the device --------------------------------------------------------------
     def tune(self, queries: list[str], labels: list[list], ids=None, k1_range=None, b_range=None,
-             recall_at_k=(10, 100, 200, 500, 1000), top_k: int = 1000) -> list[dict]:
+             recall_at_k=(10, 100, 200, 500, 1000), top_k: int = 1000, budget_bytes: int = DEVICE_BUDGET_BYTES) -> list[dict]:
         """For every (k1, b) of itertools.product(k1_range, b_range) (bm25.py:226-228): what
         `update_params(k1, b); search_all(queries, top_k); Metrics(recall_at_k).compute_all_metrics(labels, ids of the lists)` reports
         (bm25.py:231-234) -- recall@k for the given cut-offs and r-precision -- as one dict per pair: {'k1', 'b', 'recall@10', ...}.
         The lists are never built: one scoring launch + one row sort per pair, and the ranks of the gold documents (a gold document at
         rank >= top_k was cut from the list: never retrieved) come back.  ids: corpus position -> dataset id (idx2id, bm25.py:214).
+        The queries are taken in chunks whose planes fit budget_bytes, as in ranked_positions; a corpus longer than one sort row is cut to
+        its first top_k entries (_top_positions), not ranked in full: a gold document's rank is its place in that head, or none.
         The model's own k1 / b are restored afterwards."""
         from ..utils.metrics import metrics_from_gold_ranks
         k1_range = np.arange(0., 8.5, 0.5) if k1_range is None else k1_range      # bm25.py:226
@@ -278,17 +316,30 @@ class BM25(TFIDF):
             gp[q, :len(gl)] = gl
         gp_dev = torch.from_numpy(np.maximum(gp, 0)).to(self.device)
         n_gold = np.array([len(gl) for gl in labels], dtype=np.int64)             # the reference divides by len(ground_truths)
-        list_len = np.full(Q, min(top_k, N), dtype=np.int64)
+        k = max(0, min(top_k, N))
+        list_len = np.full(Q, k, dtype=np.int64)
         INF = np.iinfo(np.int64).max
+        W = ops.sort_max_n(torch.float64)
+        step = self._query_step(k, budget_bytes)
         keep = (self.k1, self.b)
-        got = torch.empty((len(combos), Q, G), dtype=torch.int32, device=self.device)
+        got = torch.full((len(combos), Q, G), k, dtype=torch.int64, device=self.device)   # k: not among the first top_k
         for w, (k1, b) in enumerate(combos):
             self.update_params(k1, b)
-            _, _, rank = ops.sort_rows_desc(self.scores(queries), want_keys=False, want_rank=True, lexical=self.zero_share_estimate >= LEXICAL_MIN_ZERO_SHARE)
-            got[w] = torch.gather(rank, 1, gp_dev)
+            for lo in range(0, Q if k else 0, step):
+                chunk = queries[lo:lo + step]
+                g = gp_dev[lo:lo + len(chunk)]
+                sc = self.scores(chunk)
+                if N <= W:
+                    _, _, rank = ops.sort_rows_desc(sc, want_keys=False, want_rank=True, lexical=self.zero_share_estimate >= LEXICAL_MIN_ZERO_SHARE)
+                    got[w, lo:lo + len(chunk)] = torch.gather(rank, 1, g).long()
+                    continue
+                pos = self._top_positions(sc, k)                           # [q, k]: a corpus position appears at most once per row
+                at = torch.arange(k, dtype=torch.int64, device=self.device)
+                for j in range(G):
+                    got[w, lo:lo + len(chunk), j] = torch.where(pos == g[:, j:j + 1], at, k).min(1).values
         self.update_params(*keep)
-        ranks = got.cpu().numpy().astype(np.int64)
-        ranks = np.where((gp[None] >= 0) & (ranks < top_k), ranks, INF)
+        ranks = got.cpu().numpy()
+        ranks = np.where((gp[None] >= 0) & (ranks < k), ranks, INF)
         names = [f"recall@{k}" for k in recall_at_k] + ["r-precision"]
         perfs = metrics_from_gold_ranks(ranks, n_gold, list_len, recall_ks=list(recall_at_k), only=names)
         return [{"k1": float(k1), "b": float(b), **p} for (k1, b), p in zip(combos, perfs)]

@@ -409,18 +409,34 @@ def case_fuse_ranked(rng):
 
 
 def case_bm25(rng):
+    """Small corpora, or (one case in four) short documents whose count lies within 2 of a boundary of the scoring walk (3,584-document
+    grains, 7,168-document slices) or of the float64 sort row W; those also check ranked_positions at a random top_k (around W / 2, W, N)."""
     from fusion_amd.retrievers.bm25 import BM25
     V = int(rng.integers(3, 400))
     vocab = np.array([f"w{i}" for i in range(V)])
     p = 1.0 / np.arange(1, V + 1); p /= p.sum()
-    docs = [" ".join(rng.choice(vocab, size=int(rng.integers(0, 80)), p=p)) for _ in range(int(rng.integers(1, 400)))]
+    W = ops.sort_max_n(torch.float64)
+    edge = rng.random() < 0.25
+    if edge:
+        n_docs = int(rng.choice([3584, 7168, 10752, 14336, W, 2 * W])) + int(rng.integers(-2, 3))
+        docs = [" ".join(rng.choice(vocab, size=int(rng.integers(0, 6)), p=p)) for _ in range(n_docs)]
+    else:
+        docs = [" ".join(rng.choice(vocab, size=int(rng.integers(0, 80)), p=p)) for _ in range(int(rng.integers(1, 400)))]
     queries = [" ".join(rng.choice(vocab, size=int(rng.integers(0, 10)), p=p)) for _ in range(int(rng.integers(1, 12)))] + ["zzz w1 w1"]
     if not any(d for d in docs):
         docs[0] = "w0"
     k1, b = float(rng.choice([0.9, 1.2, 2.5])), float(rng.choice([0.0, 0.2, 0.75, 1.0]))
-    got = BM25(docs, k1, b).scores(queries).cpu().numpy()
-    np.testing.assert_array_equal(got, oracle.BM25(docs, k1, b).scores(queries))
-    return f"bm25 docs={len(docs)} V={V} k1={k1} b={b}"
+    m, om = BM25(docs, k1, b), oracle.BM25(docs, k1, b)
+    got = m.scores(queries).cpu().numpy()
+    np.testing.assert_array_equal(got, om.scores(queries))
+    if not edge:
+        return f"bm25 docs={len(docs)} V={V} k1={k1} b={b}"
+    N = len(docs)
+    top_k = max(0, int(rng.choice([1, 1000, W // 2, W, N])) + int(rng.integers(-2, 3)))
+    pos = m.ranked_positions(queries, top_k=top_k, budget_bytes=int(rng.choice([1, 48 << 30])))
+    exp = [[x["corpus_id"] for x in r] for r in om.search_all(queries, top_k=top_k)]
+    assert pos.shape == (len(queries), min(top_k, N)) and pos.tolist() == exp
+    return f"bm25 docs={N} V={V} k1={k1} b={b} ranked_positions top_k={top_k}"
 
 
 def case_tune(rng):

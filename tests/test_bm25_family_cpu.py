@@ -126,3 +126,32 @@ def test_expected_zero_share_picks_the_ranking_sort():
     assert expected_zero_share(df, 10, [[0, 0, 1], [2], [-1], []]) == pytest.approx((0.5 + 0.0 + 1.0 + 1.0) / 4)
     assert expected_zero_share(df, 10, []) == 0.0 and expected_zero_share(df, 0, [[0]]) == 0.0
     assert expected_zero_share(np.array([998, 3]), 1000, [[0, 1]]) < LEXICAL_MIN_ZERO_SHARE < expected_zero_share(np.array([998, 3]), 1000, [[1, 1]])
+
+
+def test_hierarchical_cut_widths_strictly_narrow_and_end_in_one_row():
+    """BM25.ranked_positions / tune cut a score row longer than one sort row (W = 28,672 float64 keys) level by level (_cut_widths): every
+    W-wide stretch keeps its first min(k, W) entries.  With min(k, W) > W / 2 that stops narrowing the row -- N = 2W + 1, k = 20,000 gives
+    3 x 20,000 = 60,000 > 57,345 columns, and a loop that waited for the row to fit W never ended.  Every planned level must be strictly
+    narrower than the last (at most 3/4 of it: the depth is logarithmic, not ~W levels of a few columns each when k is close to W), keep at
+    least the k wanted entries, and the last row is sorted whole (it fits W, or one more level would not narrow it enough); k = 0 and
+    k >= W included."""
+    from fusion_amd.retrievers.bm25 import _cut_widths
+    W0 = 28_672
+    assert _cut_widths(2 * W0 + 1, 20_000, W0) == [2 * W0 + 1]                   # the hang: no level narrows, the row is sorted whole
+    assert _cut_widths(2 * W0 + 1, W0 // 2 + 1, W0) == [2 * W0 + 1]                # 43,011 columns: not narrow enough
+    assert _cut_widths(90_011, W0 // 2 + 1, W0) == [90_011, 4 * (W0 // 2 + 1), 3 * (W0 // 2 + 1), 2 * (W0 // 2 + 1)]   # ends 2 columns over W
+    assert _cut_widths(90_011, 1000, W0) == [90_011, 4000]
+    assert _cut_widths(W0, 5, W0) == [W0] and _cut_widths(0, 5, W0) == [0] and _cut_widths(7, 0, W0) == [7]
+    for W in (1, 2, 3, 4, 7, 64, 1000, W0):
+        ns = sorted({1, 2, W - 1, W, W + 1, 2 * W - 1, 2 * W + 1, 3 * W + 1234, 17 * W + 5, 1000 * W + 3} - {0})
+        ks = sorted({0, 1, 2, 7, 1000, W // 2 - 1, W // 2, W // 2 + 1, W - 1, W, W + 1, 20_000, 3 * W} - {-1})
+        for n in ns:
+            for k in ks + [n - 1, n, n + 5]:
+                w = _cut_widths(n, k, W)
+                assert w[0] == n and len(w) <= 64, (n, k, W, w)
+                assert all(4 * b <= 3 * a for a, b in zip(w, w[1:])), (n, k, W, w)     # strictly narrower, by a quarter at least
+                assert all(x >= min(k, n) for x in w), (n, k, W, w)           # every level still holds the first k entries
+                assert all(b == -(-a // W) * min(k, W) for a, b in zip(w, w[1:])), (n, k, W, w)
+                last = w[-1]
+                assert last <= W or k <= 0 or 4 * (-(-last // W) * min(k, W)) > 3 * last, (n, k, W, w)
+    assert max(len(_cut_widths(8_841_823, k, W0)) for k in range(1, W0 + 1, 7)) <= 24               # mMARCO: 157 levels at k = 28,484 if any narrowing counted
