@@ -131,3 +131,71 @@ class ShardedDenseIndex:
         out = allgather_topk(s, i, self.group)
         if mark: mark("allgather_merge")
         return out
+
+
+class ShardedSparseIndex:
+    """One rank's shard of a SPLADE corpus as an inverted index (ops.SparseIndex, documents 0 .. N-1 = global ids id_base ..) + the
+    chunked score -> top-k loop of splade/base.py:199-251 (BaseModel.search) at corpus scale.  The shape of ShardedDenseIndex: the first
+    HEAD documents are scored into a plane and ranked exactly, the rest streams through fz_sparse_dot_filter_f32 -- the posting walk whose
+    epilogue is TopkStream's threshold filter, no score plane -- in CHUNK-document pieces; one all-gather merges the shards.  Ties go to
+    the ascending global id (SPLADE rows are mostly exact zeros: this rule decides the tail of a query that matches fewer than k
+    documents)."""
+
+    CHUNK = 32 * 7168   # documents per feed (a whole number of the kernels' 7,168-document slices)
+    CAP = 7168          # candidate slots per row and window on the streaming path
+
+    def __init__(self, index, id_base: int, group=None):
+        self.index, self.id_base, self.group = index, int(id_base), group
+        self.last_overflow = 0   # windows of the last local_topk whose candidate buffers overflowed (each was redone exactly, ops.TopkStream)
+
+    def head_docs(self, k: int) -> int:
+        """ShardedDenseIndex's head for this k (8,192 at k = 1000), rounded up to whole slices (14,336)."""
+        from . import ops
+        dense = min(ShardedDenseIndex.HEAD, max(8192, -(-8 * k // 4096) * 4096))
+        return ops.round_up(dense, ops.sparse_slice_docs())
+
+    def local_topk(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, k: int, mark=None):
+        """[Q, k] (score desc, id asc) over this shard for the queries' term lists (ops.sparse_rows); short lists padded with (-inf, -1)."""
+        from . import ops
+        mark = mark or (lambda name: None)
+        idx, n, Q = self.index, self.index.N, qoff.numel() - 1
+        S = ops.sparse_slice_docs()
+        chunk = max(S, self.CHUNK // S * S)
+        head = self.head_docs(k)
+        self.last_overflow = 0
+        if n == 0 or Q == 0:
+            return (torch.full((Q, k), float("-inf"), dtype=torch.float32, device=qoff.device),
+                    torch.full((Q, k), -1, dtype=torch.int64, device=qoff.device))
+        if k + self.CAP <= 35840 and k <= head // 8 and n > head:
+            sc = ops.sparse_dot(idx, qoff, qterms, qw, doc_hi=head); mark("shard_sparse")
+            bs, bi = ops.topk_rows(sc, k, id_base=self.id_base)
+            del sc
+            stream = ops.TopkStream(bs, bi, seen=head, cap=self.CAP); mark("shard_topk_stream")
+            for c0 in range(head, n, chunk):
+                stream.feed_sparse(idx, qoff, qterms, qw, c0, min(n, c0 + chunk), self.id_base, mark=mark)
+            best_s, best_i, _ = stream.result(); mark("shard_topk_stream")
+            self.last_overflow = stream.windows_redone
+            return best_s, best_i
+        return self._exact_topk(qoff, qterms, qw, k, chunk, mark)
+
+    def _exact_topk(self, qoff, qterms, qw, k: int, chunk: int, mark):
+        """The two-pass path -- per chunk a score plane, its top-k, a merge -- for a small shard or a k beyond the streaming sort's reach
+        (and the yardstick tools/bench_splade_search.py times the fused path against)."""
+        from . import ops
+        idx, n = self.index, self.index.N
+        best_s = best_i = None
+        for c0 in range(0, n, chunk):
+            c1 = min(n, c0 + chunk)
+            s, i = ops.topk_rows(ops.sparse_dot(idx, qoff, qterms, qw, doc_lo=c0, doc_hi=c1), k, id_base=self.id_base + c0)
+            if best_s is None:
+                best_s, best_i = s, i
+            else:
+                best_s, best_i = ops.topk_merge(torch.stack([best_s, s]), torch.stack([best_i, i]))
+            mark("shard_topk_exact")
+        return best_s, best_i
+
+    def search(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, k: int = 1000, mark=None):
+        s, i = self.local_topk(qoff, qterms, qw, k, mark=mark)
+        out = allgather_topk(s, i, self.group)
+        if mark: mark("allgather_merge")
+        return out

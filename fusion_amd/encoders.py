@@ -422,6 +422,8 @@ class DenseEncoder(_Base):
 
 class SpladeEncoder(_Base):
     """SPLADE-max: amax over tokens of log1p(relu(MLM logits * mask))  (splade/splade.py:88-99)."""
+    similarity = "cos_sim"   # BaseModel's default (splade/base.py): index() and search() L2-normalise both sides; "dot_score": raw weights
+    INDEX_BLOCK = 4096       # documents per encode() call of index(): the dense rows of one block (0.5 GB at 32,005 terms) are all it holds
 
     def __init__(self, mlm, tokenizer, device):
         super().__init__(tokenizer, device)
@@ -504,6 +506,56 @@ class SpladeEncoder(_Base):
         for idx, ids, mask in self._batches(sentences, batch_size, max_len):
             out[torch.tensor(idx, device=self._device)] = self.encode_ids(ids, mask).float()
         return out
+
+
+    def _similarity_rows(self, X: torch.Tensor) -> torch.Tensor:
+        from . import ops
+        if self.similarity == "cos_sim":
+            return ops.normalize_rows(ops.pad_dim(X))
+        if self.similarity == "dot_score":
+            return X
+        raise ValueError(f"SpladeEncoder.similarity: 'cos_sim' or 'dot_score', got {self.similarity!r}")
+
+    @torch.no_grad()
+    def index(self, documents, batch_size: int = 64):
+        """Inverted index (ops.SparseIndex) of the documents' SPLADE vectors, L2-normalised for cos_sim: encoded INDEX_BLOCK documents at a
+        time and handed to ops.sparse_index_from_blocks -- the corpus is never one dense [N, vocab] matrix (1.1 TB at mMARCO size)."""
+        from . import ops
+
+        def blocks():
+            for b0 in range(0, len(documents), self.INDEX_BLOCK):
+                yield b0, self._similarity_rows(self.encode(documents[b0: b0 + self.INDEX_BLOCK], batch_size=batch_size, query_mode=False))
+        return ops.sparse_index_from_blocks(blocks(), self.dim, N=len(documents), device=self._device)
+
+    @torch.no_grad()
+    def search_index(self, query_embeddings: torch.Tensor, index, query_chunk_size: int = 100, doc_chunk_size: int = 500000, topk: int = 10):
+        """search() on already encoded queries [Q, >= vocab] and an index of the documents (index()): per block of query_chunk_size queries,
+        the sparse kernel's chunked top-k over the index (distributed.ShardedSparseIndex, pieces of doc_chunk_size documents rounded up to
+        whole slices).  Neither chunk size changes the result.  Per query a list of {"doc_id", "score"}, score descending (ties: ascending
+        doc_id), min(topk, N) entries."""
+        from . import ops
+        from .distributed import ShardedSparseIndex
+        Qn = self._similarity_rows(query_embeddings.float())
+        shard = ShardedSparseIndex(index, 0)
+        shard.CHUNK = ops.round_up(max(1, int(doc_chunk_size)), ops.sparse_slice_docs())
+        k = min(int(topk), index.N)
+        out = []
+        for q0 in range(0, Qn.shape[0], max(1, int(query_chunk_size))):
+            if k <= 0:
+                out.extend([] for _ in range(min(Qn.shape[0] - q0, query_chunk_size)))
+                continue
+            sc, ids = shard.local_topk(*ops.sparse_rows(Qn[q0: q0 + query_chunk_size], index.V), k)
+            for srow, irow in zip(sc.cpu().tolist(), ids.cpu().tolist()):
+                out.append([{"doc_id": i, "score": v} for v, i in zip(srow, irow) if i >= 0])
+        return out
+
+    @torch.no_grad()
+    def search(self, queries, documents, batch_size: int = 32, query_chunk_size: int = 100, doc_chunk_size: int = 500000, topk: int = 10):
+        """BaseModel.search (splade/base.py:199-251): the top-k documents of every query, per query a list of {"doc_id": position in
+        `documents`, "score"}, score descending.  The documents become an inverted index (index()) and the queries' term lists are scored
+        against it by the sparse kernel with the top-k filter fused in -- no [queries, documents] score matrix, no dense corpus."""
+        Qe = self.encode(queries, batch_size=batch_size, query_mode=True)
+        return self.search_index(Qe, self.index(documents, batch_size=batch_size), query_chunk_size, doc_chunk_size, topk)
 
 
 class ColbertEncoder(_Base):

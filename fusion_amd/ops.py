@@ -839,6 +839,30 @@ def topk_update(scores: torch.Tensor, id_base: int, run_scores: torch.Tensor, ru
     return ns, ni, overflow
 
 
+def stream_window(seen: int, k: int, cap: int) -> int:
+    """Documents one threshold of a TopkStream may serve: expected candidates k * window / seen <= cap / 2."""
+    return max(64, (cap // 2) * seen // k // 64 * 64)
+
+
+def sparse_pieces(doc_lo: int, doc_hi: int, seen: int, pending: int, k: int, cap: int, slice_docs: int):
+    """How TopkStream.feed_sparse cuts [doc_lo, doc_hi): [(lo, hi, fold after this piece)], ascending and back to back.  The fold window
+    (stream_window) is rounded down to whole slices, at least one; a piece ends where the window does (or at doc_hi, which may be off the
+    grain) and the stream folds there; the bookkeeping -- seen, pending -- is TopkStream's own.  Host arithmetic only."""
+    out = []
+    lo = doc_lo
+    while lo < doc_hi:
+        win = max(slice_docs, stream_window(seen, k, cap) // slice_docs * slice_docs)
+        room = max(slice_docs, (win - pending) // slice_docs * slice_docs)
+        hi = min(doc_hi, lo + room)
+        pending += hi - lo
+        fold = pending >= win
+        if fold:
+            seen, pending = seen + pending, 0
+        out.append((lo, hi, fold))
+        lo = hi
+    return out
+
+
 class TopkStream:
     """Running per-row top-k over a stream of score chunks (documents in ascending id order): only scores above a row's
     threshold (its k-th best when the list was last folded) are kept as candidates (fz_topk_filter_append_f32), and candidates
@@ -874,6 +898,7 @@ class TopkStream:
         self.exact_on_overflow = bool(exact_on_overflow)
         self.windows_redone = 0
         self._pieces = []                # what the current window was fed with: ("scores", piece, id_base) | ("gemm", Qn, Dpiece, id_base)
+                                         #   | ("sparse", index, (qoff, qterms, qw), doc_lo, doc_hi, id_base)
         self._unheld = False             # ... and whether some of it was fed without being held (feed(hold=False))
         self.unrepairable = False        # host latch: a window fed WITHOUT hold overflowed -- nothing the stream holds can repair it, the device
                                          #   flag stays set and the caller redoes the search; later windows are neither read nor redone
@@ -882,7 +907,7 @@ class TopkStream:
 
     def _window(self) -> int:
         """documents one threshold may serve: expected candidates k * window / seen <= cap / 2"""
-        return max(64, (self.cap // 2) * self.seen // self.k // 64 * 64)
+        return stream_window(self.seen, self.k, self.cap)
 
     def feed(self, scores: torch.Tensor, id_base: int, hold: bool = False):
         """scores [rows, n] of documents id_base .. id_base + n - 1.
@@ -933,6 +958,27 @@ class TopkStream:
                 self.fold()
                 if mark: mark("shard_topk_stream")
 
+    def feed_sparse(self, index, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, doc_lo: int, doc_hi: int, id_base: int, mark=None):
+        """Score documents [doc_lo, doc_hi) of a SparseIndex against the queries' term lists and keep what beats the thresholds, in ONE kernel
+        per piece (fz_sparse_dot_filter_f32: the inverted-index walk with the filter in place of the plane store).  Document d gets the id
+        id_base + d.  The range is cut at the fold windows, rounded down to whole slices (sparse_pieces); the pieces hold views of the
+        index and the query lists, nothing is copied."""
+        Q = _sparse_queries(qoff, qterms, qw, "TopkStream.feed_sparse")
+        _need(Q == self.rows, "TopkStream.feed_sparse: one query per running list")
+        doc_lo, doc_hi = _sparse_range(index, doc_lo, doc_hi, "TopkStream.feed_sparse")
+        lib = _lib.lib()
+        self.unordered = True
+        for lo, hi, fold in sparse_pieces(doc_lo, doc_hi, self.seen, self.pending, self.k, self.cap, sparse_slice_docs()):
+            check(lib.fz_sparse_dot_filter_f32(_ptr(index.toff), _ptr(index.pdoc), _ptr(index.pw), _ptr(index.slice_off), _ptr(qoff), _ptr(qterms),
+                                               _ptr(qw), Q, index.N, lo, hi, int(id_base), _ptr(self.tau), _ptr(self.cand_s), _ptr(self.cand_i),
+                                               _ptr(self.cand_len), self.cap, _ptr(self.overflow), _stream(qoff)), "fz_sparse_dot_filter_f32")
+            if mark: mark("shard_sparse_filter")
+            self._pieces.append(("sparse", index, (qoff, qterms, qw), lo, hi, int(id_base)))
+            self.pending += hi - lo
+            if fold:
+                self.fold()
+                if mark: mark("shard_topk_stream")
+
     def fold(self):
         if self.pending == 0:
             return
@@ -955,6 +1001,9 @@ class TopkStream:
                     if kind == "gemm":
                         Qn_, piece, base = args
                         sc = dot_scores(Qn_, piece)
+                    elif kind == "sparse":
+                        index, ql, lo, hi, ib = args
+                        sc, base = sparse_dot(index, *ql, doc_lo=lo, doc_hi=hi), ib + lo
                     else:
                         sc, base = args
                     if sc.shape[1] == 0:
@@ -1145,24 +1194,43 @@ def density(X: torch.Tensor) -> float:
     return float(torch.count_nonzero(X).item()) / max(1, X.numel())
 
 
+def sparse_index_from_blocks(blocks, V: int, N: int | None = None, device=None) -> SparseIndex:
+    """Inverted index of a corpus given as row blocks -- an iterable of (doc_base, rows [n, >= V] float32) in ascending document order --
+    without the corpus ever being one dense matrix: every block contributes its non-zeros (document, term, weight), then ONE stable sort by
+    term puts them in term order, documents staying ascending inside a term; documents no block covers have no postings.  Memory while it
+    sorts: 12 bytes per posting for the postings and as much again for the sort's output.  N: documents in all (default: the end of the last
+    block)."""
+    docs, terms, vals = [], [], []
+    end = 0
+    for r0, blk in blocks:
+        _dev(blk, torch.float32, "sparse_index_from_blocks(rows)")
+        _need(int(r0) >= end, "sparse_index_from_blocks: blocks must come in ascending document order")
+        device = blk.device
+        blk = blk[:, :V]
+        nz = blk.nonzero()
+        docs.append((nz[:, 0] + int(r0)).int()); terms.append(nz[:, 1].int()); vals.append(blk[nz[:, 0], nz[:, 1]])
+        end = int(r0) + blk.shape[0]
+    N = end if N is None else int(N)
+    _need(N >= end, f"sparse_index_from_blocks: the blocks reach document {end}, beyond N = {N}")
+    device = device if device is not None else "cuda"
+    doc = torch.cat(docs) if docs else torch.zeros(0, dtype=torch.int32, device=device)
+    term = torch.cat(terms) if terms else torch.zeros(0, dtype=torch.int32, device=device)
+    val = torch.cat(vals) if vals else torch.zeros(0, dtype=torch.float32, device=device)
+    del docs, terms, vals
+    order = torch.sort(term, stable=True).indices           # documents were appended ascending: stable keeps them so inside a term
+    toff = torch.zeros(V + 1, dtype=torch.int64, device=device)
+    toff[1:] = torch.cumsum(torch.bincount(term, minlength=V), 0)
+    del term
+    return SparseIndex(toff, doc[order].contiguous(), val[order].contiguous(), N, V)
+
+
 def sparse_index(Dn: torch.Tensor, V: int | None = None, rows: int = 4096) -> SparseIndex:
-    """Inverted index of the rows of Dn [N, >= V] (already L2-normalised, e.g. ops.normalize_rows): built from row blocks (a block's
-    non-zeros, then one stable sort by term -- documents stay ascending inside a term)."""
+    """Inverted index of the rows of Dn [N, >= V] (already L2-normalised, e.g. ops.normalize_rows): sparse_index_from_blocks over row blocks
+    of Dn."""
     _dev(Dn, torch.float32, "sparse_index(Dn)")
     N = Dn.shape[0]
     V = Dn.shape[1] if V is None else int(V)
-    docs, terms, vals = [], [], []
-    for r0 in range(0, N, rows):
-        blk = Dn[r0: r0 + rows, :V]
-        nz = blk.nonzero()
-        docs.append((nz[:, 0] + r0).int()); terms.append(nz[:, 1]); vals.append(blk[nz[:, 0], nz[:, 1]])
-    doc = torch.cat(docs) if docs else torch.zeros(0, dtype=torch.int32, device=Dn.device)
-    term = torch.cat(terms) if terms else torch.zeros(0, dtype=torch.int64, device=Dn.device)
-    val = torch.cat(vals) if vals else torch.zeros(0, dtype=torch.float32, device=Dn.device)
-    order = torch.sort(term, stable=True).indices           # documents were appended ascending: stable keeps them so inside a term
-    toff = torch.zeros(V + 1, dtype=torch.int64, device=Dn.device)
-    toff[1:] = torch.cumsum(torch.bincount(term, minlength=V), 0)
-    return SparseIndex(toff, doc[order].contiguous(), val[order].contiguous(), N, V)
+    return sparse_index_from_blocks(((r0, Dn[r0: r0 + rows]) for r0 in range(0, N, rows)), V, N=N, device=Dn.device)
 
 
 def sparse_rows(Qn: torch.Tensor, V: int | None = None):
@@ -1176,19 +1244,41 @@ def sparse_rows(Qn: torch.Tensor, V: int | None = None):
     return qoff, nz[:, 1].int().contiguous(), blk[nz[:, 0], nz[:, 1]].contiguous()
 
 
-def sparse_dot(index: SparseIndex, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-    """scores[q][d] = sum over query q's terms of qw * (document d's weight of that term): [Q, N] float32 plane."""
-    for t, dt, what in ((qoff, torch.int64, "qoff"), (qterms, torch.int32, "qterms"), (qw, torch.float32, "qw")):
-        _need(_dev(t, dt, f"sparse_dot({what})").is_contiguous(), f"sparse_dot({what}) must be contiguous")
+def _sparse_queries(qoff, qterms, qw, what):
+    for t, dt, name in ((qoff, torch.int64, "qoff"), (qterms, torch.int32, "qterms"), (qw, torch.float32, "qw")):
+        _need(_dev(t, dt, f"{what}({name})").is_contiguous(), f"{what}({name}) must be contiguous")
     Q = qoff.numel() - 1
-    _need(Q >= 0 and qterms.numel() == qw.numel(), "sparse_dot: qoff must hold Q + 1 offsets, qterms and qw one entry per non-zero")
+    _need(Q >= 0 and qterms.numel() == qw.numel(), f"{what}: qoff must hold Q + 1 offsets, qterms and qw one entry per non-zero")
+    return Q
+
+
+def sparse_slice_docs() -> int:
+    """Documents per workgroup slice of the sparse kernels: document ranges start on a multiple of it."""
+    return int(_lib.lib().fz_sparse_slice_docs())
+
+
+def _sparse_range(index: SparseIndex, doc_lo: int, doc_hi: int | None, what: str):
+    doc_hi = index.N if doc_hi is None else int(doc_hi)
+    S = sparse_slice_docs()
+    _need(0 <= doc_lo <= doc_hi <= index.N and doc_lo % S == 0 and (doc_hi % S == 0 or doc_hi == index.N),
+          f"{what}: [doc_lo, doc_hi) = [{doc_lo}, {doc_hi}) must start on a multiple of {S} and end on one or at N = {index.N}")
+    return int(doc_lo), doc_hi
+
+
+def sparse_dot(index: SparseIndex, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, out: torch.Tensor | None = None,
+               doc_lo: int = 0, doc_hi: int | None = None) -> torch.Tensor:
+    """scores[q][j] = sum over query q's terms of qw * (document doc_lo + j's weight of that term): [Q, doc_hi - doc_lo] float32 plane
+    (default: all N documents).  doc_lo a multiple of sparse_slice_docs(), doc_hi one too or N; a range's columns are the full plane's, bit
+    for bit."""
+    Q = _sparse_queries(qoff, qterms, qw, "sparse_dot")
+    doc_lo, doc_hi = _sparse_range(index, doc_lo, doc_hi, "sparse_dot")
     if out is None:
-        out = alloc_plane(Q, index.N, torch.float32, qoff.device)
+        out = alloc_plane(Q, doc_hi - doc_lo, torch.float32, qoff.device)
     else:
         _dev(out, torch.float32, "sparse_dot(out)")
-        _need(tuple(out.shape) == (Q, index.N), f"sparse_dot(out): expected shape {(Q, index.N)}, got {tuple(out.shape)}")
-    check(_lib.lib().fz_sparse_dot_f32(_ptr(index.toff), _ptr(index.pdoc), _ptr(index.pw), _ptr(index.slice_off), _ptr(qoff), _ptr(qterms), _ptr(qw),
-                                       Q, index.N, _ptr(out), _ld(out), _stream(qoff)), "fz_sparse_dot_f32")
+        _need(tuple(out.shape) == (Q, doc_hi - doc_lo), f"sparse_dot(out): expected shape {(Q, doc_hi - doc_lo)}, got {tuple(out.shape)}")
+    check(_lib.lib().fz_sparse_dot_range_f32(_ptr(index.toff), _ptr(index.pdoc), _ptr(index.pw), _ptr(index.slice_off), _ptr(qoff), _ptr(qterms),
+                                             _ptr(qw), Q, index.N, doc_lo, doc_hi, _ptr(out), _ld(out), _stream(qoff)), "fz_sparse_dot_range_f32")
     return out
 
 

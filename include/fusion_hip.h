@@ -401,6 +401,19 @@ int fz_sparse_slice_docs(void);
 int fz_sparse_slice_offsets(const int64_t* toff, const int32_t* pdoc, int V, int N, int64_t* out, void* stream);
 int fz_sparse_dot_f32(const int64_t* toff, const int32_t* pdoc, const float* pw, const int64_t* slice_off, const int64_t* qoff,
                       const int32_t* qterms, const float* qw, int Q, int N, float* scores, int lds, void* stream);
+/* (ABI 20) The same scores for the documents [doc_lo, doc_hi) of the index only: doc_lo % fz_sparse_slice_docs() == 0, doc_hi a multiple of it
+ * or N; scores [Q][lds], lds >= doc_hi - doc_lo, column j = document doc_lo + j -- bit for bit the full plane's column doc_lo + j (same chain of
+ * adds per document).  fz_sparse_dot_f32 is this call with [0, N). */
+int fz_sparse_dot_range_f32(const int64_t* toff, const int32_t* pdoc, const float* pw, const int64_t* slice_off, const int64_t* qoff,
+                            const int32_t* qterms, const float* qw, int Q, int N, int doc_lo, int doc_hi, float* scores, int lds, void* stream);
+/* (ABI 20) The corpus-scale SPLADE search step (splade/base.py:199-251's chunked top-k): the same walk over [doc_lo, doc_hi) with the streaming
+ * top-k's threshold filter in place of the plane -- NO score plane is written; document d enters query q's candidate list iff
+ * !(score <= tau[q]) (greater, or NaN), appended as (score, id_base + d) -- the rule and lists of fz_dot_scores_filter_f32: cand_scores /
+ * cand_ids [Q][cap], cand_len [Q] int32 (may run past cap: the excess is dropped and *overflow set to 1), in arrival order, i.e. for
+ * fz_topk_fold_f32(unordered = 1).  tau [Q]. */
+int fz_sparse_dot_filter_f32(const int64_t* toff, const int32_t* pdoc, const float* pw, const int64_t* slice_off, const int64_t* qoff,
+                             const int32_t* qterms, const float* qw, int Q, int N, int doc_lo, int doc_hi, int64_t id_base, const float* tau,
+                             float* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow, void* stream);
 
 /* ---- encoder side: the per-sequence parts of SentenceTransformer.encode (hybrid.py:97-102) on PACKED token rows -- */
 /* Self-attention of a BERT/CamemBERT layer for ragged sequences without padding: for every sequence and head,
