@@ -70,6 +70,15 @@ def _need(cond: bool, msg: str):
         raise ValueError(msg)
 
 
+MAX_SYSTEMS = 8   # FZ_MAX_SYSTEMS (csrc/common.h): every fusion kernel's argument block holds this many systems
+
+
+def _max_systems(S: int, what: str):
+    """Host-side system-count contract of the fusion entry points, checked before any tensor is looked at: the C ABI would only
+    answer a generic FZ_ERR_ARG."""
+    _need(S <= MAX_SYSTEMS, f"{what}: {S} systems, but fusion takes at most {MAX_SYSTEMS} (FZ_MAX_SYSTEMS)")
+
+
 def _same_shape(ts, what: str):
     shapes = {tuple(t.shape) for t in ts if t is not None}
     _need(len(shapes) <= 1, f"{what}: planes differ in shape: {sorted(shapes)}")
@@ -352,6 +361,7 @@ def select_topk(fused: torch.Tensor, pos: torch.Tensor | None, k: int, cap: int 
 # ---------------------------------------------------------------------------------------
 def fuse_rank(ranks: list[torch.Tensor], lens: torch.Tensor, method: str) -> torch.Tensor:
     """rrf / bcf in float64 (hybrid.py:248-252,301-304). ranks[s] [Q,N] int32 planes, lens [S,Q] int32."""
+    _max_systems(len(ranks), "fuse_rank")
     for r in ranks:
         _dev(r, torch.int32, "fuse_rank(ranks)")
     _same_shape(ranks, "fuse_rank")
@@ -374,6 +384,7 @@ def sort_rank_fused(ranks: list[torch.Tensor], lens: torch.Tensor, method: str, 
     sort_rows_desc(fuse_rank(ranks, lens, method), init_order / init_rank, row_len) without the float64 plane in between
     (fz_sort_rank_fused_desc).  Returns (order, fused scores in list order [float64], rank | None) -- bit-identical to the two calls.
     Rows longer than one workgroup holds raise FusionHipError(FZ_ERR_UNSUPPORTED): callers take the two calls there."""
+    _max_systems(len(ranks), "sort_rank_fused")
     for r in ranks:
         _dev(r, torch.int32, "sort_rank_fused(ranks)")
     _same_shape(ranks, "sort_rank_fused")
@@ -491,6 +502,7 @@ class PreparedTables:
 def nsf_tables_prepare(distr: list[torch.Tensor], norm: str) -> PreparedTables | None:
     """None when a table is too long for LDS (fuse_nsf then searches it in global memory)."""
     _need(norm in ("percentile-rank", "normal-curve-equivalent"), f"nsf_tables_prepare: {norm!r} has no tables")
+    _max_systems(len(distr), "nsf_tables_prepare")
     distr = [_dev(d, torch.float32, "distr").contiguous() for d in distr]
     S = len(distr)
     _need(all(d.dim() == 1 and d.numel() > 0 for d in distr), "nsf_tables_prepare: tables must be non-empty 1-d tensors")
@@ -522,6 +534,7 @@ def fuse_nsf(planes: list[torch.Tensor], ranks: list[torch.Tensor | None] | None
     valid_bits[s] (optional): the validity of system s as a bitmap (rank_to_bitmap), read instead of its rank plane.
     tables (optional): nsf_tables_prepare(distr, norm) of these very tables, to prepare them once for many calls; False: stay on
     fz_fuse_nsf_f32 whatever the table size (its all-tables-in-LDS kernel or its global-memory search: what tests compare against)."""
+    _max_systems(len(planes), "fuse_nsf")
     for p in planes:
         _dev(p, torch.float32, "fuse_nsf(planes)")
     S = len(planes)
@@ -662,6 +675,7 @@ def zero_unlisted_(plane: torch.Tensor, rank: torch.Tensor) -> torch.Tensor:
 
 def fuse_none(planes: list[torch.Tensor], ranks: list[torch.Tensor | None] | None, weights) -> torch.Tensor:
     """'none' / unknown normalisation: float64 passthrough (hybrid.py:280,291,304)."""
+    _max_systems(len(planes), "fuse_none")
     for p in planes:
         _dev(p, torch.float32, "fuse_none(planes)")
     S = len(planes)
@@ -695,6 +709,7 @@ def fuse_wsum(planes: list[torch.Tensor], ranks: list[torch.Tensor | None] | Non
     (per system); narrow[s] = the weight is weak / float32 (fl32 product; the document's sum stays fl32 until its first
     float64 product).  narrow=None: everything float64 (the 'none' passthrough, hybrid.py:280,291,304)."""
     S = len(planes)
+    _max_systems(S, "fuse_wsum")
     for p in planes:
         _dev(p, None, "fuse_wsum(planes)")
         if p.dtype not in (torch.float32, torch.float64):
@@ -722,6 +737,7 @@ def fuse_wsum(planes: list[torch.Tensor], ranks: list[torch.Tensor | None] | Non
 def insertion_order(orders: list[torch.Tensor], lens: torch.Tensor, N: int, want_pos: bool = False):
     """First-insertion order of the fused dict (hybrid.py:301-304). Returns (ins_order [Q,N] int32, U [Q] int32), with want_pos also the
     inverse plane pos [Q,N] int32 (first-insertion position of every document, -1 = in no list)."""
+    _max_systems(len(orders), "insertion_order")
     for o in orders:
         _dev(o, torch.int32, "insertion_order(orders)")
     _same_shape(orders, "insertion_order")
@@ -746,6 +762,7 @@ def gold_ranks(T: list[torch.Tensor], pos: torch.Tensor, weights: torch.Tensor, 
     T[s] [Q,N] normalised planes, pos [Q,N] int32 insertion positions (-1 absent), weights [W,S] fp32,
     gold [Q,G] int32 corpus positions (-1 pad) -> ranks [W,Q,G] int32 (0 where gold is padding / unlisted: check pos).
     float64 weights select the float64 sweep (np.float64 grid weights: NumPy promotes the products and sums)."""
+    _max_systems(len(T), "gold_ranks")
     for t in T:
         _dev(t, torch.float32, "gold_ranks(T)")
     _dev(pos, torch.int32, "gold_ranks(pos)")

@@ -351,6 +351,7 @@ class Aggregator:
     def fuse(cls, ranked_lists: dict, method: str, normalization: str = None, linear_weights: dict[str, float] = None,
              percentile_distributions: dict[str, np.ndarray] = None, return_topk: int = 1000, *, as_device: bool = False):
         """hybrid.py:170-220.  `ranked_lists`: system -> RankedLists (reference format) or system -> RankedSystem (device)."""
+        ops._max_systems(len(ranked_lists), "Aggregator.fuse")
         fused = cls.fuse_device(cls._to_device(ranked_lists), method, normalization, linear_weights, percentile_distributions)
         if as_device:
             return fused
@@ -365,6 +366,7 @@ class Aggregator:
         predictions(1000), hybrid.py:537) -- the rows are selected, not sorted (ops.select_topk); the entries and their order are those
         of the full lists, bit for bit.  Aggregator.fuse always returns the full lists, as the reference does."""
         names = list(systems.keys())
+        ops._max_systems(len(names), "Aggregator.fuse_device")
         S = [systems[n] for n in names]
         Q = S[0].Q
         assert all(s.Q == Q for s in S), (
@@ -448,6 +450,7 @@ class Aggregator:
         systems are normalised once and one counting kernel yields the fused ranks of the gold documents for all weight
         vectors (csrc/tune.hip) -- every metric is a function of those ranks."""
         from ..utils.metrics import metrics_from_gold_ranks
+        ops._max_systems(len(ranked_lists), "Aggregator.tune")
         systems = cls._to_device(ranked_lists)
         names = list(systems.keys())
         S = [systems[n] for n in names]

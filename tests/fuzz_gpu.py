@@ -203,8 +203,13 @@ def case_rank_fused(rng):
 
 
 def case_fuse(rng):
-    S, Q = int(rng.integers(1, 5)), int(rng.integers(1, 5))
-    N = int(rng.choice([rng.integers(1, 300), rng.integers(300, 9000), rng.integers(9000, 33000)]))
+    """1 to FZ_MAX_SYSTEMS = 8 systems; now and then more rows than the 256 persistent workgroups of the nsf row kernel (then rows
+    of at most ~10,000 columns: the oracle's cost), or rows past its 32,768 columns (the two-pass form)"""
+    S = int(rng.integers(1, 9))
+    Q = int(rng.integers(1, 5)) if rng.random() < 0.85 else int(rng.integers(5, 301))
+    N = int(rng.choice([rng.integers(1, 300), rng.integers(300, 9000), rng.integers(9000, 33000), rng.integers(32769, 40001)],
+                       p=[0.3, 0.3, 0.3, 0.1]))
+    N = min(N, max(1, 3_000_000 // Q))
     partial = rng.random() < 0.5
     planes, ranks, orders, lens = systems(rng, S, Q, N, partial)
     what = rng.choice(["rrf", "bcf", "none", "insertion"] + list(NSF_TOL))
