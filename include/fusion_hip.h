@@ -80,7 +80,11 @@ int fz_dot_scores_filter_f32(const float* Qn, int ldq, const float* Dn, int ldd,
  * Qtok [Q][Lq][dim] fp16; Dtok packed ragged [sumL][dim] fp16, doc j owns rows [Doff[j], Doff[j+1]);
  * Doff [N+1] int64 (device), sumL = Doff[N] (known to the host: rows of Dtok); max_doc_len = upper bound of the
  * document lengths (the reference's doc_maxlen = 512, hybrid.py:129; tokens beyond it are ignored; <= 16384).
- * dim must be 128 (run_colbert.sh:26); Lq in {32, 64, 128} (64: hybrid.py:129).  Empty documents score 0. */
+ * dim must be 128 (run_colbert.sh:26); Lq in {32, 64, 128} (64: hybrid.py:129).  Empty documents score 0.
+ * Special values: dot products are IEEE fp32 (+-inf carried through, inf * 0 and inf - inf give NaN); the maximum over a
+ * document's tokens is fmaxf, which DROPS a NaN term -- the formula in plain IEEE arithmetic would propagate it -- and a
+ * query token whose dot products with every token of a document are NaN contributes the empty maximum, -inf
+ * (tests/test_gpu_maxsim_edges.py::test_special_values).  L2-normalised token vectors never get there. */
 int fz_maxsim_f16(const void* Qtok, const void* Dtok, const int64_t* Doff, int64_t sumL, int max_doc_len, int Q, int Lq, int N,
                   int dim, float* scores, int lds, void* stream);
 

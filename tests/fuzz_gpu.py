@@ -10,6 +10,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from fusion_amd import ops
 from oracle import oracle
 from helpers import quantile_table
+from maxsim_cases import grid_corpus, grid_queries, unit_corpus, unit_queries
 
 NSF_TOL = {"min-max": 0.0, "z-score": 2e-6, "arctan": 1e-6, "percentile-rank": 0.0, "normal-curve-equivalent": 1e-4}
 
@@ -305,23 +306,39 @@ def case_layernorm(rng):
 
 
 def case_maxsim(rng):
+    """Part of the time: max_doc_len below the longest document (the oracle has no such parameter: it gets the kept tokens, packed),
+    documents of up to 2,000 tokens (docs_per_wg < 32), Doff[0] > 0 with rows beyond Doff[N], and grid-valued inputs with poisoned
+    guards and tails (maxsim_cases.py), on which the bar is equality."""
     Q, N, Lq = int(rng.choice([rng.integers(1, 12), rng.integers(12, 80)])), int(rng.integers(1, 120)), int(rng.choice([32, 64, 128]))
-    lens = rng.integers(0, int(rng.choice([40, 200, 600])), N)
-    Doff = np.zeros(N + 1, dtype=np.int64); np.cumsum(lens, out=Doff[1:])
-    Dtok = rng.normal(0, 1, (max(int(Doff[-1]), 1), 128)).astype(np.float32)
-    Dtok /= np.linalg.norm(Dtok, axis=1, keepdims=True)
-    Dtok = Dtok.astype(np.float16)[: int(Doff[-1])] if Doff[-1] > 0 else np.zeros((0, 128), dtype=np.float16)
-    Qtok = rng.normal(0, 1, (Q, Lq, 128)).astype(np.float32)
-    Qtok /= np.linalg.norm(Qtok, axis=2, keepdims=True)
-    Qtok = Qtok.astype(np.float16)
+    hi = int(rng.choice([40, 200, 600, 2000]))
+    if hi == 2000:      # the host cost of the oracle bounds the case
+        Q, N = min(Q, 12), min(N, 12)
+    lens = rng.integers(0, hi, N)
+    longest = int(max(lens.max(), 1))
+    m = int(rng.integers(1, longest + 1)) if rng.random() < 0.4 else longest if rng.random() < 0.7 else int(rng.integers(longest, 2001))
+    pre, post = (int(rng.integers(1, 50)), int(rng.integers(0, 50))) if rng.random() < 0.3 else (0, 0)
+    grid = rng.random() < 0.3
+    if grid:
+        Qtok = grid_queries(rng, Q, Lq)
+        Dtok, Doff = grid_corpus(rng, lens, m, guards=True, pre=pre, post=post)
+    else:
+        Qtok = unit_queries(rng, Q, Lq)
+        Dtok, Doff = unit_corpus(rng, lens, pre=pre, post=post)
     if Dtok.shape[0] == 0:   # every document empty: all scores 0
         got = ops.maxsim(dev(Qtok), torch.zeros((0, 128), dtype=torch.float16, device="cuda"), dev(Doff), max_doc_len=1).cpu().numpy()
         assert got.shape == (Q, N) and not got.any()
         return "maxsim with every document empty"
-    got = ops.maxsim(dev(Qtok), dev(Dtok), dev(Doff), max_doc_len=int(max(lens.max(), 1))).cpu().numpy()
-    exp = oracle.maxsim(Qtok.astype(np.float32), Dtok.astype(np.float32), Doff)
-    assert np.max(np.abs(got - exp)) <= 1e-4 * max(1, Lq / 32)
-    return f"maxsim Q={Q} N={N} Lq={Lq} sumL={int(Doff[-1])}"
+    got = ops.maxsim(dev(Qtok), dev(Dtok), dev(Doff), max_doc_len=m).cpu().numpy()
+    kept = np.minimum(lens, m)
+    koff = np.zeros(N + 1, dtype=np.int64); np.cumsum(kept, out=koff[1:])
+    rows = np.concatenate([np.arange(Doff[d], Doff[d] + kept[d]) for d in range(N)]) if koff[-1] else np.zeros(0, dtype=np.int64)
+    Dkept = Dtok[rows] if len(rows) else np.zeros((1, 128), dtype=np.float16)       # (the oracle wants a pointer)
+    exp = oracle.maxsim(Qtok.astype(np.float32), Dkept.astype(np.float32), koff)
+    if grid:
+        assert np.array_equal(got, exp)
+    else:
+        assert np.max(np.abs(got - exp)) <= 1e-4 * max(1, Lq / 32)
+    return f"maxsim Q={Q} N={N} Lq={Lq} sumL={int(Doff[-1] - Doff[0])} max_doc_len={m} of {longest} pre={pre} {'grid' if grid else 'unit'}"
 
 
 
