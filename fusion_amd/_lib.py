@@ -75,6 +75,9 @@ _PROTOS = {
     "fz_fuse_wsum_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "fz_insertion_order_workspace_bytes": (_sz, [_i, _i]),
     "fz_insertion_order": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "fz_lists_max_entries": (_i, []),
+    "fz_lists_join_workspace_bytes": (_sz, [_i, _i]),
+    "fz_lists_join": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "fz_topk_max_k": (_i, []),
     "fz_topk_workspace_bytes": (_sz, [_i, _i, _i]),
     "fz_topk_rows_f32": (_i, [_vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _sz, _vp]),

@@ -757,6 +757,74 @@ def insertion_order(orders: list[torch.Tensor], lens: torch.Tensor, N: int, want
     return (ins, U, pos) if want_pos else (ins, U)
 
 
+LISTS_METHODS = {"rrf": 0, "bcf": 1, "wsum32": 2, "wsum64": 3}   # fz_lists_method
+
+
+def lists_max_entries() -> int:
+    """The largest sum of list widths one fz_lists_join call takes (the union of a query's ids lives in one workgroup's LDS)."""
+    return int(_lib.lib().fz_lists_max_entries())
+
+
+def lists_join(ids: list[torch.Tensor], lens: list[torch.Tensor], method: str, values: list[torch.Tensor] | None = None,
+               weights=None, narrow=None):
+    """Per-query id join of S systems' top-k lists (fz_lists_join; hybrid.py:293-307 on lists of any int64 ids).
+    ids[s] [Q, k_s] int64, lens[s] [Q] int32 (entries past a list's length are never read), k_s may differ between systems.
+    method: 'rrf' | 'bcf' (contributions from the list positions, float64), 'wsum32' (values[s] [Q, k_s] float32, fl32(value * w),
+    float32 sum) or 'wsum64' (values float32 or float64 per system, narrow[s] as in fuse_wsum; float64 sum).
+    Returns (out_ids [Q, n] int64, out_scores [Q, n], out_len [Q] int32), n = sum of k_s, the columns in the fused dict's
+    first-insertion order: sort_rows_desc(out_scores, row_len=out_len) ranks them with the reference's tie rule.  Columns past
+    out_len hold (-1, -inf).  An id listed twice inside one list raises ValueError (one flag read per call)."""
+    S = len(ids)
+    _max_systems(S, "lists_join")
+    _need(S >= 1, "lists_join: no system")
+    _need(method in LISTS_METHODS, f"lists_join: unknown method {method!r} (one of {sorted(LISTS_METHODS)})")
+    _need(len(lens) == S, f"lists_join: {S} id lists but {len(lens)} length vectors")
+    wsum = method in ("wsum32", "wsum64")
+    if wsum:
+        _need(values is not None and len(values) == S, f"lists_join({method}): needs {S} value planes")
+        _need(weights is not None and len(weights) == S, f"lists_join({method}): needs {S} weights")
+    ids = [_dev(t, torch.int64, "lists_join(ids)") for t in ids]
+    Q = ids[0].shape[0]
+    for t in ids:
+        _need(t.dim() == 2 and t.shape[0] == Q, f"lists_join(ids): every system needs a [{Q}, k] tensor, got {tuple(t.shape)}")
+    total = sum(int(t.shape[1]) for t in ids)
+    cap = lists_max_entries()
+    _need(total <= cap, f"lists_join: the lists of one query hold up to {total} entries, a join takes at most {cap} (fz_lists_max_entries)")
+    lens = [_dev(t, torch.int32, "lists_join(lens)").contiguous() for t in lens]
+    for t in lens:
+        _need(t.numel() == Q, f"lists_join(lens): expected {Q} lengths, got {t.numel()}")
+    vals = [None] * S
+    if wsum:
+        for s, v in enumerate(values):
+            _dev(v, None, "lists_join(values)")
+            if v.dtype != torch.float32 and not (method == "wsum64" and v.dtype == torch.float64):
+                raise TypeError(f"lists_join({method}): value planes must be float32{' or float64' if method == 'wsum64' else ''}, got {v.dtype}")
+            _need(tuple(v.shape) == tuple(ids[s].shape), f"lists_join(values): system {s} has ids {tuple(ids[s].shape)} but values {tuple(v.shape)}")
+            if _ld(v) != _ld(ids[s]):       # one row stride per system: ids and values side by side
+                ids[s], v = ids[s].contiguous(), v.contiguous()
+            vals[s] = v
+    dev = ids[0].device
+    ld_out = max(round_up(total, _PAD), _PAD)
+    f32 = method == "wsum32"
+    out_ids = torch.full((max(Q, 1), ld_out), -1, dtype=torch.int64, device=dev)[:Q, :total]
+    out_scores = torch.full((max(Q, 1), ld_out), float("-inf"), dtype=torch.float32 if f32 else torch.float64, device=dev)[:Q, :total]
+    out_len = torch.zeros(Q, dtype=torch.int32, device=dev)
+    lib = _lib.lib()
+    wsb = int(lib.fz_lists_join_workspace_bytes(S, Q))
+    ws = torch.zeros(max(wsb, 4), dtype=torch.uint8, device=dev)
+    n_h = (C.c_int32 * S)(*[int(t.shape[1]) for t in ids])
+    ld_h = (C.c_int32 * S)(*[max(_ld(t), int(t.shape[1])) for t in ids])
+    w = (C.c_double * S)(*[float(x) for x in weights]) if wsum else None
+    v64 = (C.c_int32 * S)(*[int(v.dtype == torch.float64) for v in vals]) if wsum else None
+    nr = (C.c_int32 * S)(*[int(bool(x)) for x in (narrow if narrow is not None else [False] * S)]) if method == "wsum64" else None
+    check(lib.fz_lists_join(_ptr_array(ids), _ptr_array(lens), _ptr_array(vals) if wsum else None, v64, w, nr, n_h, ld_h, S, Q,
+                            LISTS_METHODS[method], _ptr(out_ids), _ptr(out_scores), _ptr(out_len), ld_out, _ptr(ws), ws.numel(),
+                            _stream(ids[0])), "fz_lists_join")
+    if Q > 0 and total > 0 and int(ws[:4].view(torch.int32).item()) != 0:
+        raise ValueError("lists_join: a list holds the same id twice (ids inside one system's list must be distinct)")
+    return out_ids, out_scores, out_len
+
+
 def gold_ranks(T: list[torch.Tensor], pos: torch.Tensor, weights: torch.Tensor, gold: torch.Tensor) -> torch.Tensor:
     """Fused ranks of the gold documents for every weight vector (N1, hybrid.py:404-426).
     T[s] [Q,N] normalised planes, pos [Q,N] int32 insertion positions (-1 absent), weights [W,S] fp32,

@@ -115,6 +115,66 @@ class RankedSystem:
 
 
 @dataclass
+class RankedTopk:
+    """One system's top-k LISTS, as the corpus-scale searches return them (ShardedDenseIndex.search, ShardedSparseIndex.search,
+    TFIDF.search_topk): per query k (score, global id) pairs in list order.  Nothing here is indexed by corpus position, so the corpus
+    may be of any size and the ids any int64; Aggregator.fuse_topk joins such lists per query on their ids."""
+    ids: torch.Tensor             # [Q, k] int64: id at list position r (r < lens[q]); padding slots hold -1 and are never read
+    scores: torch.Tensor          # [Q, k] float32: its score (what the normalisations take, hybrid.py:255)
+    lens: torch.Tensor            # [Q] int32: list length per query
+    scores64: torch.Tensor | None = None   # [Q, k] float64 when the raw scores are not float32 values (BM25): the 'none' passthrough keeps them
+
+    @classmethod
+    def from_search(cls, scores: torch.Tensor, ids: torch.Tensor, scores64: torch.Tensor | None = None) -> "RankedTopk":
+        """From a search's ([Q, k] float32 scores, [Q, k] int64 ids), padded with (-inf, -1): the lengths are read off the padding
+        (a list's entries come first, so its length is the number of ids >= 0)."""
+        if ids.dtype != torch.int64 or scores.dtype != torch.float32:
+            raise TypeError(f"RankedTopk.from_search: expected float32 scores and int64 ids, got {scores.dtype} / {ids.dtype}")
+        if ids.dim() != 2 or tuple(ids.shape) != tuple(scores.shape):
+            raise ValueError(f"RankedTopk.from_search: scores {tuple(scores.shape)} and ids {tuple(ids.shape)} must be the same [Q, k]")
+        return cls(ids=ids, scores=scores, lens=(ids >= 0).sum(1, dtype=torch.int32), scores64=scores64)
+
+    @property
+    def Q(self) -> int:
+        return self.ids.shape[0]
+
+    @property
+    def k(self) -> int:
+        return self.ids.shape[1]
+
+    def to_lists(self) -> list[list[dict]]:
+        """-> the reference's RankedLists (hybrid.py:75,106,137): Python-float scores."""
+        ids = self.ids.cpu().numpy()
+        sc = (self.scores if self.scores64 is None else self.scores64).cpu().numpy().astype(np.float64)
+        lens = self.lens.cpu().numpy()
+        with _gc_paused():
+            return [_dict_list(ids[q, :int(lens[q])].tolist(), sc[q, :int(lens[q])].tolist()) for q in range(ids.shape[0])]
+
+
+@dataclass
+class FusedTopk:
+    """Output of Aggregator.fuse_topk: the fused lists over each query's own union of ids, in fused rank order."""
+    ids: torch.Tensor             # [Q, n] int64: id at fused rank r (r < lens[q]), -1 beyond
+    scores: torch.Tensor          # [Q, n] fused score at fused rank r (float64 for rrf / bcf / 'none' / np.float64 weights, float32 otherwise)
+    lens: torch.Tensor            # [Q] int32 = |union of ids| (or the cut, with topk)
+
+    def to_lists(self) -> list[list[dict]]:
+        """The reference's types, as FusedResult.to_lists: Python floats for float64 scores, np.float32 scalars for float32."""
+        ids = self.ids.cpu().numpy()
+        sc = self.scores.cpu().numpy()
+        lens = self.lens.cpu().numpy()
+        f32 = sc.dtype == np.float32
+        with _gc_paused():
+            return [_dict_list(ids[q, :int(lens[q])].tolist(), list(sc[q, :int(lens[q])]) if f32 else sc[q, :int(lens[q])].tolist())
+                    for q in range(ids.shape[0])]
+
+    def predictions(self, topk: int | None = None) -> list[list]:
+        ids = self.ids.cpu().numpy()
+        lens = self.lens.cpu().numpy()
+        return [ids[q, :(int(lens[q]) if topk is None else min(int(lens[q]), topk))].tolist() for q in range(ids.shape[0])]
+
+
+@dataclass
 class FusedResult:
     """Output of Aggregator.fuse on the device: fused lists over the union of ids per query."""
     order: torch.Tensor           # [Q, N] int32: corpus position at fused rank r (r < lens[q])

@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..planes import RankedSystem
+from ..planes import RankedSystem, RankedTopk
 
 
 LEXICAL_MIN_ZERO_SHARE = 0.3   # expected share of exact zeros per row from which the ranking sort's zero-compacting instantiation is asked for
@@ -188,6 +188,29 @@ class TFIDF:
             else:
                 out[lo:lo + len(chunk)] = self._top_positions(self.scores(chunk), k).cpu().numpy()
         return out
+
+    def search_topk(self, queries: list[str], k: int, budget_bytes: int = DEVICE_BUDGET_BYTES) -> RankedTopk:
+        """The first min(k, N) entries of every ranked list as device-resident top-k lists (what Aggregator.fuse_topk takes): the positions
+        ranked_positions computes, kept on the device, with their float64 scores gathered next to them (scores64; `scores` holds the
+        float32 roundings the normalisations take, hybrid.py:255).  ids = corpus positions."""
+        N, k = self.corpus_size, max(0, min(k, self.corpus_size))
+        Q = len(queries)
+        pos = torch.empty((Q, k), dtype=torch.int64, device=self.device)
+        sc64 = torch.empty((Q, k), dtype=torch.float64, device=self.device)
+        W = ops.sort_max_n(torch.float64)
+        step = self._query_step(k, budget_bytes)
+        for lo in range(0, Q if k else 0, step):
+            chunk = queries[lo:lo + step]
+            if N <= W:
+                rs = self.search_device(chunk)
+                p, plane = rs.order[:, :k].long(), rs.scores64
+            else:
+                plane = self.scores(chunk)
+                p = self._top_positions(plane, k)
+            pos[lo:lo + len(chunk)] = p
+            sc64[lo:lo + len(chunk)] = torch.gather(plane, 1, p)
+        lens = torch.full((Q,), k, dtype=torch.int32, device=self.device)
+        return RankedTopk(ids=pos, scores=sc64.to(torch.float32), lens=lens, scores64=sc64)
 
     def _query_step(self, k: int, budget_bytes: int) -> int:
         """Queries per chunk whose planes fit budget_bytes (at least one)."""

@@ -12,6 +12,7 @@ Reference map (file:line in the reference tree)
 Interchange type: the reference's RankedLists (list[Q] of list[<=N] of {'corpus_id','score'}) is accepted and
 returned everywhere the reference does; additionally every Ranker method takes `as_device=True` to hand over
 device-resident `RankedSystem` planes, which `Aggregator.fuse` consumes without a host round trip.
+The corpus-scale searches return top-k LISTS over global ids instead (`RankedTopk`); `Aggregator.fuse_topk` fuses those per query on the device.
 
 Documented deviations: D1 own SPLADE wrapper; D2 working cross-encoder rerank; D4 the weights
 check really checks (KeyError); ties inside a system are broken by ascending corpus position; percentile tables
@@ -28,7 +29,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..planes import FusedResult, RankedSystem
+from ..planes import FusedResult, FusedTopk, RankedSystem, RankedTopk
 
 RankedLists = list  # list[list[dict]]
 
@@ -440,6 +441,69 @@ class Aggregator:
         if topk is not None and topk < N:
             return FusedResult(order=order[:, :topk], scores=sk[:, :topk], lens=torch.clamp(lens_out, max=topk), ids=S[0].ids)
         return FusedResult(order=order, scores=sk, lens=lens_out, ids=S[0].ids)
+
+    # -- top-k lists over any ids: per-query id join (csrc/lists.hip) -------------------------------
+    @classmethod
+    def fuse_topk(cls, systems: dict[str, RankedTopk], method: str, normalization: str = None,
+                  linear_weights: dict[str, float] = None, percentile_distributions: dict[str, np.ndarray] = None,
+                  topk: int | None = None) -> FusedTopk:
+        """Aggregator.fuse for the lists the corpus-scale searches return (RankedTopk: k (score, int64 global id) pairs per query and
+        system), on the device and with no plane over the corpus or over the batch's union of ids: every query's lists are joined on
+        their ids by one workgroup (ops.lists_join), the fused scores come out in the fused dict's first-insertion order, and the
+        existing stable row sort ranks them.  Same methods, normalisations, weights and errors as fuse; a system's statistics are
+        taken over its listed entries (hybrid.py:254-264).  topk=k keeps the first k entries of every fused list.  Lists of
+        different k mix; one query's lists may hold ops.lists_max_entries() entries in all (ValueError beyond)."""
+        names = list(systems.keys())
+        ops._max_systems(len(names), "Aggregator.fuse_topk")
+        S = [systems[n] for n in names]
+        Q = S[0].Q
+        assert all(s.Q == Q for s in S), (
+            "Ranked results from different retrieval systems have varying lenghts across systems (i.e., some systems have been run on more queries).")
+        ids, lens = [s.ids for s in S], [s.lens for s in S]
+        raw = [s.scores if s.scores64 is None else s.scores64 for s in S]
+        if method in ("bcf", "rrf"):
+            joined = ops.lists_join(ids, lens, method)
+        elif method == "nsf":
+            if percentile_distributions is None:            # the reference calls .get() on it for every system (hybrid.py:213)
+                raise AttributeError("'NoneType' object has no attribute 'get'")
+            w = [linear_weights[n] for n in names]          # KeyError when a system has no weight (hybrid.py:214)
+            wide = [cls._wide(x) for x in w]
+            if normalization in ("min-max", "z-score", "arctan", "percentile-rank", "normal-curve-equivalent"):
+                dev = S[0].ids.device
+                tabled = normalization in ("percentile-rank", "normal-curve-equivalent")
+                T = []
+                for n, s in zip(names, S):
+                    if s.k == 0:
+                        T.append(s.scores)
+                        continue
+                    # the list IS a plane of k columns in list order (rank plane: r where r < len, else -1): the same kernels and the
+                    # same statistics as the dense path, transformed with weight 1 (fl32(t * 1) + 0 == t); the join weights and sums
+                    r = torch.arange(s.k, dtype=torch.int32, device=dev)
+                    rank = ops.alloc_plane(Q, s.k, torch.int32, dev)
+                    rank.copy_(torch.where(r[None, :] < s.lens[:, None], r[None, :], torch.full_like(r, -1)[None, :]))
+                    rs = RankedSystem(scores=ops.as_plane(s.scores), order=rank, rank=rank, lens=s.lens, ids=None, full=False)
+                    distr = [cls._table(percentile_distributions.get(n), dev)] if tabled else None
+                    st = [rs.stats(normalization)] if normalization in ("min-max", "z-score") else None
+                    T.append(cls._normalised_planes([rs], normalization, distr, st)[0])
+                if any(wide):
+                    joined = ops.lists_join(ids, lens, "wsum64", T, w, narrow=[not x for x in wide])
+                else:
+                    joined = ops.lists_join(ids, lens, "wsum32", T, w)
+            else:                                           # 'none' / unknown string: raw Python floats, float64 (hybrid.py:280)
+                joined = ops.lists_join(ids, lens, "wsum64", raw, w)
+        else:                                               # unknown method: raw scores are summed (hybrid.py:203-218)
+            joined = ops.lists_join(ids, lens, "wsum64", raw, [1.0] * len(S))
+        out_ids, out_scores, out_len = joined
+        n = out_ids.shape[1]
+        if Q == 0 or n == 0:
+            return FusedTopk(ids=out_ids, scores=out_scores, lens=out_len)
+        # the columns are in first-insertion order: the stable sort's tie rule (ascending column) IS the reference's.  The cut comes from
+        # out_len, never from the scores: NCE produces real -inf
+        order, sk, _ = ops.sort_rows_desc(out_scores, row_len=out_len)
+        fids = torch.gather(out_ids, 1, order.clamp(min=0).long()).masked_fill_(order < 0, -1)
+        if topk is not None and topk < n:
+            return FusedTopk(ids=fids[:, :topk], scores=sk[:, :topk], lens=torch.clamp(out_len, max=topk))
+        return FusedTopk(ids=fids, scores=sk, lens=out_len)
 
     # -- N1: the whole weight grid in one pass (hybrid.py:404-426) ----------------------------------
     @classmethod

@@ -326,6 +326,34 @@ size_t fz_topk_allgather_workspace_bytes(int world, int Q, int k);
 int fz_topk_allgather(const float* local_scores, const int64_t* local_ids, int Q, int k, void* rccl_comm, int world,
                       float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- fusion of top-k LISTS: per-query id join (hybrid.py:293-307 on lists of any ids) --------- */
+/* What the searches above return -- per query k (score, int64 global id) pairs per system -- fused without any plane over the
+ * corpus: one workgroup per query joins the S lists on their ids in LDS (csrc/lists.hip).
+ * Inputs, per system s (HOST arrays of S entries): ids_h[s] device [Q][ld_h[s]] int64; lens_h[s] device [Q] int32 (clamped to
+ * [0, n_h[s]]; entries past it are padding and are never read); n_h[s] = list width (k), ld_h[s] >= n_h[s] = row stride in elements
+ * of ids_h[s] and values_h[s].  Ids are arbitrary int64 and must be distinct inside one list.
+ * Outputs, per query, in the fused dict's FIRST-INSERTION order (system 0's entries in list order, then system 1's new ones, ...):
+ * out_ids [Q][ld_out] int64, out_scores [Q][ld_out] (float32 for FZ_LISTS_WSUM_F32, float64 otherwise), out_len [Q] = size of the
+ * union; columns past out_len are not written.  ld_out >= sum of n_h.  The final ranking is fz_sort_rows_desc on out_scores with
+ * row_len = out_len (ties -> ascending column = the reference's tie rule) and a gather of out_ids.
+ * Score of a column: 0 + c_s1 + c_s2 + ... over the systems that list the id, in system order, with
+ *   FZ_LISTS_RRF       c = 1 / (60 + r + 1), float64 (fz_fuse_rank_f64's bits), r = position in the list;
+ *   FZ_LISTS_BCF       c = (n - r + 1) / n, float64, n = the list's length;
+ *   FZ_LISTS_WSUM_F32  c = fl32(values_h[s][q][r] * fl32(w_h[s])), float32 sum (fz_fuse_nsf_f32's weighting);
+ *   FZ_LISTS_WSUM_F64  fz_fuse_wsum_f64's rule: value_is_f64_h[s] / narrow_h[s] as there (both nullable).
+ * values_h / w_h are read by the two WSUM methods only.  sum of n_h <= fz_lists_max_entries() (>= 8192), FZ_ERR_UNSUPPORTED
+ * beyond.  Workspace: fz_lists_join_workspace_bytes(S, Q) device bytes; its first int32 is the DUPLICATE FLAG: zeroed by the
+ * call, non-zero afterwards when some list held an id twice (the outputs are then unspecified, never out of bounds).
+ * Every argument is checked before the first HIP call.  Q == 0 or all n_h == 0: FZ_OK, nothing launched (out_len is left as the
+ * caller initialised it: zeros). */
+typedef enum { FZ_LISTS_RRF = 0, FZ_LISTS_BCF = 1, FZ_LISTS_WSUM_F32 = 2, FZ_LISTS_WSUM_F64 = 3 } fz_lists_method;
+int fz_lists_max_entries(void);
+size_t fz_lists_join_workspace_bytes(int S, int Q);
+int fz_lists_join(const int64_t* const* ids_h, const int32_t* const* lens_h, const void* const* values_h,
+                  const int32_t* value_is_f64_h, const double* w_h, const int32_t* narrow_h, const int32_t* n_h,
+                  const int32_t* ld_h, int S, int Q, int method, int64_t* out_ids, void* out_scores, int32_t* out_len,
+                  int ld_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- A1: BM25 scoring on device, bm25.py:149-156 -------------------------------------- */
 /* scores[q][j] (fp64) = sum over query terms in query order of idf*tf*(k1+1)/(tf+k1*(1-b+b*dl/avgdl)).
  * CSR postings by term (toff [V+1], pdoc, ptf), idf [V] fp64, doc_len [N]; queries as CSR of term
