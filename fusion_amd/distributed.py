@@ -17,6 +17,8 @@ from __future__ import annotations
 
 import torch
 
+from . import ops
+
 
 def shard_bounds(n: int, world: int, rank: int) -> tuple[int, int]:
     """Contiguous, balanced row shards: the first n % world shards get one extra row."""
@@ -47,7 +49,6 @@ def allgather_topk(local_scores: torch.Tensor, local_ids: torch.Tensor, group=No
     merge_fn([G,Q,k] scores, [G,Q,k] ids) -> ([Q,k], [Q,k]); defaults to the HIP merge."""
     import torch.distributed as dist
     if merge_fn is None:
-        from . import ops
         merge_fn = ops.topk_merge
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     if world == 1:
@@ -61,141 +62,137 @@ def allgather_topk(local_scores: torch.Tensor, local_ids: torch.Tensor, group=No
     return merge_fn(gs, gi)
 
 
-class ShardedDenseIndex:
-    """One rank's shard of the L2-normalised corpus embeddings + the chunked score -> top-k loop."""
+class _ShardedIndex:
+    """One rank's shard of a corpus + the chunked score -> top-k search over it; a subclass supplies its constants and the scoring source of its
+    shard for a set of queries (_source: what ops.TopkStream is fed from).  The first head_docs(k) documents are scored into a plane and get an
+    exact top-k (one sort-kernel row per query); after that only scores above a query's running k-th best can enter, so the rest goes through the
+    source's filter kernel -- no score plane, no filter pass -- in CHUNK-document feeds and the candidates are folded into the list a few times
+    per shard (ops.TopkStream).  A window in which a row overflowed its candidate buffer is redone exactly, on its own (flag read at every fold: 4
+    small reads per shard).  `mark(name)`: optional instrumentation hook (bench.py records a HIP event per call).
+    Everything runs on ONE stream: issuing the top-k work of chunk c on a second stream under the GEMM of chunk c + 1 was
+    measured twice and lost both times (17.3 vs 15.5 ms per 1.1 M-document shard in round 2: the persistent GEMM owns every
+    CU, and what squeezes in next to it costs the matrix pipe more than it hides)."""
+
+    CAP = 7168          # candidate slots per row and window on the streaming path (k + CAP = one 8192-key sort row at k = 1024)
+    HEAD = 28672        # at most this many leading documents get the exact top-k (one sort-kernel row); 8 k of them (>= 8192) are enough
+    _grain = 1          # document ranges start on a multiple of it
+    last_overflow = 0   # windows of the last local_topk whose candidate buffers overflowed (each was redone exactly, ops.TopkStream)
+
+    def head_docs(self, k: int) -> int:
+        """8,192 at k = 1000 (a 0.09 ms sort instead of 0.35, one fold more), rounded up to whole grains (sparse: 14,336)."""
+        return ops.round_up(min(self.HEAD, max(8192, -(-8 * k // 4096) * 4096)), self._grain)
+
+    def _streams(self, k: int, n: int) -> bool:
+        return k + self.CAP <= ops.sort_max_n() and k <= self.head_docs(k) // 8 and n > self.head_docs(k)
+
+    def _chunk(self) -> int:
+        return max(self._grain, self.CHUNK // self._grain * self._grain)
+
+    def _topk(self, q: tuple, k: int, streaming: bool, mark):
+        mark = mark or (lambda name: None)
+        src = self._source(*q)
+        self.last_overflow = 0
+        if not (streaming and self._streams(k, src.n)):
+            return self.two_pass_topk(q, k, mark)
+        head, chunk = self.head_docs(k), self._chunk()
+        S, _ = src.plane(0, head); mark(self.PLANE_MARK)
+        bs, bi = ops.topk_rows(S, k, id_base=self.id_base)
+        del S
+        stream = ops.TopkStream(bs, bi, seen=head, cap=self.CAP); mark("shard_topk_stream")
+        for c0 in range(head, src.n, chunk):
+            stream._feed(src, c0, min(src.n, c0 + chunk), mark)
+        best_s, best_i, _ = stream.result(); mark("shard_topk_stream")
+        self.last_overflow = stream.windows_redone
+        return best_s, best_i
+
+    def two_pass_topk(self, q: tuple, k: int, mark=None):
+        """Per chunk a score plane, its top-k, a merge: for a small shard or a k beyond the streaming sort's reach (and the fused paths' yardstick)."""
+        mark = mark or (lambda name: None)
+        src, best_s, best_i = self._source(*q), None, None
+        for c0 in range(0, max(src.n, 1), self._chunk()):
+            S, base = src.plane(c0, min(src.n, c0 + self._chunk())); mark(self.PLANE_MARK)
+            s, i = ops.topk_rows(S, k, id_base=base)
+            if best_s is not None:   # merge two id-ascending lists (chunks arrive in id order)
+                s, i = ops.topk_merge(torch.stack([best_s, s]), torch.stack([best_i, i]))
+            best_s, best_i = s, i; mark("shard_topk_exact")
+        return best_s, best_i
+
+    def _search(self, q: tuple, k: int, mark):
+        out = allgather_topk(*self.local_topk(*q, k, mark=mark), group=self.group)
+        if mark: mark("allgather_merge")
+        return out
+
+
+class ShardedDenseIndex(_ShardedIndex):
+    """One rank's shard of the L2-normalised corpus embeddings: the fp32-MFMA GEMM scores it, and after the head the GEMM's epilogue is
+    the threshold filter (fz_dot_scores_filter_f32: per shard 4.5 GB less written and 4.5 GB less read than a plane and a filter pass)."""
 
     CHUNK = 8 * 28672   # documents per GEMM launch: 8 sort-kernel rows per query
-    CAP = 7168          # candidate slots per row and chunk on the streaming path (k + CAP = one 8192-key sort row at k = 1024)
     FUSED = True        # after the head, score and filter in one kernel (fz_dot_scores_filter_f32); False: GEMM, then the filter pass
-    HEAD = 28672        # at most this many leading documents get the exact top-k (one sort-kernel row); 8 k of them (>= 8192) are enough
+    PLANE_MARK = "shard_gemm"
 
     def __init__(self, Dn_local: torch.Tensor, id_base: int, group=None):
         self.Dn, self.id_base, self.group = Dn_local, int(id_base), group
-        self.last_overflow = 0   # windows of the last local_topk whose candidate buffers overflowed (each was redone exactly, ops.TopkStream)
+
+    def _source(self, Qn):
+        return ops._gemm_source(Qn, self.Dn, self.id_base)
 
     def local_topk(self, Qn: torch.Tensor, k: int, streaming: bool = True, mark=None):
-        """Chunked score -> top-k over this shard.  The first HEAD documents get an exact top-k (one sort-kernel row per query);
-        after that only scores above a query's running k-th best can enter, so every later chunk goes through the streaming
-        threshold filter and the candidates are folded into the list a few times per shard (ops.TopkStream).  A window in which a
-        row overflowed its candidate buffer is redone exactly, on its own (flag read at every fold: 4 small reads per shard).
-        `mark(name)`: optional instrumentation hook (bench.py records a HIP event per call).
-        Everything runs on ONE stream: issuing the top-k work of chunk c on a second stream under the GEMM of chunk c + 1 was
-        measured twice and lost both times (17.3 vs 15.5 ms per 1.1 M-document shard in round 2: the persistent GEMM owns every
-        CU, and what squeezes in next to it costs the matrix pipe more than it hides)."""
-        from . import ops
-        mark = mark or (lambda name: None)
-        n = self.Dn.shape[0]
-        head = min(self.HEAD, max(8192, -(-8 * k // 4096) * 4096))   # 8192 at k = 1000: a 0.09 ms sort instead of 0.35, one fold more
-        streaming = streaming and k + self.CAP <= 35840 and k <= head // 8 and n > head
-        best_s = best_i = stream = None
-        if streaming and self.FUSED and Qn.shape[1] % 4 == 0:
-            # the head's scores are materialised and ranked exactly; everything after it goes through the GEMM whose epilogue is the
-            # threshold filter: no score plane, no filter pass -- per shard 4.5 GB less written and 4.5 GB less read
-            S = ops.dot_scores(Qn, self.Dn[:head]); mark("shard_gemm")
-            bs, bi = ops.topk_rows(S, k, id_base=self.id_base)
-            stream = ops.TopkStream(bs, bi, seen=head, cap=self.CAP); mark("shard_topk_stream")
-            for c0 in range(head, n, self.CHUNK):
-                c1 = min(n, c0 + self.CHUNK)
-                stream.feed_gemm(Qn, self.Dn[c0:c1], self.id_base + c0, mark=mark)
-            best_s, best_i, _ = stream.result(); mark("shard_topk_stream")
-            self.last_overflow = stream.windows_redone
-            return best_s, best_i
-        for c0 in range(0, max(n, 1), self.CHUNK):
+        """[Q, k] (score desc, id asc) over this shard; streaming=False forces the two-pass path."""
+        if streaming and self._streams(k, self.Dn.shape[0]) and not (self.FUSED and Qn.shape[1] % 4 == 0):
+            return self._unfused_topk(Qn, k, mark or (lambda name: None))
+        return self._topk((Qn,), k, streaming, mark)
+
+    def _unfused_topk(self, Qn, k, mark):
+        """Streaming with the filter as a pass of its own over each chunk's GEMM plane (FUSED = False, or a d the fused kernel does not take).
+        The stream holds no score plane (one chunk alive at a time): after a window that overflowed, this shard again on the two-pass path."""
+        n, head, stream = self.Dn.shape[0], self.head_docs(k), None
+        for c0 in range(0, n, self.CHUNK):
             c1 = min(n, c0 + self.CHUNK)
             S = ops.dot_scores(Qn, self.Dn[c0:c1]); mark("shard_gemm")
-            if streaming:
-                lo = 0
-                if stream is None:
-                    lo = min(head, c1 - c0)
-                    bs, bi = ops.topk_rows(S[:, :lo], k, id_base=self.id_base + c0)
-                    stream = ops.TopkStream(bs, bi, seen=lo, cap=self.CAP)
-                stream.feed(S[:, lo:], self.id_base + c0 + lo); mark("shard_topk_stream")
-                if stream.unrepairable:   # a window of scores the stream does not hold overflowed: the rest of the streaming pass would be wasted
-                    break
-            elif best_s is None:
-                best_s, best_i = ops.topk_rows(S, k, id_base=self.id_base + c0); mark("shard_topk_exact")
-            else:   # exact path: per-chunk top-k, then merge two id-ascending lists (chunks arrive in id order)
-                s, i = ops.topk_rows(S, k, id_base=self.id_base + c0)
-                best_s, best_i = ops.topk_merge(torch.stack([best_s, s]), torch.stack([best_i, i])); mark("shard_topk_exact")
+            lo = 0
+            if stream is None:
+                lo = min(head, c1 - c0)
+                bs, bi = ops.topk_rows(S[:, :lo], k, id_base=self.id_base + c0)
+                stream = ops.TopkStream(bs, bi, seen=lo, cap=self.CAP)
+            stream.feed(S[:, lo:], self.id_base + c0 + lo); mark("shard_topk_stream")
+            if stream.unrepairable:   # a window of scores the stream does not hold overflowed: the rest of the streaming pass would be wasted
+                break
+        best_s, best_i, flag = stream.result(); mark("shard_topk_stream")
         self.last_overflow = 0
-        if stream is not None:
-            best_s, best_i, flag = stream.result(); mark("shard_topk_stream")
-            if int(flag.item()) != 0:   # a window of materialised scores overflowed (the stream holds no score plane: one chunk alive at a
-                res = self.local_topk(Qn, k, streaming=False, mark=mark)   # time): this shard again on the exact path
-                self.last_overflow = 1
-                return res
+        if int(flag.item()) != 0:
+            best_s, best_i = self.local_topk(Qn, k, streaming=False, mark=mark)
+            self.last_overflow = 1
         return best_s, best_i
 
     def search(self, Qn: torch.Tensor, k: int = 1000, mark=None):
-        s, i = self.local_topk(Qn, k, mark=mark)
-        out = allgather_topk(s, i, self.group)
-        if mark: mark("allgather_merge")
-        return out
+        return self._search((Qn,), k, mark)
 
 
-class ShardedSparseIndex:
+class ShardedSparseIndex(_ShardedIndex):
     """One rank's shard of a SPLADE corpus as an inverted index (ops.SparseIndex, documents 0 .. N-1 = global ids id_base ..) + the
-    chunked score -> top-k loop of splade/base.py:199-251 (BaseModel.search) at corpus scale.  The shape of ShardedDenseIndex: the first
-    HEAD documents are scored into a plane and ranked exactly, the rest streams through fz_sparse_dot_filter_f32 -- the posting walk whose
-    epilogue is TopkStream's threshold filter, no score plane -- in CHUNK-document pieces; one all-gather merges the shards.  Ties go to
-    the ascending global id (SPLADE rows are mostly exact zeros: this rule decides the tail of a query that matches fewer than k
-    documents)."""
+    chunked score -> top-k loop of splade/base.py:199-251 (BaseModel.search) at corpus scale: ops.sparse_dot scores the head, the rest
+    streams through fz_sparse_dot_filter_f32, the posting walk whose epilogue is the filter.  Ties go to the ascending global id (SPLADE
+    rows are mostly exact zeros: this rule decides the tail of a query that matches fewer than k documents)."""
 
-    CHUNK = 32 * 7168   # documents per feed (a whole number of the kernels' 7,168-document slices)
-    CAP = 7168          # candidate slots per row and window on the streaming path
+    CHUNK = 32 * 7168   # documents per feed (rounded down to whole slices of the kernels, 7,168 documents each; at least one)
+    PLANE_MARK = "shard_sparse"
+    _grain = property(lambda self: ops.sparse_slice_docs())
 
     def __init__(self, index, id_base: int, group=None):
         self.index, self.id_base, self.group = index, int(id_base), group
-        self.last_overflow = 0   # windows of the last local_topk whose candidate buffers overflowed (each was redone exactly, ops.TopkStream)
 
-    def head_docs(self, k: int) -> int:
-        """ShardedDenseIndex's head for this k (8,192 at k = 1000), rounded up to whole slices (14,336)."""
-        from . import ops
-        dense = min(ShardedDenseIndex.HEAD, max(8192, -(-8 * k // 4096) * 4096))
-        return ops.round_up(dense, ops.sparse_slice_docs())
+    def _source(self, qoff, qterms, qw):
+        return ops._sparse_source(self.index, qoff, qterms, qw, self.id_base)
 
     def local_topk(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, k: int, mark=None):
         """[Q, k] (score desc, id asc) over this shard for the queries' term lists (ops.sparse_rows); short lists padded with (-inf, -1)."""
-        from . import ops
-        mark = mark or (lambda name: None)
-        idx, n, Q = self.index, self.index.N, qoff.numel() - 1
-        S = ops.sparse_slice_docs()
-        chunk = max(S, self.CHUNK // S * S)
-        head = self.head_docs(k)
-        self.last_overflow = 0
-        if n == 0 or Q == 0:
+        Q = qoff.numel() - 1
+        if self.index.N == 0 or Q == 0:
+            self.last_overflow = 0
             return (torch.full((Q, k), float("-inf"), dtype=torch.float32, device=qoff.device),
                     torch.full((Q, k), -1, dtype=torch.int64, device=qoff.device))
-        if k + self.CAP <= 35840 and k <= head // 8 and n > head:
-            sc = ops.sparse_dot(idx, qoff, qterms, qw, doc_hi=head); mark("shard_sparse")
-            bs, bi = ops.topk_rows(sc, k, id_base=self.id_base)
-            del sc
-            stream = ops.TopkStream(bs, bi, seen=head, cap=self.CAP); mark("shard_topk_stream")
-            for c0 in range(head, n, chunk):
-                stream.feed_sparse(idx, qoff, qterms, qw, c0, min(n, c0 + chunk), self.id_base, mark=mark)
-            best_s, best_i, _ = stream.result(); mark("shard_topk_stream")
-            self.last_overflow = stream.windows_redone
-            return best_s, best_i
-        return self._exact_topk(qoff, qterms, qw, k, chunk, mark)
-
-    def _exact_topk(self, qoff, qterms, qw, k: int, chunk: int, mark):
-        """The two-pass path -- per chunk a score plane, its top-k, a merge -- for a small shard or a k beyond the streaming sort's reach
-        (and the yardstick tools/bench_splade_search.py times the fused path against)."""
-        from . import ops
-        idx, n = self.index, self.index.N
-        best_s = best_i = None
-        for c0 in range(0, n, chunk):
-            c1 = min(n, c0 + chunk)
-            s, i = ops.topk_rows(ops.sparse_dot(idx, qoff, qterms, qw, doc_lo=c0, doc_hi=c1), k, id_base=self.id_base + c0)
-            if best_s is None:
-                best_s, best_i = s, i
-            else:
-                best_s, best_i = ops.topk_merge(torch.stack([best_s, s]), torch.stack([best_i, i]))
-            mark("shard_topk_exact")
-        return best_s, best_i
+        return self._topk((qoff, qterms, qw), k, True, mark)
 
     def search(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, k: int = 1000, mark=None):
-        s, i = self.local_topk(qoff, qterms, qw, k, mark=mark)
-        out = allgather_topk(s, i, self.group)
-        if mark: mark("allgather_merge")
-        return out
+        return self._search((qoff, qterms, qw), k, mark)

@@ -929,23 +929,65 @@ def stream_window(seen: int, k: int, cap: int) -> int:
     return max(64, (cap // 2) * seen // k // 64 * 64)
 
 
-def sparse_pieces(doc_lo: int, doc_hi: int, seen: int, pending: int, k: int, cap: int, slice_docs: int):
-    """How TopkStream.feed_sparse cuts [doc_lo, doc_hi): [(lo, hi, fold after this piece)], ascending and back to back.  The fold window
-    (stream_window) is rounded down to whole slices, at least one; a piece ends where the window does (or at doc_hi, which may be off the
-    grain) and the stream folds there; the bookkeeping -- seen, pending -- is TopkStream's own.  Host arithmetic only."""
+def stream_pieces(lo: int, hi: int, seen: int, pending: int, k: int, cap: int, grain: int = 1):
+    """How a TopkStream cuts a source's documents [lo, hi): [(lo, hi, fold after this piece)], ascending and back to back.  The fold window
+    (stream_window) is rounded down to whole grains (1, or the sparse kernels' slice), at least one; a piece ends where the window does (or
+    at hi, which may be off the grain) and the stream folds there; the bookkeeping -- seen, pending -- is TopkStream's own.  Host arithmetic only."""
     out = []
-    lo = doc_lo
-    while lo < doc_hi:
-        win = max(slice_docs, stream_window(seen, k, cap) // slice_docs * slice_docs)
-        room = max(slice_docs, (win - pending) // slice_docs * slice_docs)
-        hi = min(doc_hi, lo + room)
-        pending += hi - lo
+    while lo < hi:
+        win = max(grain, stream_window(seen, k, cap) // grain * grain)
+        room = max(grain, (win - pending) // grain * grain)
+        end = min(hi, lo + room)
+        pending += end - lo
         fold = pending >= win
         if fold:
             seen, pending = seen + pending, 0
-        out.append((lo, hi, fold))
-        lo = hi
+        out.append((lo, end, fold))
+        lo = end
     return out
+
+
+sparse_pieces = stream_pieces   # its name while feed_sparse alone used it
+
+
+class _Source:
+    """What a TopkStream is fed from: the scorer of n documents, [lo, hi) in its own numbering, for the stream's queries.  filter(stream, lo,
+    hi) launches its filter kernel against the stream's thresholds and candidate buffers; plane(lo, hi) -> (scores [rows, hi - lo], id of
+    column 0) is the same piece materialised, for the exact redo of an overflowed window.  grain: pieces start on a multiple of it; unordered:
+    candidates arrive in no particular order; mark: the name reported after a launch; held: the stream may keep it (views, no copies)."""
+
+    def __init__(self, n, filter, plane, grain=1, unordered=True, mark=None, held=True):
+        self.n, self.filter, self.plane, self.grain, self.unordered, self.mark, self.held = n, filter, plane, grain, unordered, mark, held
+
+
+def _plane_source(scores, id_base: int, held: bool) -> _Source:
+    """A materialised score plane, column c = document id_base + c (TopkStream.feed)."""
+    def filter(st, lo, hi):
+        check(_lib.lib().fz_topk_filter_append_f32(_ptr(scores[:, lo:hi]), st.rows, hi - lo, _ld(scores), id_base + lo, _ptr(st.tau), _ptr(st.cand_s),
+                                                   _ptr(st.cand_i), _ptr(st.cand_len), st.cap, _ptr(st.overflow), _stream(scores)),
+              "fz_topk_filter_append_f32")
+    return _Source(scores.shape[1], filter, lambda lo, hi: (scores[:, lo:hi], id_base + lo), unordered=False, held=held)
+
+
+def _gemm_source(Qn, Dn, id_base: int) -> _Source:
+    """The GEMM whose epilogue is the filter, row r of Dn = document id_base + r (TopkStream.feed_gemm, ShardedDenseIndex)."""
+    Qn, Dn = Qn.contiguous(), Dn.contiguous()
+
+    def filter(st, lo, hi):
+        check(_lib.lib().fz_dot_scores_filter_f32(_ptr(Qn), Qn.stride(0), _ptr(Dn[lo:hi]), Dn.stride(0), st.rows, hi - lo, Qn.shape[1], id_base + lo,
+                                                  _ptr(st._tau_pad), _ptr(st.cand_s), _ptr(st.cand_i), _ptr(st.cand_len), st.cap, _ptr(st.overflow),
+                                                  _stream(Qn)), "fz_dot_scores_filter_f32")
+    return _Source(Dn.shape[0], filter, lambda lo, hi: (dot_scores(Qn, Dn[lo:hi]), id_base + lo), mark="shard_gemm_filter")
+
+
+def _sparse_source(index, qoff, qterms, qw, id_base: int) -> _Source:
+    """The posting walk whose epilogue is the filter, document d of the index = id id_base + d (TopkStream.feed_sparse, ShardedSparseIndex)."""
+    def filter(st, lo, hi):
+        check(_lib.lib().fz_sparse_dot_filter_f32(_ptr(index.toff), _ptr(index.pdoc), _ptr(index.pw), _ptr(index.slice_off), _ptr(qoff), _ptr(qterms),
+                                                  _ptr(qw), st.rows, index.N, lo, hi, id_base, _ptr(st.tau), _ptr(st.cand_s), _ptr(st.cand_i),
+                                                  _ptr(st.cand_len), st.cap, _ptr(st.overflow), _stream(qoff)), "fz_sparse_dot_filter_f32")
+    return _Source(index.N, filter, lambda lo, hi: (sparse_dot(index, qoff, qterms, qw, doc_lo=lo, doc_hi=hi), id_base + lo),
+                   grain=sparse_slice_docs(), mark="shard_sparse_filter")
 
 
 class TopkStream:
@@ -958,9 +1000,9 @@ class TopkStream:
     flag is read at every fold (one small device -> host read per window: 4 per 1.1 M-document shard) and an overflowed WINDOW is redone
     exactly -- per-piece top-k (fz_topk_rows_f32) merged into the list as it stood before the window -- so a corpus ordered by relevance
     (every window overflows) costs the exact search once, not a wasted streaming pass plus the exact search of the whole shard;
-    `windows_redone` counts them.  That needs what the window was fed with: feed_gemm's pieces are views of Qn / Dn (kept: no copies);
-    feed()'s score buffers are kept only on request (hold=True) -- otherwise, and without exact_on_overflow, the flag stays set and
-    the caller redoes the search."""
+    `windows_redone` counts them.  That needs what the window was fed with: feed_gemm's and feed_sparse's pieces are views of their
+    inputs (kept: no copies); feed()'s score buffers are kept only on request (hold=True) -- otherwise, and without exact_on_overflow,
+    the flag stays set and the caller redoes the search.  The three feeds differ only in their _Source; the loop is _feed's."""
 
     def __init__(self, run_scores: torch.Tensor, run_ids: torch.Tensor, seen: int, cap: int = 7168, exact_on_overflow: bool = True):
         _dev(run_scores, torch.float32, "TopkStream(run_scores)"); _dev(run_ids, torch.int64, "TopkStream(run_ids)")
@@ -973,7 +1015,7 @@ class TopkStream:
         self._tau_pad = torch.full((round_up(max(rows, 1), 128),), float("inf"), dtype=torch.float32, device=dev)
         self.tau = self._tau_pad[:rows]
         self.tau.copy_(self.best_s[:, k - 1])
-        self.unordered = False           # candidates appended by the fused GEMM arrive in no particular order
+        self.unordered = False           # candidates appended by the fused feeds arrive in no particular order
         self.cand_s = torch.empty((rows, cap), dtype=torch.float32, device=dev)
         self.cand_i = torch.empty((rows, cap), dtype=torch.int64, device=dev)
         self.cand_len = torch.zeros(rows, dtype=torch.int32, device=dev)
@@ -982,17 +1024,27 @@ class TopkStream:
         self.pending = 0                 # documents filtered against tau since
         self.exact_on_overflow = bool(exact_on_overflow)
         self.windows_redone = 0
-        self._pieces = []                # what the current window was fed with: ("scores", piece, id_base) | ("gemm", Qn, Dpiece, id_base)
-                                         #   | ("sparse", index, (qoff, qterms, qw), doc_lo, doc_hi, id_base)
+        self._pieces = []                # what the current window was fed with: (source, lo, hi)
         self._unheld = False             # ... and whether some of it was fed without being held (feed(hold=False))
         self.unrepairable = False        # host latch: a window fed WITHOUT hold overflowed -- nothing the stream holds can repair it, the device
                                          #   flag stays set and the caller redoes the search; later windows are neither read nor redone
         wsb = int(_lib.lib().fz_topk_fold_workspace_bytes(rows, k, cap))
         self._ws, self._wsb = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev), wsb
 
-    def _window(self) -> int:
-        """documents one threshold may serve: expected candidates k * window / seen <= cap / 2"""
-        return stream_window(self.seen, self.k, self.cap)
+    def _feed(self, source, lo: int, hi: int, mark=None):
+        """The source's documents [lo, hi), cut at the fold windows (stream_pieces): one filter launch per piece, a fold where planned."""
+        self.unordered = self.unordered or source.unordered
+        for lo, hi, fold in stream_pieces(lo, hi, self.seen, self.pending, self.k, self.cap, source.grain):
+            source.filter(self, lo, hi)
+            if mark: mark(source.mark)
+            if source.held:
+                self._pieces.append((source, lo, hi))
+            else:
+                self._unheld = True          # this window saw scores the stream does not hold: no exact redo for it
+            self.pending += hi - lo
+            if fold:
+                self.fold()
+                if mark: mark("shard_topk_stream")
 
     def feed(self, scores: torch.Tensor, id_base: int, hold: bool = False):
         """scores [rows, n] of documents id_base .. id_base + n - 1.
@@ -1002,22 +1054,7 @@ class TopkStream:
         overflowed window exactly from it -- only for callers that leave the buffer untouched (and can afford it alive) until then."""
         _dev(scores, torch.float32, "TopkStream.feed(scores)")
         _need(scores.shape[0] == self.rows, "TopkStream.feed: one row per running list")
-        lib = _lib.lib()
-        n, lo = scores.shape[1], 0
-        while lo < n:
-            hi = min(n, lo + self._window() - self.pending)
-            piece = scores[:, lo:hi]
-            check(lib.fz_topk_filter_append_f32(_ptr(piece), self.rows, hi - lo, _ld(scores), int(id_base) + lo, _ptr(self.tau), _ptr(self.cand_s),
-                                                _ptr(self.cand_i), _ptr(self.cand_len), self.cap, _ptr(self.overflow), _stream(scores)),
-                  "fz_topk_filter_append_f32")
-            if hold:
-                self._pieces.append(("scores", piece, int(id_base) + lo))
-            else:
-                self._unheld = True          # this window saw scores the stream does not hold: no exact redo for it
-            self.pending += hi - lo
-            lo = hi
-            if self.pending >= self._window():
-                self.fold()
+        self._feed(_plane_source(scores, int(id_base), hold), 0, scores.shape[1])
 
     def feed_gemm(self, Qn: torch.Tensor, Dn: torch.Tensor, id_base: int, mark=None):
         """Score documents id_base .. id_base + len(Dn) - 1 against the queries and keep what beats the thresholds, in ONE kernel:
@@ -1025,44 +1062,17 @@ class TopkStream:
         L2-normalised float32, d % 4 == 0.  The documents are cut at the fold windows, one GEMM launch per piece."""
         _dev(Qn, torch.float32, "TopkStream.feed_gemm(Qn)"); _dev(Dn, torch.float32, "TopkStream.feed_gemm(Dn)")
         _need(Qn.shape[0] == self.rows and Qn.shape[1] == Dn.shape[1] and Qn.shape[1] % 4 == 0, "TopkStream.feed_gemm: [rows, d] x [n, d], d % 4 == 0")
-        Qn, Dn = Qn.contiguous(), Dn.contiguous()
-        lib = _lib.lib()
-        n, lo, d = Dn.shape[0], 0, Qn.shape[1]
-        self.unordered = True
-        while lo < n:
-            hi = min(n, lo + self._window() - self.pending)
-            piece = Dn[lo:hi]
-            check(lib.fz_dot_scores_filter_f32(_ptr(Qn), Qn.stride(0), _ptr(piece), Dn.stride(0), self.rows, hi - lo, d, int(id_base) + lo,
-                                               _ptr(self._tau_pad), _ptr(self.cand_s), _ptr(self.cand_i), _ptr(self.cand_len), self.cap,
-                                               _ptr(self.overflow), _stream(Qn)), "fz_dot_scores_filter_f32")
-            if mark: mark("shard_gemm_filter")
-            self._pieces.append(("gemm", Qn, piece, int(id_base) + lo))
-            self.pending += hi - lo
-            lo = hi
-            if self.pending >= self._window():
-                self.fold()
-                if mark: mark("shard_topk_stream")
+        self._feed(_gemm_source(Qn, Dn, int(id_base)), 0, Dn.shape[0], mark)
 
     def feed_sparse(self, index, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, doc_lo: int, doc_hi: int, id_base: int, mark=None):
         """Score documents [doc_lo, doc_hi) of a SparseIndex against the queries' term lists and keep what beats the thresholds, in ONE kernel
         per piece (fz_sparse_dot_filter_f32: the inverted-index walk with the filter in place of the plane store).  Document d gets the id
-        id_base + d.  The range is cut at the fold windows, rounded down to whole slices (sparse_pieces); the pieces hold views of the
-        index and the query lists, nothing is copied."""
+        id_base + d.  The range is cut at the fold windows, rounded down to whole slices; the pieces hold views of the index and the query
+        lists, nothing is copied."""
         Q = _sparse_queries(qoff, qterms, qw, "TopkStream.feed_sparse")
         _need(Q == self.rows, "TopkStream.feed_sparse: one query per running list")
         doc_lo, doc_hi = _sparse_range(index, doc_lo, doc_hi, "TopkStream.feed_sparse")
-        lib = _lib.lib()
-        self.unordered = True
-        for lo, hi, fold in sparse_pieces(doc_lo, doc_hi, self.seen, self.pending, self.k, self.cap, sparse_slice_docs()):
-            check(lib.fz_sparse_dot_filter_f32(_ptr(index.toff), _ptr(index.pdoc), _ptr(index.pw), _ptr(index.slice_off), _ptr(qoff), _ptr(qterms),
-                                               _ptr(qw), Q, index.N, lo, hi, int(id_base), _ptr(self.tau), _ptr(self.cand_s), _ptr(self.cand_i),
-                                               _ptr(self.cand_len), self.cap, _ptr(self.overflow), _stream(qoff)), "fz_sparse_dot_filter_f32")
-            if mark: mark("shard_sparse_filter")
-            self._pieces.append(("sparse", index, (qoff, qterms, qw), lo, hi, int(id_base)))
-            self.pending += hi - lo
-            if fold:
-                self.fold()
-                if mark: mark("shard_topk_stream")
+        self._feed(_sparse_source(index, qoff, qterms, qw, int(id_base)), doc_lo, doc_hi, mark)
 
     def fold(self):
         if self.pending == 0:
@@ -1082,17 +1092,8 @@ class TopkStream:
                 # a candidate list was cut short (or a tie run was too long to order): this window again, exactly, on top of the list as
                 # it stood before it -- per piece: scores -> fz_topk_rows_f32 -> merge (ties by ascending id, as everywhere)
                 ns, ni = self.best_s, self.best_i
-                for kind, *args in self._pieces:
-                    if kind == "gemm":
-                        Qn_, piece, base = args
-                        sc = dot_scores(Qn_, piece)
-                    elif kind == "sparse":
-                        index, ql, lo, hi, ib = args
-                        sc, base = sparse_dot(index, *ql, doc_lo=lo, doc_hi=hi), ib + lo
-                    else:
-                        sc, base = args
-                    if sc.shape[1] == 0:
-                        continue
+                for source, lo, hi in self._pieces:
+                    sc, base = source.plane(lo, hi)
                     ps, pi = topk_rows(sc, self.k, id_base=base)
                     ns, ni = topk_merge(torch.stack([ns, ps]), torch.stack([ni, pi]))
                 self.tau.copy_(ns[:, self.k - 1])

@@ -62,3 +62,20 @@ def quantile_table(pool, P):
     lo = np.floor(pos).astype(np.int64)
     hi = np.minimum(lo + 1, len(s) - 1)
     return s[lo] + (s[hi] - s[lo]) * (pos - lo)
+
+
+def planned_search_marks(ops, head, n, chunk, k, cap, grain, plane_mark, filter_mark):
+    """The marks a streamed sharded search of n documents must report, derived from the piece planner alone: the head's plane and the
+    opening of the stream, then per CHUNK-document feed one launch mark per planned piece with the stream's mark after every planned fold,
+    then the closing fold and the all-gather.  -> (marks, planned folds, feeds that start inside a window)."""
+    marks, folds, inside = [plane_mark, "shard_topk_stream"], 0, 0
+    seen, pending = head, 0
+    for c0 in range(head, n, chunk):
+        inside += pending > 0
+        for lo, hi, fold in ops.stream_pieces(c0, min(n, c0 + chunk), seen, pending, k, cap, grain):
+            marks.append(filter_mark)
+            pending += hi - lo
+            if fold:
+                marks.append("shard_topk_stream")
+                seen, pending, folds = seen + pending, 0, folds + 1
+    return marks + ["shard_topk_stream", "allgather_merge"], folds, inside

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
-from helpers import assert_ranked_close, load_lists, sparse_to_dense
+from helpers import assert_ranked_close, load_lists, planned_search_marks, sparse_to_dense
 
 pytestmark = pytest.mark.gpu
 
@@ -779,3 +779,24 @@ def test_fused_gemm_filter_flags_a_tie_run_it_cannot_order(ops, oracle):
     es, ei = oracle.topk_rows(ops.dot_scores(Qn, Dn).cpu().numpy(), k)
     np.testing.assert_array_equal(s.cpu().numpy(), es)
     np.testing.assert_array_equal(i.cpu().numpy(), ei)
+
+
+@pytest.mark.gpu
+def test_fused_gemm_filter_search_launches_one_kernel_per_planned_piece(ops):
+    """The marks of a fused ShardedDenseIndex.search are the ones the piece planner predicts: the head, then per CHUNK feed one
+    shard_gemm_filter per planned piece and a shard_topk_stream after every planned fold, then the closing fold and the all-gather --
+    with a small CAP (short windows: three planned folds) and a CHUNK that ends inside windows."""
+    from fusion_amd.distributed import ShardedDenseIndex
+    g = torch.Generator(device="cuda").manual_seed(1)
+    Q, N, d, k = 4, 120_000, 32, 100
+    Dn = ops.normalize_rows(torch.randn((N, d), generator=g, device="cuda"))
+    Qn = ops.normalize_rows(torch.randn((Q, d), generator=g, device="cuda"))
+    idx = ShardedDenseIndex(Dn, id_base=5)
+    idx.CAP, idx.CHUNK = 256, 30_000
+    exp, folds, inside = planned_search_marks(ops, 8192, N, idx.CHUNK, k, idx.CAP, 1, "shard_gemm", "shard_gemm_filter")
+    assert folds >= 3 and inside >= 1 and exp[-3] == "shard_gemm_filter"        # ... and the shard ends mid-window
+    marks = []
+    s, i = idx.search(Qn, k, mark=marks.append)
+    assert marks == exp
+    es, ei = ops.topk_rows(ops.dot_scores(Qn, Dn), k, id_base=5)
+    assert torch.equal(s, es) and torch.equal(i, ei)

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
-from helpers import assert_ranked_close
+from helpers import assert_ranked_close, planned_search_marks
 
 pytestmark = pytest.mark.gpu
 
@@ -185,6 +185,25 @@ def test_k_beyond_the_shard_pads(ops, big):
             assert torch.all(i[:, 195:] == -1) and torch.all(torch.isneginf(s[:, 195:]))
     s, i = ShardedSparseIndex(small, 0).local_topk(*ops.sparse_rows(Qd[:0], V), 10)
     assert s.shape == (0, 10) and i.shape == (0, 10)
+
+
+def test_search_launches_one_kernel_per_planned_piece(ops, big):
+    """The marks of ShardedSparseIndex.search are the ones the piece planner predicts: the head, then per CHUNK feed one shard_sparse_filter
+    per planned piece and a shard_topk_stream after every planned fold, then the closing fold and the all-gather -- with a small CAP (short
+    windows: three planned folds) and a CHUNK that ends inside windows."""
+    from fusion_amd.distributed import ShardedSparseIndex
+    idx, _, _, ql, full, _ = big
+    k = 100
+    shard = ShardedSparseIndex(idx, BASE)
+    shard.CAP, shard.CHUNK = 256, 5 * S
+    assert shard.head_docs(k) == 2 * S
+    exp, folds, inside = planned_search_marks(ops, 2 * S, N_BIG, shard.CHUNK, k, shard.CAP, S, "shard_sparse", "shard_sparse_filter")
+    assert folds >= 3 and inside >= 1 and exp[-3] == "shard_sparse_filter"      # ... and the shard ends mid-window
+    marks = []
+    g_sc, g_ids = shard.search(*ql, k=k, mark=marks.append)
+    assert marks == exp
+    e_sc, e_ids = ops.topk_rows(full, k, id_base=BASE)
+    assert torch.equal(g_ids, e_ids) and torch.equal(g_sc, e_sc)
 
 
 # ---- 4. every window overflows: the exact redo ------------------------------------------------------------------------------------

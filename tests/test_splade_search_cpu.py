@@ -1,5 +1,7 @@
 """Corpus-scale SPLADE search, host side (no GPU): the two ABI 20 entry points reject bad arguments before any HIP call, and the piece
-planning of TopkStream.feed_sparse cuts a document range into whole slices that cover it exactly once."""
+planning of TopkStream's feeds cuts a document range into whole grains (slices for feed_sparse, single documents otherwise) that cover it
+exactly once."""
+import numpy as np
 import pytest
 
 from fusion_amd import _lib, ops
@@ -86,7 +88,22 @@ def test_filter_entry_nothing_to_do(L):
     (7168, 7168, 7168, 0, 10, 7168),               # empty
 ])
 def test_sparse_pieces_are_whole_slices_covering_the_range_once(lo, hi, seen, pending, k, cap):
-    pieces = ops.sparse_pieces(lo, hi, seen, pending, k, cap, S)
+    check_pieces(lo, hi, seen, pending, k, cap, S)
+
+
+@pytest.mark.parametrize("lo,hi,seen,pending,k,cap", [
+    (8192, 1_105_228, 8192, 0, 1000, 7168),        # feed, feed_gemm: the dense shard after its head
+    (0, 150_000, 4096, 40_959, 100, 2000),         # pending one document below the window (40,960)
+    (5, 30_000, 512, 0, 7, 256),                   # the range ends mid-window
+    (0, 10_000, 1, 0, 1000, 64),                   # the 64-document minimum window
+    (9, 9, 4096, 3, 100, 2000),                    # empty
+])
+def test_stream_pieces_at_grain_one_cover_the_range_once(lo, hi, seen, pending, k, cap):
+    check_pieces(lo, hi, seen, pending, k, cap, 1)
+
+
+def check_pieces(lo, hi, seen, pending, k, cap, grain):
+    pieces = ops.stream_pieces(lo, hi, seen, pending, k, cap, grain)
     if lo == hi:
         assert pieces == []
         return
@@ -94,15 +111,15 @@ def test_sparse_pieces_are_whole_slices_covering_the_range_once(lo, hi, seen, pe
     for (a, b, _), (c, _, _) in zip(pieces, pieces[1:]):
         assert b == c                                      # back to back, ascending
     for a, b, _ in pieces:
-        assert a < b and a % S == 0
-        assert (b - a) % S == 0 or b == hi                 # whole slices, the last one may end at the range's end
-        assert b - a >= S or b == hi                        # at least one slice per piece
-    # the fold flags replay TopkStream's window bookkeeping (its window rounded down to whole slices): a fold where the window is full,
-    # and pieces never cross a window boundary by more than the one-slice minimum
+        assert a < b and a % grain == 0
+        assert (b - a) % grain == 0 or b == hi             # whole grains, the last one may end at the range's end
+        assert b - a >= grain or b == hi                   # at least one grain per piece
+    # the fold flags replay TopkStream's window bookkeeping (its window rounded down to whole grains): a fold where the window is full,
+    # and pieces never cross a window boundary by more than the one-grain minimum
     for a, b, fold in pieces:
-        win = max(S, ops.stream_window(seen, k, cap) // S * S)
+        win = max(grain, ops.stream_window(seen, k, cap) // grain * grain)
         room = win - pending
-        assert b - a <= max(S, room)
+        assert b - a <= max(grain, room)
         pending += b - a
         assert fold == (pending >= win)
         if fold:
@@ -111,8 +128,40 @@ def test_sparse_pieces_are_whole_slices_covering_the_range_once(lo, hi, seen, pe
 
 def test_sparse_pieces_windows_grow():
     """After the 14,336-document head at k = 1000 the windows grow geometrically: a 1.1 M-document shard folds a handful of times."""
-    pieces = ops.sparse_pieces(14336, 1_105_228, 14336, 0, 1000, 7168, S)
+    pieces = ops.stream_pieces(14336, 1_105_228, 14336, 0, 1000, 7168, S)
     folds = sum(f for _, _, f in pieces) + (not pieces[-1][2])    # + the one TopkStream.result() does on what is left
     assert 3 <= folds <= 8
     sizes = [b - a for a, b, _ in pieces]
     assert sizes[-1] >= sizes[0]
+
+
+def inline_cut(n, seen, pending, k, cap):
+    """The cut TopkStream.feed and feed_gemm made in place before they shared the planner: a piece ends where the window does (or at n),
+    and the stream folds when the window is full."""
+    out, lo = [], 0
+    while lo < n:
+        hi = min(n, lo + ops.stream_window(seen, k, cap) - pending)
+        pending += hi - lo
+        fold = pending >= ops.stream_window(seen, k, cap)
+        if fold:
+            seen, pending = seen + pending, 0
+        out.append((lo, hi, fold))
+        lo = hi
+    return out
+
+
+def test_stream_pieces_at_grain_one_are_the_inline_cut():
+    rng = np.random.default_rng(7)
+    cases = [(0, 4096, 0, 100, 2000),                          # nothing to feed
+             (150_000, 4096, 40_959, 100, 2000),               # pending one document below the window (40,960)
+             (150_000, 4096, 40_896, 100, 2000),               # ... and one 64-document step below it
+             (100_000, 8192, 0, 1000, 7168),                   # the range ends mid-window
+             (29_312, 8192, 0, 1000, 7168),                    # ... and exactly on the window's end
+             (1_097_036, 8192, 0, 1000, 7168)]                 # one eighth of mMARCO after the dense head
+    for _ in range(2000):
+        k, cap, seen = int(rng.integers(1, 2001)), int(rng.integers(2, 9001)), int(rng.integers(1, 2_000_000))
+        cases.append((int(rng.integers(0, 3_000_000)), seen, int(rng.integers(0, ops.stream_window(seen, k, cap))), k, cap))
+    for n, seen, pending, k, cap in cases:
+        assert pending < ops.stream_window(seen, k, cap)        # TopkStream's invariant between feeds
+        assert ops.stream_pieces(0, n, seen, pending, k, cap, 1) == inline_cut(n, seen, pending, k, cap), (n, seen, pending, k, cap)
+        assert ops.stream_pieces(0, n, seen, pending, k, cap) == inline_cut(n, seen, pending, k, cap)          # grain defaults to 1

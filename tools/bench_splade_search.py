@@ -75,18 +75,17 @@ def run(N, Q, k, reps):
     Qn = next(splade_blocks(2, Q, 40, block=Q))[1]
     ql = ops.sparse_rows(Qn, V)
     shard = ShardedSparseIndex(idx, 0)
-    chunk = shard.CHUNK
     fused_ms = timed(lambda: shard.local_topk(*ql, k), reps)
-    two_ms = timed(lambda: shard._exact_topk(*ql, k, chunk, lambda name: None), reps)
+    two_ms = timed(lambda: shard.two_pass_topk(ql, k), reps)
     f_s, f_i = shard.local_topk(*ql, k)
-    t_s, t_i = shard._exact_topk(*ql, k, chunk, lambda name: None)
+    t_s, t_i = shard.two_pass_topk(ql, k)
     cands, redone = window_stats(shard, ql, k)
     index_bytes = sum(t.numel() * t.element_size() for t in (idx.toff, idx.pdoc, idx.pw, idx.slice_off))
     res = dict(N=N, Q=Q, k=k, V=V, nnz=idx.nnz, postings_per_doc=round(idx.nnz / N, 1), query_terms=round(ql[1].numel() / Q, 1),
-               index_bytes=index_bytes, index_build_s=round(build_s, 2), head_docs=shard.head_docs(k), chunk_docs=chunk, cap=shard.CAP,
+               index_bytes=index_bytes, index_build_s=round(build_s, 2), head_docs=shard.head_docs(k), chunk_docs=shard.CHUNK, cap=shard.CAP,
                fused_ms=round(fused_ms, 2), two_pass_ms=round(two_ms, 2), fused_ms_per_1024q=round(fused_ms * 1024 / Q, 2),
                two_pass_ms_per_1024q=round(two_ms * 1024 / Q, 2), speedup=round(two_ms / fused_ms, 3),
-               two_pass_plane_bytes_per_chunk=Q * ops.round_up(chunk, 64) * 4, folds=len(cands), windows_redone=redone,
+               two_pass_plane_bytes_per_chunk=Q * ops.round_up(shard.CHUNK, 64) * 4, folds=len(cands), windows_redone=redone,
                candidates_per_window=cands, identical=bool(torch.equal(f_s, t_s) and torch.equal(f_i, t_i)), timing="best of %d, after one warm-up" % reps)
     print(json.dumps(res), flush=True)
     del idx, shard
