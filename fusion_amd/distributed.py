@@ -196,3 +196,57 @@ class ShardedSparseIndex(_ShardedIndex):
 
     def search(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, k: int = 1000, mark=None):
         return self._search((qoff, qterms, qw), k, mark)
+
+
+class ShardedTokenIndex:
+    """One rank's shard of a ColBERT corpus as its packed token matrix (Dtok_local [sumL, 128] float16, Doff_local [N + 1] int64;
+    documents 0 .. N-1 = global ids id_base ..) + the exact rerank of candidate lists over it: the corpus-scale counterpart of
+    ops.maxsim's [Q, N] plane, which the reference never builds either (its PLAID searcher scores candidates only, hybrid.py:108-137).
+    fz_maxsim_pairs_f16 scores every query against its own candidate ids with the bits of the all-pairs kernel; a slot this shard does
+    not own gets -inf, so the shards' [Q, k] planes combine by ONE all_reduce(MAX), and one stable descending row sort turns the plane
+    into lists (ties keep candidate-list order, whatever the number of shards).  No host synchronisation on the single-rank path."""
+
+    def __init__(self, Dtok_local: torch.Tensor, Doff_local: torch.Tensor, id_base: int, group=None, max_doc_len: int = 512):
+        self.Dtok, self.Doff, self.id_base, self.group, self.max_doc_len = Dtok_local, Doff_local, int(id_base), group, int(max_doc_len)
+
+    @classmethod
+    def from_encoder(cls, model, documents: list[str], id_base: int = 0, group=None, batch_size: int = 64, device=None):
+        """Encode this shard's documents with a ColBERT encoder (fusion_amd.encoders: encode_docs -> packed token rows + offsets)."""
+        Dtok, Doff = model.encode_docs(documents, batch_size=batch_size)
+        if device is None:
+            device = Dtok.device if Dtok.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        return cls(Dtok.to(device), Doff.to(device), id_base, group=group, max_doc_len=model.max_doc_length)
+
+    @property
+    def N(self) -> int:
+        return self.Doff.numel() - 1
+
+    def local_scores(self, Qtok: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
+        """[Q, k] float32: exact MaxSim of query q and candidate cand_ids[q, r]; -inf for a slot this shard does not own (r >= cand_len[q],
+        a negative id, a document of another shard)."""
+        return ops.maxsim_pairs(Qtok, self.Dtok, self.Doff, cand_ids, cand_len, id_base=self.id_base, max_doc_len=self.max_doc_len)
+
+    def rerank(self, Qtok: torch.Tensor, candidates, k: int | None = None):
+        """candidates: a planes.RankedTopk (its ids and lens are used) or a [Q, k0] int64 id tensor (negative ids = padding) -> RankedTopk of
+        the candidates in descending exact-MaxSim order, cut to the first k (default: all k0).  lens[q] = the slots some shard owned:
+        they come first (a NaN score first of all, as in every ranking sort here), the others hold (-inf, -1).  A score of -inf itself --
+        possible only with non-finite token values -- is indistinguishable from "owned by no shard" after the reduction and counts as
+        such."""
+        from .planes import RankedTopk
+        import torch.distributed as dist
+        ids, cand_len = (candidates.ids, candidates.lens) if isinstance(candidates, RankedTopk) else (candidates, None)
+        if ids.numel() == 0:
+            return RankedTopk(ids=ids.clone(), scores=torch.empty(ids.shape, dtype=torch.float32, device=ids.device),
+                              lens=torch.zeros(ids.shape[0], dtype=torch.int32, device=ids.device))
+        scores = self.local_scores(Qtok, ids, cand_len)
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
+            scores = scores.contiguous()      # the collective takes the [Q, k] block, not the padded plane
+            dist.all_reduce(scores, op=dist.ReduceOp.MAX, group=self.group)
+        order, _, _ = ops.sort_rows_desc(scores, want_keys=False)
+        k0 = ids.shape[1]
+        k = k0 if k is None else min(int(k), k0)
+        order = order[:, :k].long()
+        sorted_scores = torch.gather(scores, 1, order)      # the scores' own bits (the sort's key plane canonicalises -0.0 and NaN)
+        owned = sorted_scores != float("-inf")
+        out_ids = torch.where(owned, torch.gather(ids, 1, order), torch.full_like(order, -1))
+        return RankedTopk(ids=out_ids, scores=sorted_scores, lens=owned.sum(1, dtype=torch.int32))

@@ -215,6 +215,40 @@ def maxsim(Qtok: torch.Tensor, Dtok: torch.Tensor, Doff: torch.Tensor, out: torc
     return out
 
 
+def maxsim_pairs(Qtok: torch.Tensor, Dtok: torch.Tensor, Doff: torch.Tensor, cand: torch.Tensor, cand_len: torch.Tensor | None = None, *,
+                 id_base: int = 0, max_doc_len: int = 512, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Exact MaxSim of every query against its own candidates (fz_maxsim_pairs_f16): out[q, r] = the score ops.maxsim gives query q and
+    document cand[q, r] - id_base, bit for bit, with no [Q, N] plane.  cand [Q, k] int64 global ids (rows may be strided), cand_len [Q]
+    int32 or None (= k everywhere).  -inf where r >= cand_len[q], the id is negative or the document is not one of this shard's N
+    (id_base .. id_base + N - 1); an empty document scores 0.  `out` [Q, k] float32 may be a view of a wider plane: only its k columns
+    are written.  No host synchronisation."""
+    _dev(Qtok, torch.float16, "maxsim_pairs(Qtok)")
+    _dev(Dtok, torch.float16, "maxsim_pairs(Dtok)")
+    _dev(Doff, torch.int64, "maxsim_pairs(Doff)")
+    _dev(cand, torch.int64, "maxsim_pairs(cand)")
+    _need(Qtok.dim() == 3, "maxsim_pairs: Qtok must be [Q, Lq, dim]")
+    Qtok, Dtok, Doff = Qtok.contiguous(), Dtok.contiguous(), Doff.contiguous()
+    Q, Lq, dim = Qtok.shape
+    N = Doff.numel() - 1
+    _need(Dtok.dim() == 2 and Dtok.shape[1] == dim, f"maxsim_pairs: Dtok must be [sumL, {dim}]")
+    _need(Doff.dim() == 1 and N >= 0, "maxsim_pairs: Doff must hold N + 1 offsets")
+    _need(cand.dim() == 2 and cand.shape[0] == Q, f"maxsim_pairs: cand must be [Q = {Q}, k], got {tuple(cand.shape)}")
+    k = cand.shape[1]
+    if cand_len is not None:
+        _dev(cand_len, torch.int32, "maxsim_pairs(cand_len)")
+        _need(tuple(cand_len.shape) == (Q,), f"maxsim_pairs(cand_len): expected shape {(Q,)}, got {tuple(cand_len.shape)}")
+    if out is None:
+        out = alloc_plane(Q, k, torch.float32, Qtok.device)
+    else:
+        _dev(out, torch.float32, "maxsim_pairs(out)")
+        _need(tuple(out.shape) == (Q, k), f"maxsim_pairs(out): expected shape {(Q, k)}, got {tuple(out.shape)}")
+    _need(int(max_doc_len) >= 1, "maxsim_pairs: max_doc_len must be at least 1")
+    check(_lib.lib().fz_maxsim_pairs_f16(_ptr(Qtok), _ptr(Dtok), _ptr(Doff), int(Dtok.shape[0]), int(max_doc_len), Q, Lq, N, dim, _ptr(cand),
+                                         _ld(cand), _ptr(cand_len), k, int(id_base), _ptr(out), _ld(out), _stream(Qtok)),
+          "fz_maxsim_pairs_f16")
+    return out
+
+
 # ---------------------------------------------------------------------------------------
 # K5a / K6 sort
 # ---------------------------------------------------------------------------------------

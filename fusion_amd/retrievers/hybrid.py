@@ -172,6 +172,16 @@ class Ranker:
         return rs if as_device else rs.to_lists()
 
     @staticmethod
+    def multi_vector_rerank(queries: list[str], index, candidates, *, encoder, return_topk: int = None):
+        """The corpus-scale form of multi_vector_search: `index` is a fusion_amd.distributed.ShardedTokenIndex (this rank's shard of the
+        encoded corpus), `candidates` a planes.RankedTopk or a [Q, k] int64 tensor of global document ids (another system's lists, or
+        their union).  The queries are encoded with the ColBERT `encoder` and every candidate gets its exact MaxSim score -- the bits
+        multi_vector_search's plane holds for that pair -- with no plane over the corpus.  -> planes.RankedTopk in descending score order
+        (ties keep candidate order), cut to return_topk: what Aggregator.fuse_topk takes next to the dense, sparse and BM25 lists."""
+        Qtok = encoder.encode_queries(queries, batch_size=64)
+        return index.rerank(Qtok, candidates, k=return_topk)
+
+    @staticmethod
     def cross_encoder_search(queries: list[str], candidates: list, model_name_or_path: str, return_topk: int = None, *, model=None,
                              corpus: dict[int, str] = None):
         """monoBERT rerank (hybrid.py:139-163).  The reference's version is dead code (`docs` undefined at :159, and main passes

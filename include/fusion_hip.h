@@ -87,6 +87,21 @@ int fz_dot_scores_filter_f32(const float* Qn, int ldq, const float* Dn, int ldd,
  * (tests/test_gpu_maxsim_edges.py::test_special_values).  L2-normalised token vectors never get there. */
 int fz_maxsim_f16(const void* Qtok, const void* Dtok, const int64_t* Doff, int64_t sumL, int max_doc_len, int Q, int Lq, int N,
                   int dim, float* scores, int lds, void* stream);
+/* The corpus-scale form (csrc/rerank.hip): every query against ITS OWN candidate list, no [Q][N] plane.
+ * scores[q][r] = the MaxSim above of query q and document cand[q][r] - id_base, for r < k.  cand [Q][ldc] int64 global ids;
+ * cand_len [Q] int32 (NULL: k for every row); id_base = global id of this shard's document 0 (any int64).  Qtok, Dtok, Doff, sumL,
+ * max_doc_len, dim, Lq and the special-value definition are fz_maxsim_f16's, and so are the BITS: for every slot whose document
+ * is in range, scores[q][r] equals fz_maxsim_f16's scores[q][cand[q][r] - id_base] bit for bit on any input (the same MFMA
+ * chain, maximum and summation tree), so the all-pairs route and the candidate route of one system are interchangeable.
+ * A slot gets -inf when r >= cand_len[q], when its id is negative or when its position falls outside [0, N) -- which is how a shard
+ * answers for a document another shard owns: the shards' planes combine by an element-wise maximum.  An empty document scores 0;
+ * duplicate ids in a row are scored independently; columns k .. lds-1 of scores are left untouched.
+ * Argument checks in fz_maxsim_f16's order: null pointers where a non-empty tensor is needed, ldc < k, lds < k or negative sizes
+ * -> FZ_ERR_ARG; dim, Lq, alignment or max_doc_len > 16384 outside what is built -> FZ_ERR_UNSUPPORTED; Q == 0 or k == 0 -> FZ_OK
+ * with nothing launched.  No workspace. */
+int fz_maxsim_pairs_f16(const void* Qtok, const void* Dtok, const int64_t* Doff, int64_t sumL, int max_doc_len, int Q, int Lq, int N,
+                        int dim, const int64_t* cand, int ldc, const int32_t* cand_len, int k, int64_t id_base, float* scores,
+                        int lds, void* stream);
 
 /* ---- K5a/K6: stable descending row sort ---------------------------------------------- */
 /* Python sorted(..., reverse=True) is stable (bm25.py:104, hybrid.py:306).  For each row:
