@@ -198,6 +198,41 @@ class ShardedSparseIndex(_ShardedIndex):
         return self._search((qoff, qterms, qw), k, mark)
 
 
+class ShardedLexicalIndex(_ShardedIndex):
+    """One rank's shard of a BM25 / AtireBM25 / TF-IDF corpus: a retrievers.bm25 model of the shard's documents built with the WHOLE corpus's
+    statistics (`stats=LexicalStats.merge(...)`: global idf and avgdl) and its `id_base`, so every document scores what the whole index
+    gives it, bit for bit.  local_topk is the model's own streamed (or plane) top-k in float64; the shards' lists are all-gathered and merged
+    by one stable float64 row sort (ops.topk_merge64): ties go to the ascending global id, whatever the number of shards.  Of _ShardedIndex
+    it takes the constants and last_overflow only: the float32 loops (_topk, two_pass_topk) are not for float64 lists."""
+
+    PLANE_MARK = "shard_lexical"
+
+    def __init__(self, model, group=None):
+        self.model, self.id_base, self.group = model, int(model.id_base), group
+        self.CAP, self.CHUNK = model.CAP, model.CHUNK
+
+    _grain = property(lambda self: ops.lexical_slice_docs(self.model.lexical_mode() or "pv"))
+
+    def local_topk(self, queries: list[str], k: int, mark=None, streaming: bool | None = True):
+        """([Q, k] float64 scores, [Q, k] int64 global ids), score desc / id asc, over this shard (k cut to the shard's size).  Marks:
+        'shard_lexical' after a plane launch, 'shard_lexical_filter' after a filter launch, 'shard_topk_stream' after a fold."""
+        out = self.model._topk_device(queries, k, streaming=streaming, mark=mark)
+        self.last_overflow = self.model.last_overflow
+        return out
+
+    def search(self, queries: list[str], k: int = 1000, mark=None):
+        """-> planes.RankedTopk of the global top-k (scores64 kept; scores = their float32 roundings)."""
+        from .planes import RankedTopk
+        s, i = self.local_topk(queries, k, mark=mark)
+        if s.shape[1] < k:     # a shard smaller than k: pad to the common width of the collective
+            pad = k - s.shape[1]
+            s = torch.cat([s, torch.full((s.shape[0], pad), float("-inf"), dtype=s.dtype, device=s.device)], 1)
+            i = torch.cat([i, torch.full((i.shape[0], pad), -1, dtype=i.dtype, device=i.device)], 1)
+        s, i = allgather_topk(s, i, group=self.group, merge_fn=ops.topk_merge64)
+        if mark: mark("allgather_merge")
+        return RankedTopk.from_search(s.to(torch.float32), i, scores64=s)
+
+
 class ShardedTokenIndex:
     """One rank's shard of a ColBERT corpus as its packed token matrix (Dtok_local [sumL, 128] float16, Doff_local [N + 1] int64;
     documents 0 .. N-1 = global ids id_base ..) + the exact rerank of candidate lists over it: the corpus-scale counterpart of

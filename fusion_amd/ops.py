@@ -1264,6 +1264,209 @@ def tfidf_scores(toff, pdoc, ptf, idf, qoff, qterms, Q: int, N: int, slice_off: 
 
 
 # ---------------------------------------------------------------------------------------
+# BM25 / TF-IDF at corpus scale: range planes, the filter walk, the float64 stream
+# ---------------------------------------------------------------------------------------
+LEXICAL_MODES = {"pv": 0, "tfidf": 1}   # the walks csrc/bm25_stream.hip builds: the posting-value table (BM25, AtireBM25) and TF-IDF
+
+
+def lexical_slice_docs(mode: str) -> int:
+    """Documents one workgroup of the range / filter walks scores: 3,584 for 'pv', 7,168 for 'tfidf'; ranges start on a multiple of it."""
+    _need(mode in LEXICAL_MODES, f"lexical_slice_docs: mode must be one of {sorted(LEXICAL_MODES)}")
+    return int(_lib.lib().fz_lexical_slice_docs(LEXICAL_MODES[mode]))
+
+
+def _lexical_args(what: str, mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int, doc_lo: int, doc_hi, slice_off):
+    """The host-side contract the four lexical range entries share -> (doc_lo, doc_hi)."""
+    for t, dt, name in ((toff, torch.int64, "toff"), (pdoc, torch.int32, "pdoc"), (qoff, torch.int64, "qoff"), (qterms, torch.int32, "qterms"),
+                        (vals, torch.float64 if mode == "pv" else torch.int32, "pval" if mode == "pv" else "ptf")):
+        _need(_dev(t, dt, f"{what}({name})").is_contiguous(), f"{what}({name}) must be contiguous")
+    V = toff.numel() - 1
+    _need(V >= 0 and vals.numel() == pdoc.numel() > 0 and qoff.numel() == Q + 1 and qterms.numel() > 0,
+          f"{what}: toff [V + 1], one value per posting (at least one), qoff [Q + 1] and a non-empty qterms expected")
+    if mode == "tfidf":
+        _need(_dev(idf, torch.float64, f"{what}(idf)").is_contiguous() and idf.numel() == V, f"{what}: idf must hold one value per term")
+    if slice_off is not None:
+        NS = max(1, -(-int(N) // int(_lib.lib().fz_bm25_slice_docs())))
+        _need(_dev(slice_off, torch.int64, f"{what}(slice_off)").is_contiguous() and tuple(slice_off.shape) == (V, NS + 1),
+              f"{what}(slice_off): expected a contiguous [{V}, {NS + 1}] table (ops.bm25_slice_offsets)")
+    S = lexical_slice_docs(mode)
+    doc_hi = int(N) if doc_hi is None else int(doc_hi)
+    doc_lo = int(doc_lo)
+    _need(0 <= doc_lo <= doc_hi <= N and doc_lo % S == 0 and (doc_hi % S == 0 or doc_hi == N),
+          f"{what}: [{doc_lo}, {doc_hi}) must start on a multiple of {S} documents and end on one or at N = {N}")
+    return doc_lo, doc_hi
+
+
+def _range_plane64(Q: int, n: int, dev) -> torch.Tensor:
+    return torch.empty((max(Q, 1), max(round_up(n, _PAD), _PAD)), dtype=torch.float64, device=dev)[:Q, :n]
+
+
+def bm25_scores_range(toff, pdoc, pval, qoff, qterms, Q: int, N: int, doc_lo: int = 0, doc_hi: int | None = None,
+                      slice_off: torch.Tensor | None = None) -> torch.Tensor:
+    """Columns [doc_lo, doc_hi) of bm25_scores(pval=...)'s float64 plane, bit for bit, without the rest of it (fz_bm25_scores_range_pv_f64):
+    [Q, doc_hi - doc_lo], column j = document doc_lo + j.  doc_lo a multiple of lexical_slice_docs('pv'), doc_hi a multiple of it or N."""
+    doc_lo, doc_hi = _lexical_args("bm25_scores_range", "pv", toff, pdoc, pval, None, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
+    out = _range_plane64(Q, doc_hi - doc_lo, toff.device)
+    check(_lib.lib().fz_bm25_scores_range_pv_f64(_ptr(toff), _ptr(pdoc), _ptr(pval), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi,
+                                                 _ptr(out), _ld(out), _stream(toff)), "fz_bm25_scores_range_pv_f64")
+    return out
+
+
+def tfidf_scores_range(toff, pdoc, ptf, idf, qoff, qterms, Q: int, N: int, doc_lo: int = 0, doc_hi: int | None = None,
+                       slice_off: torch.Tensor | None = None) -> torch.Tensor:
+    """Columns [doc_lo, doc_hi) of tfidf_scores' float64 plane, bit for bit (fz_tfidf_scores_range_f64); slices of lexical_slice_docs('tfidf')."""
+    doc_lo, doc_hi = _lexical_args("tfidf_scores_range", "tfidf", toff, pdoc, ptf, idf, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
+    out = _range_plane64(Q, doc_hi - doc_lo, toff.device)
+    check(_lib.lib().fz_tfidf_scores_range_f64(_ptr(toff), _ptr(pdoc), _ptr(ptf), _ptr(idf), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo,
+                                               doc_hi, _ptr(out), _ld(out), _stream(toff)), "fz_tfidf_scores_range_f64")
+    return out
+
+
+def lexical_filter(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int, doc_lo: int, doc_hi: int, id_base: int, tau, cand_s, cand_i,
+                   cand_len, overflow, slice_off: torch.Tensor | None = None) -> None:
+    """The range walk with the threshold filter as its epilogue (fz_bm25_filter_pv_f64 / fz_tfidf_filter_f64): document d of [doc_lo, doc_hi)
+    is appended to row q of cand_s / cand_i [Q, cap] as (float64 score, id_base + d) iff !(score <= tau[q]); cand_len [Q] int32 counts on
+    past cap, nothing is stored there, `overflow` (int32 [1]) is set.  vals: pval ('pv') or ptf ('tfidf', with idf)."""
+    what = "lexical_filter"
+    doc_lo, doc_hi = _lexical_args(what, mode, toff, pdoc, vals, idf, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
+    _need(_dev(tau, torch.float64, f"{what}(tau)").is_contiguous() and tau.numel() == Q, f"{what}: tau must hold {Q} float64 thresholds")
+    _need(_dev(cand_s, torch.float64, f"{what}(cand_s)").is_contiguous() and _dev(cand_i, torch.int64, f"{what}(cand_i)").is_contiguous()
+          and cand_s.dim() == 2 and cand_s.shape[0] == Q and cand_s.shape[1] > 0 and cand_i.shape == cand_s.shape,
+          f"{what}: contiguous cand_s float64 / cand_i int64 [{Q}, cap] expected")
+    _need(_dev(cand_len, torch.int32, f"{what}(cand_len)").is_contiguous() and cand_len.numel() == Q
+          and _dev(overflow, torch.int32, f"{what}(overflow)").numel() >= 1, f"{what}: cand_len int32 [{Q}] and overflow int32 [1] expected")
+    cap, lib = cand_s.shape[1], _lib.lib()
+    if mode == "pv":
+        check(lib.fz_bm25_filter_pv_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi, int(id_base),
+                                        _ptr(tau), _ptr(cand_s), _ptr(cand_i), _ptr(cand_len), cap, _ptr(overflow), _stream(toff)), "fz_bm25_filter_pv_f64")
+    else:
+        check(lib.fz_tfidf_filter_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(idf), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi,
+                                      int(id_base), _ptr(tau), _ptr(cand_s), _ptr(cand_i), _ptr(cand_len), cap, _ptr(overflow), _stream(toff)),
+              "fz_tfidf_filter_f64")
+
+
+def _lexical_source(model, qoff, qterms, id_base: int) -> _Source:
+    """The lexical posting walk whose epilogue is the filter (TopkStream64): document d of the model's index = id id_base + d.  model: a
+    retrievers.bm25 TFIDF / BM25 / AtireBM25 whose lexical_mode() is 'pv' or 'tfidf' (lexical_tables(): the walk's per-posting values and idf)."""
+    mode = model.lexical_mode()
+    _need(mode in LEXICAL_MODES, "_lexical_source: the model's scoring mode has no range walk (BM25.USE_POSTING_VALUES = False)")
+    vals, idf = model.lexical_tables()
+    Q, N, so = qoff.numel() - 1, model.corpus_size, model.slice_off
+
+    def filter(st, lo, hi):
+        lexical_filter(mode, model.toff, model.pdoc, vals, idf, qoff, qterms, Q, N, lo, hi, id_base, st.tau, st.cand_s, st.cand_i, st.cand_len,
+                       st.overflow, slice_off=so)
+
+    def plane(lo, hi):
+        if mode == "pv":
+            return bm25_scores_range(model.toff, model.pdoc, vals, qoff, qterms, Q, N, lo, hi, slice_off=so), id_base + lo
+        return tfidf_scores_range(model.toff, model.pdoc, vals, idf, qoff, qterms, Q, N, lo, hi, slice_off=so), id_base + lo
+    return _Source(N, filter, plane, grain=lexical_slice_docs(mode), unordered=True, mark="shard_lexical_filter")
+
+
+def _merge_ranked64(best_s, best_i, s, i, seq: torch.Tensor | None = None, seq_len: torch.Tensor | None = None):
+    """The first k = best_s.shape[1] entries of the ranking (score desc, id asc) of [best | s]: ONE stable float64 row sort.  best: a ranked
+    list whose ids are all below those of (s, i); (s, i): in the sequence `seq` ([rows, m] columns of s, the first seq_len[row] of them) or as
+    they stand -- either way entries of equal score must come in ascending-id order, stability then gives the full ranking's tie rule.
+    Returns the scores' own bits (gathered through the order, not the sort's canonicalised key plane)."""
+    rows, k = best_s.shape
+    m, dev = s.shape[1], best_s.device
+    keys = as_plane(torch.cat([best_s, s], 1))
+    ids = torch.cat([best_i, i], 1)
+    init = row_len = None
+    if seq is not None:
+        init = torch.cat([torch.arange(k, dtype=torch.int32, device=dev).expand(rows, k), seq.to(torch.int32) + k], 1)
+        row_len = (seq_len.to(torch.int32) + k).contiguous()
+    order, _, _ = sort_rows_desc(keys, init_order=init, row_len=row_len, want_keys=False)
+    top = order[:, :k].long()
+    return torch.gather(keys, 1, top).contiguous(), torch.gather(ids, 1, top).contiguous()
+
+
+class TopkStream64(TopkStream):
+    """TopkStream for float64 lists, thresholds and candidate scores (BM25 / TF-IDF: the ranking is decided in float64).  The feed loop, the
+    windows and their bookkeeping are TopkStream's own (_feed, stream_pieces); the buffers and the fold are this class's.  The fold needs no
+    sort kernel of its own: the running list holds only documents seen earlier -- every id in it is below every candidate's -- and is
+    ordered (score desc, id asc); the window's candidates are put in ascending-id order (one argsort of the id slots, unwritten slots last)
+    and the stable float64 row sort orders the row [best (k) | candidates (<= cap)] once: ties go to the ascending id, the rule of the full
+    ranking.  Same overflow / windows_redone / exact_on_overflow contract; an overflowed window is redone from its pieces' range planes
+    (`top_positions(plane, k)`: the exact stable top-k of a plane, TFIDF._top_positions)."""
+
+    def __init__(self, run_scores: torch.Tensor, run_ids: torch.Tensor, seen: int, cap: int = 7168, exact_on_overflow: bool = True,
+                 top_positions=None):
+        _dev(run_scores, torch.float64, "TopkStream64(run_scores)"); _dev(run_ids, torch.int64, "TopkStream64(run_ids)")
+        rows, k = run_scores.shape
+        _need(tuple(run_ids.shape) == (rows, k) and seen > 0 and cap > 0, "TopkStream64: lists [rows, k], seen > 0, cap > 0 expected")
+        _need(k + cap <= sort_max_n(torch.float64), f"TopkStream64: k + cap = {k + cap} exceeds one float64 sort row ({sort_max_n(torch.float64)})")
+        dev = run_scores.device
+        self.rows, self.k, self.cap = rows, k, int(cap)
+        self.best_s, self.best_i = run_scores.contiguous(), run_ids.contiguous()
+        self.tau = self.best_s[:, k - 1].clone()
+        self.unordered = False
+        self.cand_s = torch.empty((rows, cap), dtype=torch.float64, device=dev)
+        self.cand_i = torch.empty((rows, cap), dtype=torch.int64, device=dev)
+        self.cand_len = torch.zeros(rows, dtype=torch.int32, device=dev)
+        self.overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.seen, self.pending = int(seen), 0
+        self.exact_on_overflow = bool(exact_on_overflow)
+        self.windows_redone = 0
+        self._pieces, self._unheld, self.unrepairable = [], False, False
+        self._top_positions = top_positions
+        self._slot = torch.arange(cap, dtype=torch.int32, device=dev)
+
+    def feed_lexical(self, model, qoff: torch.Tensor, qterms: torch.Tensor, doc_lo: int, doc_hi: int, id_base: int, mark=None):
+        """Score documents [doc_lo, doc_hi) of a lexical model's index and keep what beats the thresholds, in one kernel per piece."""
+        _need(qoff.numel() - 1 == self.rows, "TopkStream64.feed_lexical: one query per running list")
+        self._feed(_lexical_source(model, qoff, qterms, int(id_base)), doc_lo, doc_hi, mark)
+
+    def fold(self):
+        if self.pending == 0:
+            return
+        n = torch.clamp(self.cand_len, max=self.cap)
+        live = self._slot[None, :] < n[:, None]
+        by_id = torch.argsort(torch.where(live, self.cand_i, torch.iinfo(torch.int64).max), dim=1)       # ascending ids, unwritten slots last
+        ns, ni = _merge_ranked64(self.best_s, self.best_i, torch.where(live, self.cand_s, float("-inf")), self.cand_i, seq=by_id, seq_len=n)
+        if self.exact_on_overflow and not self.unrepairable and int(self.overflow.item()) != 0:
+            if self._unheld or self._top_positions is None:
+                self.unrepairable = True     # nothing to redo the window from: the flag stays set
+            else:
+                # a candidate list was cut short: this window again, exactly, on top of the list as it stood before it -- per piece:
+                # range plane -> exact top-k of it -> the same [best | piece] stable sort
+                ns, ni = self.best_s, self.best_i
+                for source, lo, hi in self._pieces:
+                    sc, base = source.plane(lo, hi)
+                    pos = self._top_positions(sc, min(self.k, hi - lo))
+                    ns, ni = _merge_ranked64(ns, ni, torch.gather(sc, 1, pos), pos + base)
+                self.overflow.zero_()
+                self.windows_redone += 1
+        self.tau.copy_(ns[:, self.k - 1])
+        self.cand_len.zero_()
+        self._pieces.clear()
+        self._unheld = False
+        self.best_s, self.best_i = ns, ni
+        self.seen += self.pending
+        self.pending = 0
+
+
+def topk_merge64(in_scores: torch.Tensor, in_ids: torch.Tensor):
+    """[G, rows, k] per-shard float64 lists (each score desc, id asc; shard g's ids all below shard g + 1's; padding = (-inf, -1)) -> the
+    global top-k [rows, k]: the shards side by side in rank order -- equal scores then stand in ascending-id order -- one stable float64 row
+    sort, the first k.  The scores' own bits come back."""
+    _dev(in_scores, torch.float64, "topk_merge64(in_scores)")
+    _dev(in_ids, torch.int64, "topk_merge64(in_ids)")
+    _need(in_scores.dim() == 3 and in_scores.shape == in_ids.shape, "topk_merge64: scores and ids must both be [G, rows, k]")
+    G, rows, k = in_scores.shape
+    if G * k > sort_max_n(torch.float64):
+        raise ValueError(f"topk_merge64: {G} lists of {k} entries exceed one float64 sort row ({sort_max_n(torch.float64)} keys)")
+    if G == 1 or rows == 0 or k == 0:
+        return in_scores[0].contiguous(), in_ids[0].contiguous()
+    keys = as_plane(in_scores.permute(1, 0, 2).reshape(rows, G * k))
+    ids = in_ids.permute(1, 0, 2).reshape(rows, G * k)
+    order, _, _ = sort_rows_desc(keys, want_keys=False)
+    top = order[:, :k].long()
+    return torch.gather(keys, 1, top).contiguous(), torch.gather(ids, 1, top).contiguous()
+
+
+# ---------------------------------------------------------------------------------------
 # A3, sparse form: SPLADE cosine scoring over an inverted index
 # ---------------------------------------------------------------------------------------
 class SparseIndex:

@@ -83,13 +83,53 @@ def expected_zero_share(df: np.ndarray, n_docs: int, query_terms: list[list[int]
     return float(per_query.mean())
 
 
-class TFIDF:
-    """bm25.py:33-127: score(q, d) = sum over q.split(), in order, of tf(t, d) * idf(t), idf = log10((N + 1) / (df + 1))."""
+class LexicalStats:
+    """The collection statistics a lexical model's idf table and BM25's avgdl are made from: number of documents, document frequency of
+    every word, total length in words.  Those of a whole corpus are the sums of its shards' (`merge`), so a shard's model built with the
+    merged statistics scores its documents exactly as the model of the whole corpus does."""
 
-    def __init__(self, corpus: list[str], device="cuda", slice_table_max_bytes: int | None = None):
+    def __init__(self, n_docs: int, df: dict[str, int], total_len: int):
+        self.n_docs, self.df, self.total_len = int(n_docs), df, int(total_len)
+
+    @property
+    def avgdl(self) -> float:
+        """total_len / n_docs on Python ints: correctly rounded, as statistics.mean of the lengths is (bm25.py:138)."""
+        return self.total_len / self.n_docs if self.n_docs else 0.0
+
+    @classmethod
+    def merge(cls, parts: list["LexicalStats"]) -> "LexicalStats":
+        df: Counter = Counter()
+        for p in parts:
+            df.update(p.df)
+        return cls(sum(p.n_docs for p in parts), dict(df), sum(p.total_len for p in parts))
+
+    def __eq__(self, other):
+        return isinstance(other, LexicalStats) and (self.n_docs, self.total_len, self.df) == (other.n_docs, other.total_len, other.df)
+
+    def __repr__(self):
+        return f"LexicalStats(n_docs={self.n_docs}, words={len(self.df)}, total_len={self.total_len})"
+
+
+class TFIDF:
+    """bm25.py:33-127: score(q, d) = sum over q.split(), in order, of tf(t, d) * idf(t), idf = log10((N + 1) / (df + 1)).
+
+    stats (a LexicalStats, default None): the index is one SHARD of a larger corpus -- idf comes from the global document count and the
+    global df of each local word (and BM25's avgdl from the global lengths); postings and vocabulary stay local.  id_base: the id of
+    document 0 in search_topk's lists.  Without them everything is as the reference has it."""
+
+    CAP = 7168            # candidate slots per query and window of the streamed search_topk (k + CAP: one float64 sort row)
+    CHUNK = 64 * 3584     # documents per feed of the streamed search_topk (whole slices of either walk)
+    HEAD = 28672          # at most this many leading documents get the exact top-k before the stream starts
+    STREAM_QUERIES = 1024 # queries per block of the streamed route
+
+    def __init__(self, corpus: list[str], device="cuda", slice_table_max_bytes: int | None = None, stats: LexicalStats | None = None,
+                 id_base: int = 0):
         self.corpus = corpus
         self.corpus_size = len(corpus)
         self.device = torch.device(device)
+        self.global_stats, self.id_base = stats, int(id_base)
+        self._idf_n = self.corpus_size if stats is None else stats.n_docs      # the N of the idf formulas
+        self.last_path, self.last_overflow = None, 0                           # of the last search_topk: 'stream' | 'plane', windows redone exactly
         toks = [doc.split() for doc in corpus]
         self.vocab: dict[str, int] = {}
         for t in toks:
@@ -103,7 +143,8 @@ class TFIDF:
         uniq, tf = np.unique(key, return_counts=True)
         pt, pd = uniq // max(self.corpus_size, 1), uniq % max(self.corpus_size, 1)
         self.df_host = np.bincount(pt, minlength=V).astype(np.int64)
-        self.idf_host = np.array([self._compute_idf(int(x)) for x in self.df_host], dtype=np.float64)
+        idf_df = self.df_host if stats is None else np.array([stats.df[w] for w in self.vocab], dtype=np.int64)   # (vocab: insertion order = term id)
+        self.idf_host = np.array([self._compute_idf(int(x)) for x in idf_df], dtype=np.float64)
         self.doc_len_host = np.array([len(t) for t in toks], dtype=np.int32)
         toff = np.zeros(V + 1, dtype=np.int64)
         np.cumsum(self.df_host, out=toff[1:])
@@ -132,7 +173,20 @@ class TFIDF:
         return sorted(self.vocab)
 
     def _compute_idf(self, df: int) -> float:
-        return math.log10((self.corpus_size + 1) / (df + 1))              # bm25.py:86-88
+        return math.log10((self._idf_n + 1) / (df + 1))                   # bm25.py:86-88
+
+    def stats(self) -> LexicalStats:
+        """This index's own collection statistics (of a shard: the shard's)."""
+        return LexicalStats(self.corpus_size, {w: int(self.df_host[t]) for w, t in self.vocab.items()}, int(self.doc_len_host.sum(dtype=np.int64)))
+
+    # -- what the range / filter walks of csrc/bm25_stream.hip take (ops._lexical_source) --
+    def lexical_mode(self) -> str | None:
+        """'tfidf' | 'pv' | None: the walk this model's scores() launches, if it has a range form."""
+        return "tfidf" if self.pdoc.numel() else None
+
+    def lexical_tables(self):
+        """(per-posting values, idf table or None) of that walk."""
+        return self.ptf, self.idf
 
     # -- queries -> CSR of term ids (kept for the last list of queries: the grid search scores the same queries 187 times) --
     def _query_csr(self, queries: list[str]):
@@ -189,12 +243,43 @@ class TFIDF:
                 out[lo:lo + len(chunk)] = self._top_positions(self.scores(chunk), k).cpu().numpy()
         return out
 
-    def search_topk(self, queries: list[str], k: int, budget_bytes: int = DEVICE_BUDGET_BYTES) -> RankedTopk:
+    def search_topk(self, queries: list[str], k: int, budget_bytes: int = DEVICE_BUDGET_BYTES, streaming: bool | None = None) -> RankedTopk:
         """The first min(k, N) entries of every ranked list as device-resident top-k lists (what Aggregator.fuse_topk takes): the positions
         ranked_positions computes, kept on the device, with their float64 scores gathered next to them (scores64; `scores` holds the
-        float32 roundings the normalisations take, hybrid.py:255).  ids = corpus positions."""
+        float32 roundings the normalisations take, hybrid.py:255).  ids = id_base + corpus position.
+
+        streaming: False -- the plane route: the whole [q, N] float64 plane per chunk of queries, ranked (N within one sort row) or cut
+        (_top_positions).  True -- the streamed route wherever it can run (_streams): an exact top-k of the first head_docs(k) documents,
+        then the posting walk with the threshold filter as its epilogue over the rest (no plane; ops.TopkStream64 folds the candidates a
+        few times) -- the same lists, bit for bit.  None: stream when N exceeds one float64 sort row.  BM25.USE_POSTING_VALUES = False
+        (the per-posting expression has no range walk) keeps the plane route.  last_path / last_overflow record what ran."""
+        sc64, ids = self._topk_device(queries, k, budget_bytes, streaming)
+        lens = torch.full((len(queries),), ids.shape[1], dtype=torch.int32, device=self.device)
+        return RankedTopk(ids=ids, scores=sc64.to(torch.float32), lens=lens, scores64=sc64)
+
+    def head_docs(self, k: int) -> int:
+        """Leading documents that get the exact top-k: 8,192 at k = 1000, rounded up to whole slices of the walk (10,752 / 14,336)."""
+        return ops.round_up(min(self.HEAD, max(8192, -(-8 * k // 4096) * 4096)), ops.lexical_slice_docs(self.lexical_mode()))
+
+    def _streams(self, k: int) -> bool:
+        if self.lexical_mode() is None or k <= 0:
+            return False
+        head = self.head_docs(k)
+        return k + self.CAP <= ops.sort_max_n(torch.float64) and k <= head // 8 and self.corpus_size > head
+
+    def _topk_device(self, queries: list[str], k: int, budget_bytes: int = DEVICE_BUDGET_BYTES, streaming: bool | None = None, mark=None):
+        """search_topk's ([Q, k] float64 scores, [Q, k] int64 ids); mark(name): optional instrumentation hook, called after every launch
+        group ('shard_lexical': a plane, 'shard_lexical_filter': a filter walk, 'shard_topk_stream': top-k work)."""
+        mark = mark or (lambda name: None)
         N, k = self.corpus_size, max(0, min(k, self.corpus_size))
         Q = len(queries)
+        if streaming is None:
+            streaming = N > ops.sort_max_n(torch.float64)
+        self.last_overflow = 0
+        if streaming and Q > 0 and self._streams(k):
+            self.last_path = "stream"
+            return self._stream_topk(queries, k, mark)
+        self.last_path = "plane"
         pos = torch.empty((Q, k), dtype=torch.int64, device=self.device)
         sc64 = torch.empty((Q, k), dtype=torch.float64, device=self.device)
         W = ops.sort_max_n(torch.float64)
@@ -202,15 +287,37 @@ class TFIDF:
         for lo in range(0, Q if k else 0, step):
             chunk = queries[lo:lo + step]
             if N <= W:
-                rs = self.search_device(chunk)
+                rs = self.search_device(chunk); mark("shard_lexical")
                 p, plane = rs.order[:, :k].long(), rs.scores64
             else:
-                plane = self.scores(chunk)
+                plane = self.scores(chunk); mark("shard_lexical")
                 p = self._top_positions(plane, k)
             pos[lo:lo + len(chunk)] = p
-            sc64[lo:lo + len(chunk)] = torch.gather(plane, 1, p)
-        lens = torch.full((Q,), k, dtype=torch.int32, device=self.device)
-        return RankedTopk(ids=pos, scores=sc64.to(torch.float32), lens=lens, scores64=sc64)
+            sc64[lo:lo + len(chunk)] = torch.gather(plane, 1, p); mark("shard_topk_exact")
+        return sc64, (pos + self.id_base if self.id_base else pos)
+
+    def _stream_topk(self, queries: list[str], k: int, mark):
+        N, Q = self.corpus_size, len(queries)
+        head = self.head_docs(k)
+        grain = ops.lexical_slice_docs(self.lexical_mode())
+        chunk = max(grain, self.CHUNK // grain * grain)
+        ids = torch.empty((Q, k), dtype=torch.int64, device=self.device)
+        sc64 = torch.empty((Q, k), dtype=torch.float64, device=self.device)
+        for lo in range(0, Q, self.STREAM_QUERIES):
+            block = queries[lo:lo + self.STREAM_QUERIES]
+            qoff, flat = self._query_csr(block)
+            src = ops._lexical_source(self, qoff, flat, self.id_base)
+            S, base = src.plane(0, head); mark("shard_lexical")
+            pos = self._top_positions(S, k)
+            stream = ops.TopkStream64(torch.gather(S, 1, pos), pos + base, seen=head, cap=self.CAP, top_positions=self._top_positions)
+            del S
+            mark("shard_topk_stream")
+            for c0 in range(head, N, chunk):
+                stream._feed(src, c0, min(N, c0 + chunk), mark)
+            bs, bi, _ = stream.result(); mark("shard_topk_stream")
+            self.last_overflow += stream.windows_redone
+            sc64[lo:lo + len(block)], ids[lo:lo + len(block)] = bs, bi
+        return sc64, ids
 
     def _query_step(self, k: int, budget_bytes: int) -> int:
         """Queries per chunk whose planes fit budget_bytes (at least one)."""
@@ -282,16 +389,28 @@ class BM25(TFIDF):
 
     USE_POSTING_VALUES = True   # False: the per-posting expression (fz_bm25_scores_f64_f32): A/B runs and tests of the two forms
 
-    def __init__(self, corpus: list[str], k1: float, b: float, device="cuda", slice_table_max_bytes: int | None = None):
+    def __init__(self, corpus: list[str], k1: float, b: float, device="cuda", slice_table_max_bytes: int | None = None,
+                 stats: LexicalStats | None = None, id_base: int = 0):
         self.k1, self.b = k1, b
         self._pval = None
-        super().__init__(corpus, device=device, slice_table_max_bytes=slice_table_max_bytes)
-        self.avgdl = float(mean(self.doc_len_host.tolist())) if self.corpus_size else 0.0   # bm25.py:138
+        super().__init__(corpus, device=device, slice_table_max_bytes=slice_table_max_bytes, stats=stats, id_base=id_base)
+        if stats is None:
+            self.avgdl = float(mean(self.doc_len_host.tolist())) if self.corpus_size else 0.0   # bm25.py:138
+        else:
+            self.avgdl = stats.avgdl                                       # the whole corpus's mean length, the same correctly rounded quotient
         self._norm_key, self._norm = None, None
 
     def _compute_idf(self, df: int) -> float:
-        N = self.corpus_size
+        N = self._idf_n
         return math.log10((N - df + 0.5) / (df + 0.5))                    # bm25.py:145-147
+
+    def lexical_mode(self) -> str | None:
+        """'pv' with the posting-value table (the default); USE_POSTING_VALUES = False -- the per-posting expression -- has no range walk."""
+        return "pv" if self.USE_POSTING_VALUES and self.pdoc.numel() else None
+
+    def lexical_tables(self):
+        self._doc_norm()                                                  # (re)tabulates the posting values for the current (k1, b)
+        return self._pval, None
 
     def update_params(self, k1: float, b: float) -> None:
         self.k1, self.b = k1, b
@@ -372,7 +491,7 @@ class AtireBM25(BM25):
     """bm25.py:164-173 (https://www.cs.otago.ac.nz/homepages/andrew/papers/2014-2.pdf): BM25's score with TFIDF's idf."""
 
     def _compute_idf(self, df: int) -> float:
-        return math.log10((self.corpus_size + 1) / (df + 1))
+        return math.log10((self._idf_n + 1) / (df + 1))
 
 
 # ---------------------------------------------------------------------------------------------------

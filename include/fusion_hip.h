@@ -462,6 +462,35 @@ int fz_sparse_dot_filter_f32(const int64_t* toff, const int32_t* pdoc, const flo
                              const int32_t* qterms, const float* qw, int Q, int N, int doc_lo, int doc_hi, int64_t id_base, const float* tau,
                              float* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow, void* stream);
 
+/* ---- A1 at corpus scale: the lexical posting walk over a document range, plane or filter epilogue (csrc/bm25_stream.hip; ABI 20, additive) ----
+ * The walks of fz_bm25_scores_pv_f64_f32 (BM25 / AtireBM25 from the posting-value table) and fz_tfidf_scores_f64 for the documents
+ * [doc_lo, doc_hi) of an index of N documents only.  A workgroup scores one (query, slice) of fz_lexical_slice_docs(tfidf) documents:
+ * 3,584 for the posting-value walk (tfidf = 0), 7,168 for TF-IDF (tfidf != 0) -- one or two grains of fz_bm25_slice_docs().
+ * doc_lo must be a multiple of that slice, doc_hi a multiple of it or N.  slice_off (nullable): fz_bm25_slice_offsets' table for the WHOLE
+ * index (row stride from N); without it every workgroup finds its posting sub-ranges by binary search.  Per document the score is the
+ * same chain of float64 adds in query-term order as the full-plane kernels make (terms not de-duplicated, id -1 adds nothing):
+ * scores [Q][lds] float64, lds >= doc_hi - doc_lo, column j = document doc_lo + j = the full plane's column doc_lo + j, bit for bit.
+ * Checks, in this order: Q < 0, a bad range or lds -> FZ_ERR_ARG; Q == 0 or an empty range -> FZ_OK, nothing launched; then null pointers
+ * (every array but slice_off: an index without postings has nothing to walk) -> FZ_ERR_ARG. */
+int fz_lexical_slice_docs(int tfidf);
+int fz_bm25_scores_range_pv_f64(const int64_t* toff, const int32_t* pdoc, const double* pval, const int64_t* slice_off, const int64_t* qoff,
+                                const int32_t* qterms, int Q, int N, int doc_lo, int doc_hi, double* scores, int lds, void* stream);
+int fz_tfidf_scores_range_f64(const int64_t* toff, const int32_t* pdoc, const int32_t* ptf, const double* idf, const int64_t* slice_off,
+                              const int64_t* qoff, const int32_t* qterms, int Q, int N, int doc_lo, int doc_hi, double* scores, int lds,
+                              void* stream);
+/* The same walks with the streaming top-k's threshold filter in place of the plane store -- NO score plane is written.  Document d enters
+ * query q's candidate list iff !(score <= tau[q]) (greater, or NaN; tau [Q] float64), appended as (float64 score, int64 id_base + d):
+ * cand_scores / cand_ids [Q][cap], cand_len [Q] int32 (the caller zeroes it; it keeps counting past cap), in arrival order.  Nothing is
+ * written at or past slot cap; a workgroup that had to drop a candidate sets *overflow to 1.  Checks as above with cap <= 0 among the
+ * FZ_ERR_ARG cases and tau, cand_scores, cand_ids, cand_len, overflow among the pointers. */
+int fz_bm25_filter_pv_f64(const int64_t* toff, const int32_t* pdoc, const double* pval, const int64_t* slice_off, const int64_t* qoff,
+                          const int32_t* qterms, int Q, int N, int doc_lo, int doc_hi, int64_t id_base, const double* tau,
+                          double* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow, void* stream);
+int fz_tfidf_filter_f64(const int64_t* toff, const int32_t* pdoc, const int32_t* ptf, const double* idf, const int64_t* slice_off,
+                        const int64_t* qoff, const int32_t* qterms, int Q, int N, int doc_lo, int doc_hi, int64_t id_base,
+                        const double* tau, double* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow,
+                        void* stream);
+
 /* ---- encoder side: the per-sequence parts of SentenceTransformer.encode (hybrid.py:97-102) on PACKED token rows -- */
 /* Self-attention of a BERT/CamemBERT layer for ragged sequences without padding: for every sequence and head,
  * out = softmax(q k^T * scale) v in fp32 (MFMA products, online softmax over 16-key tiles), scale > 0.  qkv [T][ld] = fused
