@@ -22,14 +22,9 @@
 //
 // LDS: ids [cap] int64 + table [2 * cap rounded up to a power of two] uint32 + 16 wave totals, cap = min(sum of the list widths,
 // 8,192) of the CALL: 128 KB + 64 B at the capacity (one workgroup per CU), 56 KB for three lists of 1,000 (two per CU).
-#include "common.h"
+#include "lists.h"
 
 namespace fz {
-
-constexpr int LJ_T = 1024;                 // threads per workgroup = entries per chunk
-constexpr int LJ_MAX_ENTRIES = 8192;       // fz_lists_max_entries(): FZ_MAX_SYSTEMS x 1,024
-constexpr uint32_t LJ_EMPTY = 0xffffffffu;
-constexpr uint32_t LJ_COL = 0xffffu;       // low half of a slot: the column; bits 16..23: the systems that list it
 
 struct JoinArgs {
     const int64_t* ids[FZ_MAX_SYSTEMS];
@@ -41,13 +36,6 @@ struct JoinArgs {
     int S, ld_out, cap, table_size;
     unsigned f64_mask, narrow_mask;
 };
-
-__device__ __forceinline__ uint32_t lj_hash(int64_t id, uint32_t mask) {
-    // multiplicative (Fibonacci) hashing on the full 64 bits, high half folded in: ids that differ only above bit 32, or by
-    // multiples of the table size, spread like any others
-    const uint64_t h = (uint64_t)id * 0x9E3779B97F4A7C15ull;
-    return (uint32_t)(h >> 40) & mask;
-}
 
 // METHOD: FZ_LISTS_RRF / FZ_LISTS_BCF / FZ_LISTS_WSUM_F32 / FZ_LISTS_WSUM_F64.  ACC = float for WSUM_F32, double otherwise.
 template <int METHOD, typename ACC>

@@ -859,6 +859,69 @@ def lists_join(ids: list[torch.Tensor], lens: list[torch.Tensor], method: str, v
     return out_ids, out_scores, out_len
 
 
+def lists_columns(ids: list[torch.Tensor], lens: list[torch.Tensor], values: list[torch.Tensor] | None = None,
+                  gold_ids: torch.Tensor | None = None):
+    """The per-query id join of lists_join, to per-system COLUMNS instead of one fused row (fz_lists_columns): the form gold_ranks /
+    tune_metrics take, for top-k lists over any int64 ids.  ids[s] [Q, k_s] int64, lens[s] [Q] int32, values[s] [Q, k_s] float32
+    (None: an ids / pos / gold-only join), gold_ids [Q, G] int64 (negative = padding; None: no gold look-up).
+    Returns (out_ids [Q, n] int64, T: list of S [Q, n] float32 planes (None without values), pos [Q, n] int32, out_len [Q] int32,
+    gold_col [Q, G] int32), n = sum of k_s, every plane with the same row stride.  Column c < out_len[q] is the c-th id of the
+    fused dict's first-insertion order: out_ids holds the id (-1 beyond out_len), T[s] system s's value for it (+0.0 where s does
+    not list it, and beyond out_len), pos holds c (-1 beyond); gold_col holds the column of each gold id, -1 for padding or an id in
+    no list.  An id listed twice inside one list raises ValueError (one flag read per call)."""
+    S = len(ids)
+    _max_systems(S, "lists_columns")
+    _need(S >= 1, "lists_columns: no system")
+    _need(len(lens) == S, f"lists_columns: {S} id lists but {len(lens)} length vectors")
+    _need(values is None or len(values) == S, f"lists_columns: needs {S} value planes")
+    ids = [_dev(t, torch.int64, "lists_columns(ids)") for t in ids]
+    Q = ids[0].shape[0]
+    for t in ids:
+        _need(t.dim() == 2 and t.shape[0] == Q, f"lists_columns(ids): every system needs a [{Q}, k] tensor, got {tuple(t.shape)}")
+    total = sum(int(t.shape[1]) for t in ids)
+    cap = lists_max_entries()
+    _need(total <= cap, f"lists_columns: the lists of one query hold up to {total} entries, a join takes at most {cap} (fz_lists_max_entries)")
+    lens = [_dev(t, torch.int32, "lists_columns(lens)").contiguous() for t in lens]
+    for t in lens:
+        _need(t.numel() == Q, f"lists_columns(lens): expected {Q} lengths, got {t.numel()}")
+    vals = None
+    if values is not None:
+        vals = []
+        for s, v in enumerate(values):
+            _dev(v, torch.float32, "lists_columns(values)")
+            _need(tuple(v.shape) == tuple(ids[s].shape), f"lists_columns(values): system {s} has ids {tuple(ids[s].shape)} but values {tuple(v.shape)}")
+            if _ld(v) != _ld(ids[s]):       # one row stride per system: ids and values side by side
+                ids[s], v = ids[s].contiguous(), v.contiguous()
+            vals.append(v)
+    dev = ids[0].device
+    if gold_ids is None:
+        gold_ids = torch.empty((Q, 0), dtype=torch.int64, device=dev)
+    _dev(gold_ids, torch.int64, "lists_columns(gold_ids)")
+    _need(gold_ids.dim() == 2 and gold_ids.shape[0] == Q, f"lists_columns(gold_ids): expected a [{Q}, G] tensor, got {tuple(gold_ids.shape)}")
+    gold_ids = gold_ids.contiguous()
+    G = int(gold_ids.shape[1])
+    out_len = torch.empty(Q, dtype=torch.int32, device=dev)
+    gold_col = torch.empty((Q, G), dtype=torch.int32, device=dev)
+    out_ids = alloc_plane(Q, total, torch.int64, dev)
+    pos = alloc_plane(Q, total, torch.int32, dev)
+    T = [alloc_plane(Q, total, torch.float32, dev) for _ in range(S)] if vals is not None else None
+    if Q == 0 or total == 0:                # nothing to join, nothing launched: the (empty) planes aside, no list holds any id
+        out_len.zero_(); gold_col.fill_(-1)
+        return out_ids, T, pos, out_len, gold_col
+    ld_out = _same_ld(out_ids, pos, *(T or []))
+    lib = _lib.lib()
+    ws = torch.empty(max(int(lib.fz_lists_columns_workspace_bytes(S, Q)), 4), dtype=torch.uint8, device=dev)
+    n_h = (C.c_int32 * S)(*[int(t.shape[1]) for t in ids])
+    ld_h = (C.c_int32 * S)(*[max(_ld(t), int(t.shape[1])) for t in ids])
+    check(lib.fz_lists_columns(_ptr_array(ids), _ptr_array(lens), _ptr_array(vals) if vals is not None else None, n_h, ld_h, S, Q,
+                               _ptr(gold_ids) if G else None, G, _ptr(out_ids), _ptr_array(T) if T is not None else None, _ptr(pos),
+                               _ptr(out_len), _ptr(gold_col) if G else None, ld_out, _ptr(ws), ws.numel(), _stream(ids[0])),
+          "fz_lists_columns")
+    if int(ws[:4].view(torch.int32).item()) != 0:
+        raise ValueError("lists_columns: a list holds the same id twice (ids inside one system's list must be distinct)")
+    return out_ids, T, pos, out_len, gold_col
+
+
 def gold_ranks(T: list[torch.Tensor], pos: torch.Tensor, weights: torch.Tensor, gold: torch.Tensor) -> torch.Tensor:
     """Fused ranks of the gold documents for every weight vector (N1, hybrid.py:404-426).
     T[s] [Q,N] normalised planes, pos [Q,N] int32 insertion positions (-1 absent), weights [W,S] fp32,

@@ -479,22 +479,7 @@ class Aggregator:
             w = [linear_weights[n] for n in names]          # KeyError when a system has no weight (hybrid.py:214)
             wide = [cls._wide(x) for x in w]
             if normalization in ("min-max", "z-score", "arctan", "percentile-rank", "normal-curve-equivalent"):
-                dev = S[0].ids.device
-                tabled = normalization in ("percentile-rank", "normal-curve-equivalent")
-                T = []
-                for n, s in zip(names, S):
-                    if s.k == 0:
-                        T.append(s.scores)
-                        continue
-                    # the list IS a plane of k columns in list order (rank plane: r where r < len, else -1): the same kernels and the
-                    # same statistics as the dense path, transformed with weight 1 (fl32(t * 1) + 0 == t); the join weights and sums
-                    r = torch.arange(s.k, dtype=torch.int32, device=dev)
-                    rank = ops.alloc_plane(Q, s.k, torch.int32, dev)
-                    rank.copy_(torch.where(r[None, :] < s.lens[:, None], r[None, :], torch.full_like(r, -1)[None, :]))
-                    rs = RankedSystem(scores=ops.as_plane(s.scores), order=rank, rank=rank, lens=s.lens, ids=None, full=False)
-                    distr = [cls._table(percentile_distributions.get(n), dev)] if tabled else None
-                    st = [rs.stats(normalization)] if normalization in ("min-max", "z-score") else None
-                    T.append(cls._normalised_planes([rs], normalization, distr, st)[0])
+                T = cls._normalised_lists(names, S, normalization, percentile_distributions)
                 if any(wide):
                     joined = ops.lists_join(ids, lens, "wsum64", T, w, narrow=[not x for x in wide])
                 else:
@@ -514,6 +499,29 @@ class Aggregator:
         if topk is not None and topk < n:
             return FusedTopk(ids=fids[:, :topk], scores=sk[:, :topk], lens=torch.clamp(out_len, max=topk))
         return FusedTopk(ids=fids, scores=sk, lens=out_len)
+
+    @classmethod
+    def _normalised_lists(cls, names, S, normalization, percentile_distributions):
+        """Every system's top-k list, transformed by one of the five normalisations with weight 1, as a [Q, k] float32 plane in list order
+        (what fuse_topk's join weights and sums, and what tune_topk's join scatters to columns)."""
+        dev = S[0].ids.device
+        Q = S[0].Q
+        tabled = normalization in ("percentile-rank", "normal-curve-equivalent")
+        T = []
+        for n, s in zip(names, S):
+            if s.k == 0:
+                T.append(s.scores)
+                continue
+            # the list IS a plane of k columns in list order (rank plane: r where r < len, else -1): the same kernels and the
+            # same statistics as the dense path, transformed with weight 1 (fl32(t * 1) + 0 == t); the join weights and sums
+            r = torch.arange(s.k, dtype=torch.int32, device=dev)
+            rank = ops.alloc_plane(Q, s.k, torch.int32, dev)
+            rank.copy_(torch.where(r[None, :] < s.lens[:, None], r[None, :], torch.full_like(r, -1)[None, :]))
+            rs = RankedSystem(scores=ops.as_plane(s.scores), order=rank, rank=rank, lens=s.lens, ids=None, full=False)
+            distr = [cls._table(percentile_distributions.get(n), dev)] if tabled else None
+            st = [rs.stats(normalization)] if normalization in ("min-max", "z-score") else None
+            T.append(cls._normalised_planes([rs], normalization, distr, st)[0])
+        return T
 
     # -- N1: the whole weight grid in one pass (hybrid.py:404-426) ----------------------------------
     @classmethod
@@ -607,6 +615,92 @@ class Aggregator:
             fused = cls.fuse_device(systems, "nsf", normalization, w, percentile_distributions, topk=1000)   # every cut-off is <= 1000
             out.append(run_evaluation(fused.predictions(1000), labels, print2console=False))
         return out
+
+    # -- the weight grid over top-k lists: per-query join to columns (csrc/lists_tune.hip) -----------------------
+    @staticmethod
+    def _gold_ids(labels, Q, dev):
+        """Labels (global ids) -> per query its distinct gold ids in order, as a [Q, G'] int64 device tensor padded with -1 to a multiple
+        of fz_tune_max_gold(); the largest gold count; len(ground_truths) per query, the reference's divisor."""
+        ops._need(len(labels) == Q, f"labels for {len(labels)} queries, ranked lists for {Q}")
+        G = int(ops._lib.lib().fz_tune_max_gold())
+        gold_lists = [list(dict.fromkeys(gl)) for gl in labels]   # unique, order kept
+        Gmax = max((len(g) for g in gold_lists), default=0)
+        gold = np.full((Q, max(ops.round_up(Gmax, G), G)), -1, dtype=np.int64)
+        for q, gl in enumerate(gold_lists):     # (a label no int64 holds is in no list: -1, like the padding)
+            gold[q, :len(gl)] = [int(g) if -(1 << 63) <= int(g) < (1 << 63) else -1 for g in gl]
+        return torch.from_numpy(gold).to(dev), Gmax, np.array([len(gl) for gl in labels], dtype=np.int64)
+
+    @staticmethod
+    def _metrics_of_gold_ranks(rk, gold_col, pos, n_gold, dev):
+        """run_evaluation's metrics per weight vector from [W, Q, G] gold ranks on the device (tune's own tail) -> list of dicts."""
+        from ..utils.metrics import MAP_KS, MRR_KS, NDCG_KS, RECALL_KS, gold_rank_tables
+        table, idcg, mnames = gold_rank_tables(n_gold)
+        means = ops.tune_metrics(rk, gold_col, pos, torch.from_numpy(n_gold.astype(np.int32)).to(dev), torch.from_numpy(idcg).to(dev),
+                                 torch.from_numpy(table).to(dev), dict(recall=RECALL_KS, map=MAP_KS, mrr=MRR_KS, ndcg=NDCG_KS)).cpu().numpy()
+        return [dict(zip(mnames, row)) for row in means.tolist()]   # Python floats, as run_evaluation returns
+
+    @classmethod
+    def tune_topk(cls, systems: dict[str, RankedTopk], normalization: str, weight_combinations: list[dict[str, float]], labels: list[list],
+                  percentile_distributions: dict[str, np.ndarray] = None) -> list[dict]:
+        """Aggregator.tune for the lists the corpus-scale searches return (RankedTopk; labels are global ids): for every weight vector
+        w the metrics of run_evaluation(fuse_topk(systems, 'nsf', normalization, w, distr).predictions(1000), labels), with tune's
+        results, key order and Python-float types.  The lists are normalised once, exactly as fuse_topk normalises them; one workgroup
+        per query joins them on their ids to per-system columns in first-insertion order (ops.lists_columns) and finds the gold ids'
+        columns; the counting and metric kernels of the dense sweep (ops.gold_ranks, ops.tune_metrics) then run unchanged on rows of
+        at most sum-of-k columns -- no plane over the corpus or over the batch's union of ids, nothing fused or sorted per vector.
+        'none' / unknown normalisations, more than 4 systems and grids that mix Python-float and np.float64 weights take one
+        fuse_topk + run_evaluation per vector.  Weights must be finite (an infinite weight times a system's 0 for an id it does not
+        list would be NaN here, where the reference adds nothing), as for tune."""
+        from ..utils.metrics import metrics_from_gold_ranks
+        names = list(systems.keys())
+        ops._max_systems(len(names), "Aggregator.tune_topk")
+        S = [systems[n] for n in names]
+        Q = S[0].Q
+        assert all(s.Q == Q for s in S), (
+            "Ranked results from different retrieval systems have varying lenghts across systems (i.e., some systems have been run on more queries).")
+        kinds = {cls._wide(x) for w in weight_combinations for x in w.values()}
+        if (normalization not in ("min-max", "z-score", "arctan", "percentile-rank", "normal-curve-equivalent") or len(S) > 4
+                or len(kinds) > 1):
+            out = []
+            for w in weight_combinations:      # generic path, as _tune_by_fusing: one device fusion + evaluation per weight vector
+                fused = cls.fuse_topk(systems, "nsf", normalization, w, percentile_distributions, topk=1000)   # every cut-off is <= 1000
+                perf = run_evaluation(fused.predictions(1000), labels, print2console=False)
+                out.append({k: float(v) for k, v in perf.items()})   # Python floats, as the fast path returns (nDCG comes as np.float64)
+            return out
+        wide = kinds == {True}
+        dev = S[0].ids.device
+        weights = torch.tensor([[float(w[n]) for n in names] for w in weight_combinations],      # KeyError as hybrid.py:214
+                               dtype=torch.float64).reshape(len(weight_combinations), len(names)).to(torch.float64 if wide else torch.float32).to(dev)
+        Tn = cls._normalised_lists(names, S, normalization, percentile_distributions)
+        gold_dev, Gmax, n_gold = cls._gold_ids(labels, Q, dev)
+        _, T, pos, out_len, gold_col = ops.lists_columns([s.ids for s in S], [s.lens for s in S], Tn, gold_dev)
+        G = int(ops._lib.lib().fz_tune_max_gold())
+        if Gmax <= G:   # ranks -> metrics stay on the device: [W, 15] float64 come back
+            return cls._metrics_of_gold_ranks(ops.gold_ranks(T, pos, weights, gold_col), gold_col, pos, n_gold, dev)
+        INF = np.iinfo(np.int64).max
+        ranks = np.full((len(weight_combinations), Q, Gmax), INF, dtype=np.int64)
+        for g0 in range(0, Gmax, G):
+            chunk = gold_col[:, g0:g0 + G].contiguous()
+            out = ops.gold_ranks(T, pos, weights, chunk).cpu().numpy().astype(np.int64)
+            blk = np.where((chunk.cpu().numpy() >= 0)[None, :, :] & (out < 1000), out, INF)   # in no list, or beyond predictions(1000): never retrieved
+            ranks[:, :, g0:g0 + G] = blk[:, :, : Gmax - g0]
+        return metrics_from_gold_ranks(ranks, n_gold, np.minimum(out_len.cpu().numpy(), 1000))
+
+    @classmethod
+    def evaluate_topk(cls, ranked, labels: list[list]) -> dict:
+        """run_evaluation(ranked.predictions(1000), labels, print2console=False) for a RankedTopk or a FusedTopk, on the device: a
+        corpus-scale run is scored without bringing Q x k ids to the host.  A one-system ids-only join (ops.lists_columns) finds every
+        gold id's column, which IS its list position; those ranks go through the sweep's metric kernel as one weight vector.  Only the
+        first 1000 entries of a list are looked at, as predictions(1000) cuts it."""
+        from ..utils.metrics import metrics_from_gold_ranks
+        ids, lens = ranked.ids[:, :1000], torch.clamp(ranked.lens, max=1000).to(torch.int32)
+        Q, dev = ids.shape[0], ids.device
+        gold_dev, Gmax, n_gold = cls._gold_ids(labels, Q, dev)
+        _, _, pos, out_len, gold_col = ops.lists_columns([ids], [lens], None, gold_dev)
+        if Gmax <= gold_col.shape[1] == int(ops._lib.lib().fz_tune_max_gold()):
+            return cls._metrics_of_gold_ranks(gold_col.clamp(min=0)[None].contiguous(), gold_col, ops.as_plane(pos), n_gold, dev)[0]
+        col = gold_col.cpu().numpy().astype(np.int64)[:, :Gmax]
+        return metrics_from_gold_ranks(np.where(col >= 0, col, np.iinfo(np.int64).max)[None], n_gold, out_len.cpu().numpy())[0]
 
     @staticmethod
     def _table(distr, dev) -> torch.Tensor:

@@ -368,6 +368,25 @@ int fz_lists_join(const int64_t* const* ids_h, const int32_t* const* lens_h, con
                   const int32_t* value_is_f64_h, const double* w_h, const int32_t* narrow_h, const int32_t* n_h,
                   const int32_t* ld_h, int S, int Q, int method, int64_t* out_ids, void* out_scores, int32_t* out_len,
                   int ld_out, void* workspace, size_t workspace_bytes, void* stream);
+/* (ABI 20, additive) The same join to per-system COLUMNS: the form the weight sweep (fz_gold_ranks_*, fz_tune_metrics_f64) takes, for
+ * lists over any ids (csrc/lists_tune.hip).  Inputs as for fz_lists_join; values_h[s] device [Q][ld_h[s]] fp32 (the system's
+ * normalised scores in list order).  Outputs, per query, all with ONE row stride ld_out >= sum of n_h:
+ *   out_ids [Q][ld_out] int64, out_len [Q]   the union's ids in first-insertion order and their number -- fz_lists_join's bytes;
+ *                                            out_ids holds -1 from out_len on;
+ *   T_h[s]  [Q][ld_out] fp32 (HOST array of S device pointers)   values_h[s][q][r] in the column of ids_h[s][q][r], r < lens;
+ *                                            +0.0 in every other element of the row (a system adds nothing for an id it does not list);
+ *   pos     [Q][ld_out] int32                c for c < out_len[q], -1 beyond: the first-insertion position, i.e. the tie-break;
+ *   gold_col[Q][G] int32                     the column of gold_ids[q][g] (device [Q][G] int64); -1 for a negative id (padding) or
+ *                                            an id in no list of the query.  G >= 0; G == 0: both may be NULL.
+ * The kernel defines every element of every output row itself (no pre-fill is needed) and two calls give the same bytes.
+ * values_h == NULL: an ids / pos / gold-only join -- T_h is not read (with S == 1 the column of an id is its list position).
+ * Capacity, duplicate flag (first int32 of the workspace, fz_lists_columns_workspace_bytes(S, Q) device bytes), argument checks
+ * and return codes as for fz_lists_join.  Q == 0 or all n_h == 0: FZ_OK, nothing launched, nothing written. */
+size_t fz_lists_columns_workspace_bytes(int S, int Q);
+int fz_lists_columns(const int64_t* const* ids_h, const int32_t* const* lens_h, const float* const* values_h, const int32_t* n_h,
+                     const int32_t* ld_h, int S, int Q, const int64_t* gold_ids, int G, int64_t* out_ids, float* const* T_h,
+                     int32_t* pos, int32_t* out_len, int32_t* gold_col, int ld_out, void* workspace, size_t workspace_bytes,
+                     void* stream);
 
 /* ---- A1: BM25 scoring on device, bm25.py:149-156 -------------------------------------- */
 /* scores[q][j] (fp64) = sum over query terms in query order of idf*tf*(k1+1)/(tf+k1*(1-b+b*dl/avgdl)).
