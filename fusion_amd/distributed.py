@@ -233,16 +233,98 @@ class ShardedLexicalIndex(_ShardedIndex):
         return RankedTopk.from_search(s.to(torch.float32), i, scores64=s)
 
 
+class ShardedCentroidIndex(_ShardedIndex):
+    """The candidate stage of one rank's ColBERT shard: an ops.CentroidIndex (per centroid the shard's documents that carry it, documents
+    0 .. N-1 = global ids id_base ..) + the chunked score -> top-k loop over it.  A query is its probe table (ops.centroid_probes); a
+    document's candidate score (ops.centroid_scores) does not depend on its shard, so the merged list is the same for any number of
+    shards.  Two routes with the same lists: a plane per chunk, its top-k and a merge (the default, see STREAMING), or the exact top-k of
+    the head's plane and the rest streamed through fz_centroid_scores_filter_f32.  Most documents score an exact +0.0 for most queries:
+    ties go to the ascending global id, as everywhere."""
+
+    CHUNK = 64 * 3584   # documents per feed (rounded down to whole slices of the kernels, 3,584 documents each; at least one)
+    PLANE_MARK = "shard_centroid"
+    # Measured (profiles/r13_colbert_search.json, 1,105,228 documents, Q = 1024): the two-pass route takes 24-42 ms where the streamed one takes
+    # 40-90 (alternated runs).  Documents reached through one probe share that probe's score exactly, so a list's cut falls inside a run of equal
+    # scores: 36-70 documents on average, up to 110, per 229,376 (measured in the same file), where the fold of unordered candidates puts only 64
+    # entries behind the cut in id order -- 2-6 windows per search overflow and are redone exactly.  The streamed route stays
+    # (local_topk(streaming=True), the same lists); the default is the faster one.
+    STREAMING = False
+    _grain = property(lambda self: ops.centroid_slice_docs())
+
+    def __init__(self, index, id_base: int, group=None):
+        self.index, self.id_base, self.group = index, int(id_base), group
+
+    def _source(self, pc, ps, Lq, nprobe):
+        return ops._centroid_source(self.index, pc, ps, Lq, nprobe, self.id_base)
+
+    def local_topk(self, pc: torch.Tensor, ps: torch.Tensor, Lq: int, nprobe: int, k: int, mark=None, streaming: bool | None = None):
+        """[Q, k] (score desc, id asc) over this shard for the probe tables pc / ps [Q, Lq * nprobe]; short lists padded with (-inf, -1).
+        streaming=True: exact head, streamed rest, an overflowed window redone exactly (where streaming applies); False: a plane per chunk, its
+        top-k, a merge; None: the class's STREAMING.  The lists are the same either way."""
+        streaming = self.STREAMING if streaming is None else bool(streaming)
+        Q = pc.shape[0]
+        if self.index.N == 0 or Q == 0:
+            self.last_overflow = 0
+            return (torch.full((Q, k), float("-inf"), dtype=torch.float32, device=pc.device),
+                    torch.full((Q, k), -1, dtype=torch.int64, device=pc.device))
+        return self._topk((pc, ps, Lq, nprobe), k, streaming, mark)
+
+    def search(self, pc: torch.Tensor, ps: torch.Tensor, Lq: int, nprobe: int, k: int = 1000, mark=None):
+        return self._search((pc, ps, Lq, nprobe), k, mark)
+
+
 class ShardedTokenIndex:
     """One rank's shard of a ColBERT corpus as its packed token matrix (Dtok_local [sumL, 128] float16, Doff_local [N + 1] int64;
     documents 0 .. N-1 = global ids id_base ..) + the exact rerank of candidate lists over it: the corpus-scale counterpart of
     ops.maxsim's [Q, N] plane, which the reference never builds either (its PLAID searcher scores candidates only, hybrid.py:108-137).
     fz_maxsim_pairs_f16 scores every query against its own candidate ids with the bits of the all-pairs kernel; a slot this shard does
     not own gets -inf, so the shards' [Q, k] planes combine by ONE all_reduce(MAX), and one stable descending row sort turns the plane
-    into lists (ties keep candidate-list order, whatever the number of shards).  No host synchronisation on the single-rank path."""
+    into lists (ties keep candidate-list order, whatever the number of shards).  No host synchronisation on the single-rank path.
+    With build_centroids the shard also generates its own candidates (ShardedCentroidIndex) and `search` is a first-stage search:
+    candidates from token centroids, every returned score exact.  The token matrix stays uncompressed."""
+
+    centroids = None        # [K, dim] float16, the same table on every rank (build_centroids)
+    candidates = None       # the ShardedCentroidIndex of this shard
 
     def __init__(self, Dtok_local: torch.Tensor, Doff_local: torch.Tensor, id_base: int, group=None, max_doc_len: int = 512):
         self.Dtok, self.Doff, self.id_base, self.group, self.max_doc_len = Dtok_local, Doff_local, int(id_base), group, int(max_doc_len)
+
+    def build_centroids(self, C: torch.Tensor, codes: torch.Tensor | None = None):
+        """Keep the centroid table C [K, dim] (ops.kmeans_centroids; trained on one rank and broadcast, the same on every rank) and build
+        this shard's candidate index: every token row is assigned its nearest centroid (ops.centroid_assign) unless `codes` [sumL] are given."""
+        if codes is None:
+            codes = ops.centroid_assign(self.Dtok, C)
+        self.centroids = C
+        self.candidates = ShardedCentroidIndex(ops.centroid_index(codes, self.Doff, C.shape[0]), self.id_base, group=self.group)
+        return self
+
+    @staticmethod
+    def search_defaults(k: int) -> tuple[int, int]:
+        """(nprobe, ncand) of `search` for a list of k.  nprobe 1 / 2 / 4 for k <= 10 / <= 100 / larger and a candidate list of 4k (at least
+        256) follow colbert-ai's published search settings in spirit; they are UNMEASURED here in the sense that no measurement chose
+        them (tools/bench_colbert_search.py records their recall on a synthetic corpus, profiles/r13_colbert_search.json: no ground to
+        retune them).  3,584 is the longest list the streaming top-k ranks; a longer one takes the two-pass path in any case."""
+        return (1 if k <= 10 else 2 if k <= 100 else 4), max(k, min(max(4 * k, 256), 3584))
+
+    def search(self, Qtok: torch.Tensor, k: int = 1000, nprobe: int | None = None, ncand: int | None = None, mark=None):
+        """First-stage ColBERT search over the sharded corpus -> planes.RankedTopk of the k best of the ncand candidates: (1) probes: every
+        query token's nprobe best centroids; (2) the global top-ncand documents by candidate score (ShardedCentroidIndex.search: one
+        all-gather); (3) `rerank` of those ids: exact MaxSim, one all_reduce(MAX); (4) the cut to k.  What is approximate is the candidate
+        set; every returned score is the exact MaxSim of its pair, the bits of ops.maxsim.  Query tokens must be finite."""
+        k = int(k)
+        d_nprobe, d_ncand = self.search_defaults(k)
+        nprobe = d_nprobe if nprobe is None else int(nprobe)
+        ncand = d_ncand if ncand is None else int(ncand)
+        if self.candidates is None:
+            raise ValueError("ShardedTokenIndex.search: no centroid index (call build_centroids first)")
+        if k < 1 or k > ncand or nprobe < 1:
+            raise ValueError(f"ShardedTokenIndex.search: k = {k} must be in 1 .. ncand = {ncand}, nprobe = {nprobe} at least 1")
+        mark = mark or (lambda name: None)
+        Qtok = Qtok.contiguous()
+        pc, ps = ops.centroid_probes(Qtok, self.centroids, nprobe); mark("colbert_probes")
+        _, cand_ids = self.candidates.search(pc, ps, Qtok.shape[1], nprobe, ncand, mark=mark)
+        out = self.rerank(Qtok, cand_ids, k=k); mark("colbert_rerank")
+        return out
 
     @classmethod
     def from_encoder(cls, model, documents: list[str], id_base: int = 0, group=None, batch_size: int = 64, device=None):

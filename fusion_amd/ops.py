@@ -1680,6 +1680,217 @@ def sparse_cos_scores(Qe: torch.Tensor, index: SparseIndex, max_query_density: f
     return sparse_dot(index, *sparse_rows(Qn, index.V))
 
 
+# ---------------------------------------------------------------------------------------
+# K2 at corpus scale, first stage: candidates from token centroids (csrc/centroid.hip)
+# ---------------------------------------------------------------------------------------
+CENTROID_BLOCK_BYTES = 256 << 20            # float32 score blocks of centroid_assign / centroid_probes / kmeans_centroids stay below this
+CENTROID_SLICE_TABLE_MAX_BYTES = 1 << 30    # centroid_index builds the [K, NS + 1] slice table only below this size (as retrievers.bm25 does)
+
+
+class CentroidIndex:
+    """Per centroid the DISTINCT local documents that carry it, ascending: coff [K + 1] int64, cdoc int32 -- the shape of SparseIndex
+    without weights.  slice_off [K, NS + 1] int64 (fz_centroid_slice_offsets) or None: without it the kernels find their list segments by
+    binary search, with the same result."""
+
+    def __init__(self, coff, cdoc, N: int, K: int, slice_off=None):
+        self.coff, self.cdoc, self.N, self.K, self.slice_off = coff, cdoc, int(N), int(K), slice_off
+
+
+def centroid_slice_docs() -> int:
+    """Documents per workgroup slice of the centroid kernels: document ranges start on a multiple of it."""
+    return int(_lib.lib().fz_centroid_slice_docs())
+
+
+def _f32_rows(X: torch.Tensor, what: str) -> torch.Tensor:
+    _need(isinstance(X, torch.Tensor) and X.dim() == 2 and X.dtype in (torch.float16, torch.float32), f"{what}: a [rows, dim] float16 or float32 tensor expected")
+    return X.float().contiguous()
+
+
+def _nearest(X32: torch.Tensor, C32: torch.Tensor) -> torch.Tensor:
+    """Row-wise argmax of X32 @ C32.T, ties to the lowest id, in blocks of CENTROID_BLOCK_BYTES of scores: dot_scores + topk_rows(1)."""
+    n, K = X32.shape[0], C32.shape[0]
+    out = torch.empty(n, dtype=torch.int32, device=X32.device)
+    rows = max(1, CENTROID_BLOCK_BYTES // (4 * round_up(max(K, 1), _PAD)))
+    for r0 in range(0, n, rows):
+        _, ids = topk_rows(dot_scores(X32[r0: r0 + rows], C32), 1)
+        out[r0: r0 + rows] = ids[:, 0]
+    return out
+
+
+def centroid_assign(Dtok: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
+    """codes [sumL] int32: for every token row of Dtok [sumL, dim] the centroid of C [K, dim] with the largest dot product, ties to the
+    lowest id.  Chunked over token rows by a byte budget; the float32 MFMA GEMM (dot_scores) on the float32 copies, then topk_rows(.., 1):
+    bit-reproducible."""
+    _dev(Dtok, None, "centroid_assign(Dtok)"); _dev(C, None, "centroid_assign(C)")
+    _need(Dtok.dim() == 2 and C.dim() == 2 and C.shape[0] >= 1 and Dtok.shape[1] == C.shape[1], "centroid_assign: Dtok [sumL, dim] and C [K >= 1, dim] expected")
+    _need(Dtok.dtype in (torch.float16, torch.float32), "centroid_assign(Dtok): float16 or float32 expected")
+    C32 = _f32_rows(C, "centroid_assign(C)")
+    n = Dtok.shape[0]
+    out = torch.empty(n, dtype=torch.int32, device=Dtok.device)
+    rows = max(1, CENTROID_BLOCK_BYTES // (4 * round_up(C.shape[0], _PAD)))
+    for r0 in range(0, n, rows):     # the float32 copy of one block of token rows at a time
+        _, ids = topk_rows(dot_scores(Dtok[r0: r0 + rows].float().contiguous(), C32), 1)
+        out[r0: r0 + rows] = ids[:, 0]
+    return out
+
+
+def kmeans_centroids(tokens: torch.Tensor, K: int, iters: int = 4, seed: int = 0, sample: int | None = None) -> torch.Tensor:
+    """K unit-norm centroids [K, dim] float16 of the token rows (tokens [n, dim] float16 / float32 on the device, n >= K): seeded Lloyd
+    iterations for the dot product (spherical k-means, what colbert-ai trains).  The start is K rows drawn by a generator seeded with
+    `seed`, `sample` (optional) trains on that many drawn rows; every step is dot_scores / topk_rows / a one-hot dot_scores -- no float
+    atomics -- so the result is deterministic for a given seed on a given device.  A cluster that loses all its rows keeps its centroid.
+    Multi-rank callers train on ONE rank and broadcast the centroids (torch.distributed.broadcast): every shard must assign against the
+    same table; no collective is built in here."""
+    _dev(tokens, None, "kmeans_centroids(tokens)")
+    K, n = int(K), tokens.shape[0]
+    _need(tokens.dim() == 2 and 1 <= K <= n, f"kmeans_centroids: tokens [n, dim] with n >= K >= 1 expected, got {tuple(tokens.shape)} and K = {K}")
+    gen = torch.Generator(device=tokens.device)
+    gen.manual_seed(int(seed))
+    perm = torch.randperm(n, generator=gen, device=tokens.device)
+    m = n if sample is None else max(K, min(n, int(sample)))
+    X = _f32_rows(tokens[perm[:m]], "kmeans_centroids(tokens)")
+    C = torch.nn.functional.normalize(X[:K].clone(), dim=1)
+    dim = X.shape[1]
+    blk = max(4, CENTROID_BLOCK_BYTES // (4 * K) // 4 * 4)     # rows per one-hot block [K, blk]
+    for _ in range(int(iters)):
+        codes = _nearest(X, C).long()
+        sums = torch.zeros((K, dim), dtype=torch.float32, device=X.device)
+        for r0 in range(0, m, blk):
+            r1 = min(m, r0 + blk)
+            w = round_up(r1 - r0, 4)
+            onehot = torch.zeros((K, w), dtype=torch.float32, device=X.device)
+            onehot[codes[r0:r1], torch.arange(r1 - r0, device=X.device)] = 1.0
+            Xt = torch.zeros((dim, w), dtype=torch.float32, device=X.device)
+            Xt[:, : r1 - r0] = X[r0:r1].t()
+            sums = sums + dot_scores(onehot, Xt)                # [K, dim]: the block's per-cluster sums, one fixed-order GEMM
+        keep = (sums == 0).all(1, keepdim=True)
+        C = torch.where(keep, C, torch.nn.functional.normalize(sums, dim=1))
+    return C.to(torch.float16)
+
+
+def centroid_slice_table_bytes(K: int, N: int) -> int:
+    return int(K) * (max(1, -(-int(N) // centroid_slice_docs())) + 1) * 8
+
+
+def centroid_slice_offsets(coff: torch.Tensor, cdoc: torch.Tensor, K: int, N: int) -> torch.Tensor:
+    _need(_dev(coff, torch.int64, "centroid_slice_offsets(coff)").is_contiguous() and coff.numel() == K + 1, f"centroid_slice_offsets: coff must hold {K + 1} offsets")
+    _need(_dev(cdoc, torch.int32, "centroid_slice_offsets(cdoc)").is_contiguous(), "centroid_slice_offsets(cdoc) must be contiguous")
+    NS = max(1, -(-int(N) // centroid_slice_docs()))
+    out = torch.empty((K, NS + 1), dtype=torch.int64, device=coff.device)
+    check(_lib.lib().fz_centroid_slice_offsets(_ptr(coff), _ptr(cdoc), K, int(N), _ptr(out), _stream(coff)), "fz_centroid_slice_offsets")
+    return out
+
+
+def centroid_index(codes: torch.Tensor, Doff: torch.Tensor, K: int, slice_table_max_bytes: int | None = None) -> CentroidIndex:
+    """The inverted index of the candidate stage: codes [sumL] (the centroid of every packed token row, centroid_assign), Doff [N + 1]
+    int64 -> CentroidIndex.  A document is listed once per centroid however many of its tokens carry it; an empty document is in no list.
+    torch ops only, on CPU tensors too (slice_off stays None there).  On the device the slice table is built when it is smaller than
+    slice_table_max_bytes (default CENTROID_SLICE_TABLE_MAX_BYTES); above that the kernels search."""
+    K, N = int(K), Doff.numel() - 1
+    _need(codes.dim() == 1 and Doff.dim() == 1 and N >= 0 and K >= 0, "centroid_index: codes [sumL] and Doff [N + 1] expected")
+    _need(N < 2 ** 31, "centroid_index: local document ids are int32")
+    dev = codes.device
+    lens = (Doff[1:] - Doff[:-1]).to(dev)
+    _need(int(lens.sum()) == codes.numel(), "centroid_index: Doff must cover the token rows exactly")
+    if codes.numel():
+        _need(0 <= int(codes.min()) and int(codes.max()) < K, f"centroid_index: codes must lie in [0, {K})")
+    doc = torch.repeat_interleave(torch.arange(N, dtype=torch.int64, device=dev), lens)
+    pair = torch.unique(codes.long() * max(N, 1) + doc)          # sorted: by centroid, then document; duplicates gone
+    c = torch.div(pair, max(N, 1), rounding_mode="floor")
+    coff = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    coff[1:] = torch.cumsum(torch.bincount(c, minlength=K), 0)
+    cdoc = (pair - c * max(N, 1)).to(torch.int32).contiguous()
+    slice_off = None
+    cap = CENTROID_SLICE_TABLE_MAX_BYTES if slice_table_max_bytes is None else int(slice_table_max_bytes)
+    if coff.is_cuda and K > 0 and centroid_slice_table_bytes(K, N) < cap:
+        slice_off = centroid_slice_offsets(coff, cdoc, K, N)
+    return CentroidIndex(coff, cdoc, N, K, slice_off)
+
+
+def centroid_probes(Qtok: torch.Tensor, C: torch.Tensor, nprobe: int):
+    """(pc [Q, Lq * nprobe] int32, ps [Q, Lq * nprobe] float32): per query token its nprobe best centroids by (score desc, id asc) and
+    their scores <q_i, C_c>, token-major.  dot_scores on the float32 copies + topk_rows over query blocks sized by a byte budget (the whole
+    [Q * Lq, K] float32 plane is 17 GB at Q = 1024, K = 65,536).  nprobe > K pads with (pc = -1, ps = -inf): the kernels skip a negative
+    id.  Query tokens must be finite: a non-finite probe score is outside the candidate score's contract."""
+    _dev(Qtok, torch.float16, "centroid_probes(Qtok)"); _dev(C, None, "centroid_probes(C)")
+    _need(Qtok.dim() == 3 and C.dim() == 2 and C.shape[0] >= 1 and Qtok.shape[2] == C.shape[1] and int(nprobe) >= 1,
+          "centroid_probes: Qtok [Q, Lq, dim], C [K >= 1, dim] and nprobe >= 1 expected")
+    Q, Lq, dim = Qtok.shape
+    K, nprobe = C.shape[0], int(nprobe)
+    C32 = _f32_rows(C, "centroid_probes(C)")
+    rowsT = Q * Lq
+    flat = Qtok.reshape(rowsT, dim)
+    pc = torch.empty((rowsT, nprobe), dtype=torch.int32, device=Qtok.device)
+    ps = torch.empty((rowsT, nprobe), dtype=torch.float32, device=Qtok.device)
+    rows = max(1, CENTROID_BLOCK_BYTES // (4 * round_up(K, _PAD)))
+    for r0 in range(0, rowsT, rows):
+        s, i = topk_rows(dot_scores(flat[r0: r0 + rows].float().contiguous(), C32), nprobe)
+        ps[r0: r0 + rows] = s
+        pc[r0: r0 + rows] = i
+    return pc.view(Q, Lq * nprobe), ps.view(Q, Lq * nprobe)
+
+
+def _centroid_args(what: str, index: CentroidIndex, pc, ps, Lq: int, nprobe: int, doc_lo: int, doc_hi):
+    _need(_dev(pc, torch.int32, f"{what}(pc)").is_contiguous() and _dev(ps, torch.float32, f"{what}(ps)").is_contiguous(), f"{what}: pc and ps must be contiguous")
+    Lq, nprobe = int(Lq), int(nprobe)
+    _need(Lq >= 1 and nprobe >= 1 and pc.dim() == 2 and pc.shape[1] == Lq * nprobe and tuple(ps.shape) == tuple(pc.shape),
+          f"{what}: pc and ps must be [Q, Lq * nprobe = {Lq * nprobe}]")
+    _dev(index.coff, torch.int64, f"{what}(index.coff)"); _dev(index.cdoc, torch.int32, f"{what}(index.cdoc)")
+    _need(index.coff.is_contiguous() and index.cdoc.is_contiguous() and index.coff.numel() == index.K + 1, f"{what}: index.coff must hold K + 1 offsets")
+    G = centroid_slice_docs()
+    if index.slice_off is not None:
+        NS = max(1, -(-index.N // G))
+        _need(_dev(index.slice_off, torch.int64, f"{what}(index.slice_off)").is_contiguous() and tuple(index.slice_off.shape) == (index.K, NS + 1),
+              f"{what}(index.slice_off): expected a contiguous [{index.K}, {NS + 1}] table (ops.centroid_slice_offsets)")
+    doc_hi = index.N if doc_hi is None else int(doc_hi)
+    doc_lo = int(doc_lo)
+    _need(0 <= doc_lo <= doc_hi <= index.N and doc_lo % G == 0 and (doc_hi % G == 0 or doc_hi == index.N),
+          f"{what}: [doc_lo, doc_hi) = [{doc_lo}, {doc_hi}) must start on a multiple of {G} and end on one or at N = {index.N}")
+    return pc.shape[0], Lq, nprobe, doc_lo, doc_hi
+
+
+def centroid_scores(index: CentroidIndex, pc: torch.Tensor, ps: torch.Tensor, Lq: int, nprobe: int, doc_lo: int = 0, doc_hi: int | None = None,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+    """The candidate scores of documents [doc_lo, doc_hi) (default: all N) for the probe tables of centroid_probes: [Q, doc_hi - doc_lo]
+    float32, scores[q][j] = the float32 chain ((+0.0 + m_i1) + m_i2) + ... over the query tokens i, ascending, that hit document
+    doc_lo + j, m_i = the largest probe score of token i among the centroids the document carries; +0.0 without a hit.  Defined bit for
+    bit: a range's columns are the full plane's.  doc_lo a multiple of centroid_slice_docs(), doc_hi one too or N.  Probe scores must be
+    finite (non-finite query tokens are outside the contract)."""
+    Q, Lq, nprobe, doc_lo, doc_hi = _centroid_args("centroid_scores", index, pc, ps, Lq, nprobe, doc_lo, doc_hi)
+    if out is None:
+        out = alloc_plane(Q, doc_hi - doc_lo, torch.float32, pc.device)
+    else:
+        _dev(out, torch.float32, "centroid_scores(out)")
+        _need(tuple(out.shape) == (Q, doc_hi - doc_lo), f"centroid_scores(out): expected shape {(Q, doc_hi - doc_lo)}, got {tuple(out.shape)}")
+    check(_lib.lib().fz_centroid_scores_range_f32(_ptr(index.coff), _ptr(index.cdoc), _ptr(index.slice_off), _ptr(pc), _ptr(ps), Q, Lq, nprobe, index.N,
+                                                  index.K, doc_lo, doc_hi, _ptr(out), _ld(out), _stream(pc)), "fz_centroid_scores_range_f32")
+    return out
+
+
+def centroid_filter(index: CentroidIndex, pc, ps, Lq: int, nprobe: int, doc_lo: int, doc_hi: int, id_base: int, tau, cand_s, cand_i, cand_len,
+                    overflow):
+    """fz_centroid_scores_filter_f32 on the buffers of a TopkStream (or a test's own): document d of [doc_lo, doc_hi) enters query q's
+    candidates iff !(score <= tau[q]), as (score, id_base + d); cand_s / cand_i [Q, cap], cand_len [Q] int32, overflow [1] int32."""
+    Q, Lq, nprobe, doc_lo, doc_hi = _centroid_args("centroid_filter", index, pc, ps, Lq, nprobe, doc_lo, doc_hi)
+    _dev(tau, torch.float32, "centroid_filter(tau)"); _dev(cand_s, torch.float32, "centroid_filter(cand_s)")
+    _dev(cand_i, torch.int64, "centroid_filter(cand_i)"); _dev(cand_len, torch.int32, "centroid_filter(cand_len)")
+    _dev(overflow, torch.int32, "centroid_filter(overflow)")
+    cap = cand_s.shape[1] if cand_s.dim() == 2 else 0
+    _need(cap >= 1 and cand_s.is_contiguous() and cand_i.is_contiguous() and tuple(cand_s.shape) == (Q, cap) and tuple(cand_i.shape) == (Q, cap)
+          and tau.numel() >= Q and cand_len.numel() >= Q and overflow.numel() >= 1, "centroid_filter: tau [Q], cand_s / cand_i [Q, cap >= 1] contiguous, cand_len [Q], overflow [1] expected")
+    check(_lib.lib().fz_centroid_scores_filter_f32(_ptr(index.coff), _ptr(index.cdoc), _ptr(index.slice_off), _ptr(pc), _ptr(ps), Q, Lq, nprobe, index.N,
+                                                   index.K, doc_lo, doc_hi, int(id_base), _ptr(tau), _ptr(cand_s), _ptr(cand_i), _ptr(cand_len), cap,
+                                                   _ptr(overflow), _stream(pc)), "fz_centroid_scores_filter_f32")
+
+
+def _centroid_source(index: CentroidIndex, pc, ps, Lq: int, nprobe: int, id_base: int) -> _Source:
+    """The centroid walk whose epilogue is the filter, document d of the index = id id_base + d (ShardedCentroidIndex)."""
+    def filter(st, lo, hi):
+        centroid_filter(index, pc, ps, Lq, nprobe, lo, hi, id_base, st.tau, st.cand_s, st.cand_i, st.cand_len, st.overflow)
+    return _Source(index.N, filter, lambda lo, hi: (centroid_scores(index, pc, ps, Lq, nprobe, doc_lo=lo, doc_hi=hi), id_base + lo),
+                   grain=centroid_slice_docs(), mark="shard_centroid_filter")
+
+
 def f64_to_f32(src: torch.Tensor) -> torch.Tensor:
     """Plane-preserving fp64 -> fp32 (what torch.tensor(..., dtype=float32) does to BM25's Python floats, hybrid.py:255)."""
     _dev(src, torch.float64, "f64_to_f32")

@@ -182,6 +182,16 @@ class Ranker:
         return index.rerank(Qtok, candidates, k=return_topk)
 
     @staticmethod
+    def multi_vector_search_topk(queries: list[str], index, *, encoder, return_topk: int = 1000, nprobe: int = None, ncand: int = None):
+        """multi_vector_search as a first-stage search at corpus scale (hybrid.py:108-137: colbert-ai generates candidates from token
+        centroids, then scores them exactly): `index` is a fusion_amd.distributed.ShardedTokenIndex with a centroid index
+        (build_centroids).  The queries are encoded with the ColBERT `encoder` and `index.search` finds each one's candidates and scores
+        them exactly -> planes.RankedTopk, what Aggregator.fuse_topk takes next to the dense, sparse and BM25 lists.  The candidate set is
+        approximate (nprobe, ncand: ShardedTokenIndex.search_defaults), every returned score is the exact MaxSim of its pair."""
+        Qtok = encoder.encode_queries(queries, batch_size=64)
+        return index.search(Qtok, k=return_topk, nprobe=nprobe, ncand=ncand)
+
+    @staticmethod
     def cross_encoder_search(queries: list[str], candidates: list, model_name_or_path: str, return_topk: int = None, *, model=None,
                              corpus: dict[int, str] = None):
         """monoBERT rerank (hybrid.py:139-163).  The reference's version is dead code (`docs` undefined at :159, and main passes

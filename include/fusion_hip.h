@@ -510,6 +510,33 @@ int fz_tfidf_filter_f64(const int64_t* toff, const int32_t* pdoc, const int32_t*
                         const double* tau, double* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow,
                         void* stream);
 
+/* ---- K2 at corpus scale, first stage: candidate scores from token centroids (csrc/centroid.hip; ABI 20, additive) ------------------------
+ * Ranker.multi_vector_search (hybrid.py:108-137) is a first-stage search: colbert-ai generates candidates from token centroids and scores
+ * them exactly (fz_maxsim_pairs_f16 is the exact part).  Every document token carries the id of its nearest of K centroids; the index
+ * lists, per centroid c, the DISTINCT documents that hold it: cdoc [coff[c], coff[c+1]) (int32, ascending), coff [K + 1] int64.  A query is
+ * its probe table, token-major: pc / ps [Q][Lq * nprobe], token i's nprobe best centroids (score desc, id asc) and their scores;
+ * pc < 0 pads.  With m_i = the largest ps over token i's probes whose list holds d,
+ *     scores[q][d] = ((+0.0 + m_i1) + m_i2) + ...     over the tokens i that hit d, ascending          (float32)
+ * A token without a hit adds nothing, a document without any scores +0.0, a negative probe score counts as it is.  The max does not
+ * depend on order and the adds have a fixed one: the score is defined bit for bit, the same for a range as for the whole index.  Probe
+ * scores must be finite (a non-finite query token is outside the contract).  Lq >= 1, nprobe >= 1, both of any size.
+ * A workgroup scores one (query, slice) of fz_centroid_slice_docs() documents: doc_lo must be a multiple of it, doc_hi a multiple or N.
+ * slice_off (nullable): fz_centroid_slice_offsets' [K][NS + 1] table for the WHOLE index, NS = max(1, ceil(N / slice)) -- where every
+ * centroid's list crosses the slices; without it a workgroup finds its segments by binary search, with the same result.
+ * Checks, in this order: negative sizes, Lq < 1, nprobe < 1, a bad range or lds < doc_hi - doc_lo -> FZ_ERR_ARG; Q == 0 or an empty
+ * range -> FZ_OK, nothing launched; then null pointers (coff, pc, ps and the outputs) -> FZ_ERR_ARG. */
+int fz_centroid_slice_docs(void);
+int fz_centroid_slice_offsets(const int64_t* coff, const int32_t* cdoc, int K, int N, int64_t* out, void* stream);
+int fz_centroid_scores_range_f32(const int64_t* coff, const int32_t* cdoc, const int64_t* slice_off, const int32_t* pc, const float* ps, int Q,
+                                 int Lq, int nprobe, int N, int K, int doc_lo, int doc_hi, float* scores, int lds, void* stream);
+/* The same walk with the streaming top-k's threshold filter in place of the plane -- fz_sparse_dot_filter_f32's rule and lists: document d
+ * enters query q's candidates iff !(score <= tau[q]), appended as (score, id_base + d); cand_scores / cand_ids [Q][cap], cand_len [Q]
+ * int32 (keeps counting past cap: the excess is dropped, nothing is written at or past slot cap and *overflow is set to 1), in arrival
+ * order, i.e. for fz_topk_fold_f32(unordered = 1).  cap <= 0 -> FZ_ERR_ARG, checked even when there is nothing to score. */
+int fz_centroid_scores_filter_f32(const int64_t* coff, const int32_t* cdoc, const int64_t* slice_off, const int32_t* pc, const float* ps, int Q,
+                                  int Lq, int nprobe, int N, int K, int doc_lo, int doc_hi, int64_t id_base, const float* tau,
+                                  float* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow, void* stream);
+
 /* ---- encoder side: the per-sequence parts of SentenceTransformer.encode (hybrid.py:97-102) on PACKED token rows -- */
 /* Self-attention of a BERT/CamemBERT layer for ragged sequences without padding: for every sequence and head,
  * out = softmax(q k^T * scale) v in fp32 (MFMA products, online softmax over 16-key tiles), scale > 0.  qkv [T][ld] = fused
