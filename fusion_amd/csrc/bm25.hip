@@ -5,7 +5,8 @@
 // scores and therefore the ranks are bit-identical to the Python loop.  Documents that lack a term add
 // +-0.0 in the reference, i.e. nothing.  The postings of one term touch distinct documents (parallel, no
 // atomics); terms are applied one after the other (barrier) to keep the reference's sum order.
-#include "common.h"
+// Modes, grain, terms per batch and workgroup shapes are bm25_walk.h's, shared with the range / filter form of the walk (bm25_stream.hip).
+#include "bm25_walk.h"
 
 namespace fz {
 
@@ -30,32 +31,8 @@ struct Bm25Args {
 // per query (the frequent terms of a Zipf vocabulary list most of the corpus); the slice's norms now come in once per workgroup,
 // coalesced.  The slice is written out once, coalesced.  Postings of a term are sorted by document, so the slice's sub-range is found by
 // two block-uniform binary searches (or read from the per-index table).
-constexpr int BM25_GRAIN = 3584;    // granularity of the per-index posting-offset table (fz_bm25_slice_offsets): a workgroup's slice is 1 or 2 of these
-constexpr int BM25_PV_GRAINS = 1, BM25_PV_THREADS = 512;   // the table-driven walk's workgroup (see bm25_kernel)
-
-__device__ __forceinline__ int64_t lower_bound_doc(const int32_t* __restrict__ pdoc, int64_t lo, int64_t hi, int doc) {
-    while (lo < hi) {   // first e in [lo, hi) with pdoc[e] >= doc  (uniform: scalar loads)
-        const int64_t mid = (lo + hi) >> 1;
-        if (pdoc[mid] < doc) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-constexpr int BM25_TERMS = 256;     // query terms whose posting ranges are resolved per batch
-
-// MODE: 0 = BM25's expression per posting; 1 = TFIDF: score += tf * idf (bm25.py:114); 2 = the posting's term comes from a table (pval):
-// every posting of the index has ONE value for a given (k1, b) -- idf, tf and the document's length norm are all the index's -- so the
-// float64 division (a dozen instructions at half rate: most of this kernel's time) is done once per index, like the idf table, not once
-// per (query, posting); the walk adds the same bits in the same order.
-enum { BM25_EXPR = 0, BM25_TFIDF = 1, BM25_PVAL = 2 };
-
-// Documents of one workgroup's slice, for the kernel's walk and the launcher's grid and LDS alike: table grains per slice x BM25_GRAIN.
-template <int MODE> constexpr int slice_grains() { return MODE == BM25_PVAL ? BM25_PV_GRAINS : 2; }
-template <int MODE> constexpr int slice_docs() { return BM25_GRAIN * slice_grains<MODE>(); }
 // LDS per workgroup: the slice's fp64 accumulators, plus its fp64 length norms for the per-posting expression (TFIDF reserves them too)
 template <int MODE> constexpr size_t slice_lds_bytes() { return (MODE == BM25_PVAL ? 1 : 2) * (size_t)slice_docs<MODE>() * sizeof(double); }
-static_assert(slice_docs<BM25_EXPR>() == 7168 && slice_docs<BM25_TFIDF>() == 7168 && slice_docs<BM25_PVAL>() == 3584,
-              "the measured slice sizes (see bm25_kernel)");
 static_assert(slice_lds_bytes<BM25_EXPR>() == 112 * 1024 && slice_lds_bytes<BM25_PVAL>() == 28 * 1024, "7168 accumulators + 7168 norms = 112 KiB of the CU's 160 KiB LDS");
 template <int MODE>
 __global__ __launch_bounds__(1024) void bm25_kernel(Bm25Args a) {
@@ -147,13 +124,6 @@ __global__ __launch_bounds__(1024) void bm25_kernel(Bm25Args a) {
     }
 }
 
-__global__ void bm25_slice_offsets_kernel(const int64_t* __restrict__ toff, const int32_t* __restrict__ pdoc, int V, int NS, int64_t* __restrict__ out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)V * (NS + 1)) return;
-    const int t = (int)(i / (NS + 1)), s_ = (int)(i % (NS + 1));
-    out[i] = s_ == NS ? toff[t + 1] : lower_bound_doc(pdoc, toff[t], toff[t + 1], s_ * BM25_GRAIN);
-}
-
 __global__ void bm25_doc_norms_kernel(const int32_t* __restrict__ doc_len, int N, double avgdl, double k1, double b, double* __restrict__ out) {
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < N; j += gridDim.x * blockDim.x)
         out[j] = k1 * (1.0 - b + b * (double)doc_len[j] / avgdl);   // the sub-expression of bm25.py:154, once per document
@@ -177,14 +147,7 @@ extern "C" int fz_bm25_doc_norms_f64(const int32_t* doc_len, int N, double avgdl
 extern "C" int fz_bm25_slice_docs(void) { return BM25_GRAIN; }
 
 extern "C" int fz_bm25_slice_offsets(const int64_t* toff, const int32_t* pdoc, int V, int N, int64_t* out, void* stream) {
-    if (V < 0 || N < 0) return FZ_ERR_ARG;
-    if (V == 0) return FZ_OK;
-    if (!toff || !out) return FZ_ERR_ARG;
-    const int NS = N > 0 ? (N + BM25_GRAIN - 1) / BM25_GRAIN : 1;
-    const long total = (long)V * (NS + 1);
-    bm25_slice_offsets_kernel<<<(unsigned)((total + 255) / 256), 256, 0, as_stream(stream)>>>(toff, pdoc, V, NS, out);
-    FZ_LAUNCH_CHECK();
-    return FZ_OK;
+    return slice_offsets_launch(toff, pdoc, V, N, BM25_GRAIN, out, stream);
 }
 
 extern "C" int fz_bm25_scores_f64(const int64_t* toff, const int32_t* pdoc, const int32_t* ptf, const double* idf,
@@ -258,17 +221,17 @@ static int bm25_launch(const Bm25Args& a, int Q, void* stream) {
         constexpr int S = slice_docs<BM25_PVAL>();
         constexpr size_t lds = slice_lds_bytes<BM25_PVAL>();
         if (int rc = raise_lds_limit((const void*)bm25_kernel<BM25_PVAL>, lds, lds_set[2])) return rc;
-        bm25_kernel<BM25_PVAL><<<dim3((unsigned)((N + S - 1) / S), (unsigned)Q), BM25_PV_THREADS, lds, as_stream(stream)>>>(a);
+        bm25_kernel<BM25_PVAL><<<dim3((unsigned)((N + S - 1) / S), (unsigned)Q), slice_threads<BM25_PVAL>(), lds, as_stream(stream)>>>(a);
     } else if (a.tfidf) {
         constexpr int S = slice_docs<BM25_TFIDF>();
         constexpr size_t lds = slice_lds_bytes<BM25_TFIDF>();
         if (int rc = raise_lds_limit((const void*)bm25_kernel<BM25_TFIDF>, lds, lds_set[1])) return rc;
-        bm25_kernel<BM25_TFIDF><<<dim3((unsigned)((N + S - 1) / S), (unsigned)Q), 1024, lds, as_stream(stream)>>>(a);
+        bm25_kernel<BM25_TFIDF><<<dim3((unsigned)((N + S - 1) / S), (unsigned)Q), slice_threads<BM25_TFIDF>(), lds, as_stream(stream)>>>(a);
     } else {
         constexpr int S = slice_docs<BM25_EXPR>();
         constexpr size_t lds = slice_lds_bytes<BM25_EXPR>();
         if (int rc = raise_lds_limit((const void*)bm25_kernel<BM25_EXPR>, lds, lds_set[0])) return rc;
-        bm25_kernel<BM25_EXPR><<<dim3((unsigned)((N + S - 1) / S), (unsigned)Q), 1024, lds, as_stream(stream)>>>(a);
+        bm25_kernel<BM25_EXPR><<<dim3((unsigned)((N + S - 1) / S), (unsigned)Q), slice_threads<BM25_EXPR>(), lds, as_stream(stream)>>>(a);
     }
     FZ_LAUNCH_CHECK();
     return FZ_OK;

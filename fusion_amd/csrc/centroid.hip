@@ -18,8 +18,8 @@
 //            does acc += decode(key) -- no float atomics, and the keys are back to "no hit" for the next token;
 //   barrier
 // Two barriers per token rather than one per list: inside a slice the lists are short (about 4 entries at 70 tokens per document and
-// 65,536 centroids).
-#include "common.h"
+// 65,536 centroids).  The slice-offset table, the document range and the plane and filter epilogues are slices.h's.
+#include "slices.h"
 
 namespace fz {
 
@@ -35,12 +35,9 @@ struct CentroidArgs {
     const int64_t* slice_off;                                      // nullable [K][NS + 1]: first entry of centroid c with document >= s * CT_SLICE
     const int32_t* pc; const float* ps;                            // probes [Q][Lq * nprobe], token-major; pc < 0: padding
     int Lq, nprobe, K;
-    int N, NS;
-    int doc_lo, doc_hi;                                            // the documents scored: [doc_lo, doc_hi), doc_lo a whole slice
+    DocRange r;                                                    // the documents scored (slice_off's row stride is r.NS + 1)
     float* scores; int lds;                                        // plane form: [Q][lds], column j = document doc_lo + j
-    // filter form (fz_centroid_scores_filter_f32): no plane; what beats tau[q] goes to query q's candidate list
-    const float* tau; float* cand_s; int64_t* cand_i; int32_t* cand_len; int32_t* overflow; int cap;
-    int64_t id_base;                                               // id of index document 0
+    FilterSink<float> f;                                           // filter form (fz_centroid_scores_filter_f32): no plane
 };
 
 // float -> unsigned key, larger float <=> larger key; no finite float maps to 0, the "no hit" mark
@@ -50,14 +47,6 @@ __device__ __forceinline__ uint32_t ct_key(float f) {
 }
 __device__ __forceinline__ float ct_key_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
-__device__ __forceinline__ int64_t ct_lower_bound(const int32_t* __restrict__ cdoc, int64_t lo, int64_t hi, int doc) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (cdoc[mid] < doc) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // probes [off, off + cnt) of the query's table -> the segment of each one's list inside [d0, d1) and its score's key
 __device__ __forceinline__ void ct_resolve(const CentroidArgs& a, const int32_t* __restrict__ pcq, const float* __restrict__ psq, int off, int cnt,
                                            int s, int d0, int d1, int64_t* s_e0, int32_t* s_n, uint32_t* s_k) {
@@ -66,11 +55,11 @@ __device__ __forceinline__ void ct_resolve(const CentroidArgs& a, const int32_t*
         int64_t e0 = 0, e1 = 0;
         if (c >= 0 && c < a.K) {
             if (a.slice_off) {
-                const int64_t* so = a.slice_off + (size_t)c * (a.NS + 1) + s;
+                const int64_t* so = a.slice_off + (size_t)c * (a.r.NS + 1) + s;
                 e0 = so[0]; e1 = so[1];
             } else {
-                e0 = ct_lower_bound(a.cdoc, a.coff[c], a.coff[c + 1], d0);
-                e1 = ct_lower_bound(a.cdoc, e0, a.coff[c + 1], d1);
+                e0 = lower_bound_doc(a.cdoc, a.coff[c], a.coff[c + 1], d0);
+                e1 = lower_bound_doc(a.cdoc, e0, a.coff[c + 1], d1);
             }
         }
         s_e0[threadIdx.x] = e0; s_n[threadIdx.x] = e1 > e0 ? (int32_t)(e1 - e0) : 0; s_k[threadIdx.x] = ct_key(psq[off + threadIdx.x]);
@@ -98,7 +87,7 @@ __device__ __forceinline__ void ct_segments(const CentroidArgs& a, float* ct_acc
     }
 }
 
-// The walk both kernels share: query q against the documents [d0, d1) of global slice s; on return ct_acc[0 .. d1 - d0) holds the scores
+// The walk of both epilogues: query q against the documents [d0, d1) of global slice s; on return ct_acc[0 .. d1 - d0) holds the scores
 // (after a barrier).  nprobe <= CT_PROBES: the table is resolved for CT_PROBES / nprobe whole tokens at a time.  A wider token is
 // resolved CT_PROBES probes at a time, once for each phase.
 __device__ __forceinline__ void centroid_walk(const CentroidArgs& a, float* ct_acc, uint32_t* ct_keys, int64_t* s_e0, int32_t* s_n, uint32_t* s_k,
@@ -141,15 +130,9 @@ __device__ __forceinline__ void centroid_walk(const CentroidArgs& a, float* ct_a
     __syncthreads();
 }
 
-// grid (slices of [doc_lo, doc_hi), Q): workgroup (x, q) scores global slice doc_lo / CT_SLICE + x
-__device__ __forceinline__ int ct_slice(const CentroidArgs& a, int& d0, int& d1) {
-    const int s = a.doc_lo / CT_SLICE + (int)blockIdx.x;
-    d0 = s * CT_SLICE;
-    d1 = (d0 + CT_SLICE < a.doc_hi) ? d0 + CT_SLICE : a.doc_hi;
-    return s;
-}
-
-__global__ __launch_bounds__(CT_THREADS) void centroid_scores_kernel(CentroidArgs a) {
+// One workgroup's work in either form.  FILTER: the streaming top-k's threshold filter in place of the plane store.
+template <bool FILTER>
+__device__ __forceinline__ void centroid_scores(const CentroidArgs& a) {
     __shared__ __attribute__((aligned(16))) float ct_acc[CT_SLICE];
     __shared__ uint32_t ct_keys[CT_SLICE];
     __shared__ int64_t s_e0[CT_PROBES];
@@ -157,59 +140,14 @@ __global__ __launch_bounds__(CT_THREADS) void centroid_scores_kernel(CentroidArg
     __shared__ uint32_t s_k[CT_PROBES];
     const int q = blockIdx.y;
     int d0, d1;
-    const int s = ct_slice(a, d0, d1);
-    const int n = d1 - d0;
+    const int s = slice_of(a.r, CT_SLICE, d0, d1);
     centroid_walk(a, ct_acc, ct_keys, s_e0, s_n, s_k, q, s, d0, d1);
-    float* __restrict__ row = a.scores + (size_t)q * a.lds + (d0 - a.doc_lo);
-    for (int j = threadIdx.x; j < n; j += blockDim.x) row[j] = ct_acc[j];
+    if constexpr (FILTER) filter_candidates(ct_acc, d1 - d0, d0, q, a.f);
+    else store_plane(ct_acc, d1 - d0, a.scores, a.lds, q, d0 - a.r.doc_lo);
 }
 
-// The same walk with the streaming top-k's threshold filter in place of the plane store: sparse_dot_filter_kernel's rule and mechanics --
-// a document enters query q's candidates iff !(score <= tau[q]); per wave and 64 documents a ballot and ONE atomicAdd on cand_len[q] for
-// the wave's survivors (none when there are none); nothing is written at or past cap, the flag is set instead.
-__global__ __launch_bounds__(CT_THREADS) void centroid_scores_filter_kernel(CentroidArgs a) {
-    __shared__ __attribute__((aligned(16))) float ct_acc[CT_SLICE];
-    __shared__ uint32_t ct_keys[CT_SLICE];
-    __shared__ int64_t s_e0[CT_PROBES];
-    __shared__ int32_t s_n[CT_PROBES];
-    __shared__ uint32_t s_k[CT_PROBES];
-    const int q = blockIdx.y;
-    int d0, d1;
-    const int s = ct_slice(a, d0, d1);
-    const int n = d1 - d0;
-    centroid_walk(a, ct_acc, ct_keys, s_e0, s_n, s_k, q, s, d0, d1);
-    const float tq = a.tau[q];
-    const int lane = threadIdx.x & 63;
-    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;    // lanes under this one
-    float* __restrict__ cs = a.cand_s + (size_t)q * a.cap;
-    int64_t* __restrict__ ci = a.cand_i + (size_t)q * a.cap;
-    bool over = false;
-    for (int j0 = 0; j0 < n; j0 += blockDim.x) {                              // wave-uniform trip count: every lane takes part in the ballot
-        const int j = j0 + (int)threadIdx.x;
-        const float v = j < n ? ct_acc[j] : 0.0f;
-        const bool keep = j < n && !(v <= tq);
-        const unsigned long long bal = __ballot(keep);
-        if (bal == 0ull) continue;                                            // wave-uniform
-        int base = 0;
-        if (lane == 0) base = atomicAdd(a.cand_len + q, (int)__popcll(bal));
-        base = __shfl(base, 0);
-        if (keep) {
-            const int pos = base + (int)__popcll(bal & below);
-            if (pos < a.cap) {
-                cs[pos] = v;
-                ci[pos] = a.id_base + d0 + j;
-            } else over = true;
-        }
-    }
-    if (over) atomicExch(a.overflow, 1);
-}
-
-__global__ void centroid_slice_offsets_kernel(const int64_t* __restrict__ coff, const int32_t* __restrict__ cdoc, int K, int NS, int64_t* __restrict__ out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)K * (NS + 1)) return;
-    const int c = (int)(i / (NS + 1)), s_ = (int)(i % (NS + 1));
-    out[i] = s_ == NS ? coff[c + 1] : ct_lower_bound(cdoc, coff[c], coff[c + 1], s_ * CT_SLICE);
-}
+__global__ __launch_bounds__(CT_THREADS) void centroid_scores_kernel(CentroidArgs a) { centroid_scores<false>(a); }
+__global__ __launch_bounds__(CT_THREADS) void centroid_scores_filter_kernel(CentroidArgs a) { centroid_scores<true>(a); }
 
 }  // namespace fz
 
@@ -219,25 +157,25 @@ extern "C" int fz_centroid_slice_docs(void) { return CT_SLICE; }
 
 // fz_sparse_slice_offsets at this walk's grain (CT_SLICE is not SP_SLICE)
 extern "C" int fz_centroid_slice_offsets(const int64_t* coff, const int32_t* cdoc, int K, int N, int64_t* out, void* stream) {
-    if (K < 0 || N < 0) return FZ_ERR_ARG;
-    if (K == 0) return FZ_OK;
-    if (!coff || !out) return FZ_ERR_ARG;
-    const int NS = N > 0 ? (N + CT_SLICE - 1) / CT_SLICE : 1;
-    const long total = (long)K * (NS + 1);
-    centroid_slice_offsets_kernel<<<(unsigned)((total + 255) / 256), 256, 0, as_stream(stream)>>>(coff, cdoc, K, NS, out);
-    FZ_LAUNCH_CHECK();
-    return FZ_OK;
+    return slice_offsets_launch(coff, cdoc, K, N, CT_SLICE, out, stream);
 }
 
 // [doc_lo, doc_hi) of an index of N documents: doc_lo a whole slice, doc_hi a whole slice or N; a probe table of Lq >= 1 tokens x nprobe >= 1
 static bool ct_args_ok(int Q, int Lq, int nprobe, int N, int K, int doc_lo, int doc_hi) {
-    return Q >= 0 && Lq >= 1 && nprobe >= 1 && (int64_t)Lq * nprobe <= INT32_MAX && K >= 0 && N >= 0 && doc_lo >= 0 && doc_lo <= doc_hi &&
-           doc_hi <= N && doc_lo % CT_SLICE == 0 && (doc_hi % CT_SLICE == 0 || doc_hi == N);
+    return Q >= 0 && Lq >= 1 && nprobe >= 1 && (int64_t)Lq * nprobe <= INT32_MAX && K >= 0 &&
+           range_ok(N, doc_lo, doc_hi, CT_SLICE);
 }
 
-static int ct_launch(CentroidArgs& a, int Q, bool filter, hipStream_t st) {
-    a.NS = (a.N + CT_SLICE - 1) / CT_SLICE;
-    dim3 grid((unsigned)((a.doc_hi - a.doc_lo + CT_SLICE - 1) / CT_SLICE), (unsigned)Q);
+static CentroidArgs ct_args(const int64_t* coff, const int32_t* cdoc, const int64_t* slice_off, const int32_t* pc, const float* ps, int Lq, int nprobe,
+                            int K, int N, int doc_lo, int doc_hi) {
+    CentroidArgs a{};
+    a.coff = coff; a.cdoc = cdoc; a.slice_off = slice_off; a.pc = pc; a.ps = ps; a.Lq = Lq; a.nprobe = nprobe; a.K = K;
+    a.r = doc_range(N, doc_lo, doc_hi, CT_SLICE);
+    return a;
+}
+
+static int ct_launch(const CentroidArgs& a, int Q, bool filter, hipStream_t st) {
+    const dim3 grid = slice_grid(a.r, CT_SLICE, Q);
     if (filter) centroid_scores_filter_kernel<<<grid, CT_THREADS, 0, st>>>(a);
     else centroid_scores_kernel<<<grid, CT_THREADS, 0, st>>>(a);
     FZ_LAUNCH_CHECK();
@@ -250,9 +188,8 @@ extern "C" int fz_centroid_scores_range_f32(const int64_t* coff, const int32_t* 
     if (!ct_args_ok(Q, Lq, nprobe, N, K, doc_lo, doc_hi) || lds < doc_hi - doc_lo) return FZ_ERR_ARG;
     if (Q == 0 || doc_hi == doc_lo) return FZ_OK;   // empty tensors carry null pointers
     if (!coff || !pc || !ps || !scores) return FZ_ERR_ARG;
-    CentroidArgs a{};
-    a.coff = coff; a.cdoc = cdoc; a.slice_off = slice_off; a.pc = pc; a.ps = ps; a.Lq = Lq; a.nprobe = nprobe; a.K = K;
-    a.N = N; a.doc_lo = doc_lo; a.doc_hi = doc_hi; a.scores = scores; a.lds = lds;
+    CentroidArgs a = ct_args(coff, cdoc, slice_off, pc, ps, Lq, nprobe, K, N, doc_lo, doc_hi);
+    a.scores = scores; a.lds = lds;
     return ct_launch(a, Q, false, as_stream(stream));
 }
 
@@ -262,9 +199,7 @@ extern "C" int fz_centroid_scores_filter_f32(const int64_t* coff, const int32_t*
     if (!ct_args_ok(Q, Lq, nprobe, N, K, doc_lo, doc_hi) || cap <= 0) return FZ_ERR_ARG;
     if (Q == 0 || doc_hi == doc_lo) return FZ_OK;
     if (!coff || !pc || !ps || !tau || !cand_scores || !cand_ids || !cand_len || !overflow) return FZ_ERR_ARG;
-    CentroidArgs a{};
-    a.coff = coff; a.cdoc = cdoc; a.slice_off = slice_off; a.pc = pc; a.ps = ps; a.Lq = Lq; a.nprobe = nprobe; a.K = K;
-    a.N = N; a.doc_lo = doc_lo; a.doc_hi = doc_hi;
-    a.tau = tau; a.cand_s = cand_scores; a.cand_i = cand_ids; a.cand_len = cand_len; a.overflow = overflow; a.cap = cap; a.id_base = id_base;
+    CentroidArgs a = ct_args(coff, cdoc, slice_off, pc, ps, Lq, nprobe, K, N, doc_lo, doc_hi);
+    a.f = {tau, cand_scores, cand_ids, cand_len, overflow, cap, id_base};
     return ct_launch(a, Q, true, as_stream(stream));
 }

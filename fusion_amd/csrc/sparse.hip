@@ -7,8 +7,9 @@
 // i.e. the same products as the dense contraction minus the exact zeros (adding +0.0 to a float32 sum changes nothing: SPLADE weights are
 // >= 0), summed in vocabulary order with one rounding per product and per add (the dense MFMA form fuses them): equal within ~1e-7 relative.
 // One workgroup = (query, slice of SP_SLICE documents): float32 accumulators in LDS, the postings of
-// one term touch distinct documents (no atomics), terms one after the other (barrier): bit-reproducible.  Structure of bm25.hip's kernel.
-#include "common.h"
+// one term touch distinct documents (no atomics), terms one after the other (barrier): bit-reproducible.  Structure of bm25.hip's kernel;
+// what is not the walk -- the slice-offset table, the document range, the plane and filter epilogues -- is slices.h.
+#include "slices.h"
 
 namespace fz {
 
@@ -24,23 +25,12 @@ struct SparseArgs {
     const int64_t* toff; const int32_t* pdoc; const float* pw;     // index: postings of term t are [toff[t], toff[t+1]), documents ascending
     const int64_t* slice_off;                                      // nullable [V][NS + 1]: first posting of term t with document >= s * SP_SLICE
     const int64_t* qoff; const int32_t* qterms; const float* qw;   // queries: non-zero terms of query q are [qoff[q], qoff[q+1]), ascending
-    int N, NS;                                                     // documents of the index, its slices (slice_off's row stride is NS + 1)
-    int doc_lo, doc_hi;                                            // the documents scored: [doc_lo, doc_hi), doc_lo a whole slice
+    DocRange r;                                                    // the documents scored (slice_off's row stride is r.NS + 1)
     float* scores; int lds;                                        // plane form: [Q][lds], column j = document doc_lo + j
-    // filter form (fz_sparse_dot_filter_f32): no plane; what beats tau[q] (or is NaN) goes to query q's candidate list
-    const float* tau; float* cand_s; int64_t* cand_i; int32_t* cand_len; int32_t* overflow; int cap;
-    int64_t id_base;                                               // id of index document 0
+    FilterSink<float> f;                                           // filter form (fz_sparse_dot_filter_f32): no plane
 };
 
-__device__ __forceinline__ int64_t sp_lower_bound(const int32_t* __restrict__ pdoc, int64_t lo, int64_t hi, int doc) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (pdoc[mid] < doc) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// The walk both kernels share: query q against the documents [d0, d1) of global slice s; on return sp_acc[0 .. d1 - d0) holds the scores
+// The walk of both epilogues: query q against the documents [d0, d1) of global slice s; on return sp_acc[0 .. d1 - d0) holds the scores
 // (after a barrier).  Per document the score is the same chain of `acc + w * pw` adds in ascending term order whatever the range or the grid:
 // a range's columns are the full plane's, bit for bit.
 __device__ __forceinline__ void sparse_walk(const SparseArgs& a, float* sp_acc, int64_t* s_e0, int64_t* s_e1, float* s_w, int q, int s, int d0,
@@ -55,11 +45,11 @@ __device__ __forceinline__ void sparse_walk(const SparseArgs& a, float* sp_acc, 
             const int t = a.qterms[pb + threadIdx.x];
             int64_t e0, e1;
             if (a.slice_off) {
-                const int64_t* so = a.slice_off + (size_t)t * (a.NS + 1) + s;
+                const int64_t* so = a.slice_off + (size_t)t * (a.r.NS + 1) + s;
                 e0 = so[0]; e1 = so[1];
             } else {
-                e0 = sp_lower_bound(a.pdoc, a.toff[t], a.toff[t + 1], d0);
-                e1 = sp_lower_bound(a.pdoc, e0, a.toff[t + 1], d1);
+                e0 = lower_bound_doc(a.pdoc, a.toff[t], a.toff[t + 1], d0);
+                e1 = lower_bound_doc(a.pdoc, e0, a.toff[t + 1], d1);
             }
             s_e0[threadIdx.x] = e0; s_e1[threadIdx.x] = e1; s_w[threadIdx.x] = a.qw[pb + threadIdx.x];
         }
@@ -88,71 +78,18 @@ __device__ __forceinline__ void sparse_walk(const SparseArgs& a, float* sp_acc, 
     __syncthreads();
 }
 
-// grid (slices of [doc_lo, doc_hi), Q): workgroup (x, q) scores global slice doc_lo / SP_SLICE + x
-__device__ __forceinline__ int sp_slice(const SparseArgs& a, int& d0, int& d1) {
-    const int s = a.doc_lo / SP_SLICE + (int)blockIdx.x;
-    d0 = s * SP_SLICE;
-    d1 = (d0 + SP_SLICE < a.doc_hi) ? d0 + SP_SLICE : a.doc_hi;
-    return s;
-}
-
+// FILTER: the streaming top-k's threshold filter in place of the plane store
+template <bool FILTER>
 __global__ __launch_bounds__(1024) void sparse_dot_kernel(SparseArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sp_acc[];        // [SP_SLICE]
     __shared__ int64_t s_e0[SP_TERMS], s_e1[SP_TERMS];
     __shared__ float s_w[SP_TERMS];
     const int q = blockIdx.y;
     int d0, d1;
-    const int s = sp_slice(a, d0, d1);
-    const int n = d1 - d0;
+    const int s = slice_of(a.r, SP_SLICE, d0, d1);
     sparse_walk(a, sp_acc, s_e0, s_e1, s_w, q, s, d0, d1);
-    float* __restrict__ row = a.scores + (size_t)q * a.lds + (d0 - a.doc_lo);
-    for (int j = threadIdx.x; j < n; j += blockDim.x) row[j] = sp_acc[j];
-}
-
-// The same walk with the streaming top-k's threshold filter in place of the plane store (fz_dot_scores_filter_f32's rule): a document
-// enters query q's candidates iff !(score <= tau[q]).  Per wave and 64 documents: ballot, ONE atomicAdd on cand_len[q] for the wave's
-// survivors (none when there are none -- the usual case once the threshold has settled), each survivor stores at base + its rank in the
-// ballot.  Candidates arrive in no particular order: fz_topk_fold_f32(unordered) restores "ties by ascending id".
-__global__ __launch_bounds__(1024) void sparse_dot_filter_kernel(SparseArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float sp_acc[];        // [SP_SLICE]
-    __shared__ int64_t s_e0[SP_TERMS], s_e1[SP_TERMS];
-    __shared__ float s_w[SP_TERMS];
-    const int q = blockIdx.y;
-    int d0, d1;
-    const int s = sp_slice(a, d0, d1);
-    const int n = d1 - d0;
-    sparse_walk(a, sp_acc, s_e0, s_e1, s_w, q, s, d0, d1);
-    const float tq = a.tau[q];
-    const int lane = threadIdx.x & 63;
-    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;    // lanes under this one
-    float* __restrict__ cs = a.cand_s + (size_t)q * a.cap;
-    int64_t* __restrict__ ci = a.cand_i + (size_t)q * a.cap;
-    bool over = false;
-    for (int j0 = 0; j0 < n; j0 += blockDim.x) {                              // wave-uniform trip count: every lane takes part in the ballot
-        const int j = j0 + (int)threadIdx.x;
-        const float v = j < n ? sp_acc[j] : 0.0f;
-        const bool keep = j < n && !(v <= tq);
-        const unsigned long long bal = __ballot(keep);
-        if (bal == 0ull) continue;                                            // wave-uniform
-        int base = 0;
-        if (lane == 0) base = atomicAdd(a.cand_len + q, (int)__popcll(bal));
-        base = __shfl(base, 0);
-        if (keep) {
-            const int pos = base + (int)__popcll(bal & below);
-            if (pos < a.cap) {
-                cs[pos] = v;
-                ci[pos] = a.id_base + d0 + j;
-            } else over = true;
-        }
-    }
-    if (over) atomicExch(a.overflow, 1);
-}
-
-__global__ void sparse_slice_offsets_kernel(const int64_t* __restrict__ toff, const int32_t* __restrict__ pdoc, int V, int NS, int64_t* __restrict__ out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)V * (NS + 1)) return;
-    const int t = (int)(i / (NS + 1)), s_ = (int)(i % (NS + 1));
-    out[i] = s_ == NS ? toff[t + 1] : sp_lower_bound(pdoc, toff[t], toff[t + 1], s_ * SP_SLICE);
+    if constexpr (FILTER) filter_candidates(sp_acc, d1 - d0, d0, q, a.f);
+    else store_plane(sp_acc, d1 - d0, a.scores, a.lds, q, d0 - a.r.doc_lo);
 }
 
 }  // namespace fz
@@ -162,30 +99,23 @@ using namespace fz;
 extern "C" int fz_sparse_slice_docs(void) { return SP_SLICE; }
 
 extern "C" int fz_sparse_slice_offsets(const int64_t* toff, const int32_t* pdoc, int V, int N, int64_t* out, void* stream) {
-    if (V < 0 || N < 0) return FZ_ERR_ARG;
-    if (V == 0) return FZ_OK;
-    if (!toff || !out) return FZ_ERR_ARG;
-    const int NS = N > 0 ? (N + SP_SLICE - 1) / SP_SLICE : 1;
-    const long total = (long)V * (NS + 1);
-    sparse_slice_offsets_kernel<<<(unsigned)((total + 255) / 256), 256, 0, as_stream(stream)>>>(toff, pdoc, V, NS, out);
-    FZ_LAUNCH_CHECK();
-    return FZ_OK;
+    return slice_offsets_launch(toff, pdoc, V, N, SP_SLICE, out, stream);
 }
 
-// [doc_lo, doc_hi) of an index of N documents: doc_lo a whole slice, doc_hi a whole slice or N
-static bool sp_range_ok(int N, int doc_lo, int doc_hi) {
-    return N >= 0 && doc_lo >= 0 && doc_lo <= doc_hi && doc_hi <= N && doc_lo % SP_SLICE == 0 && (doc_hi % SP_SLICE == 0 || doc_hi == N);
+static SparseArgs sp_args(const int64_t* toff, const int32_t* pdoc, const float* pw, const int64_t* slice_off, const int64_t* qoff,
+                          const int32_t* qterms, const float* qw, int N, int doc_lo, int doc_hi) {
+    SparseArgs a{};
+    a.toff = toff; a.pdoc = pdoc; a.pw = pw; a.slice_off = slice_off; a.qoff = qoff; a.qterms = qterms; a.qw = qw;
+    a.r = doc_range(N, doc_lo, doc_hi, SP_SLICE);
+    return a;
 }
 
-static int sp_launch(SparseArgs& a, int Q, bool filter, hipStream_t st) {
-    a.NS = (a.N + SP_SLICE - 1) / SP_SLICE;
+template <bool FILTER>
+static int sp_launch(const SparseArgs& a, int Q, hipStream_t st) {
     constexpr size_t lds_bytes = (size_t)SP_SLICE * sizeof(float);
-    static unsigned long long lds_set[2] = {0ull, 0ull};
-    const void* k = filter ? (const void*)sparse_dot_filter_kernel : (const void*)sparse_dot_kernel;
-    if (int rc = raise_lds_limit(k, lds_bytes, lds_set[filter ? 1 : 0])) return rc;
-    dim3 grid((unsigned)((a.doc_hi - a.doc_lo + SP_SLICE - 1) / SP_SLICE), (unsigned)Q);
-    if (filter) sparse_dot_filter_kernel<<<grid, SP_THREADS, lds_bytes, st>>>(a);
-    else sparse_dot_kernel<<<grid, SP_THREADS, lds_bytes, st>>>(a);
+    static unsigned long long lds_set = 0ull;      // (one per instantiation)
+    if (int rc = raise_lds_limit((const void*)sparse_dot_kernel<FILTER>, lds_bytes, lds_set)) return rc;
+    sparse_dot_kernel<FILTER><<<slice_grid(a.r, SP_SLICE, Q), SP_THREADS, lds_bytes, st>>>(a);
     FZ_LAUNCH_CHECK();
     return FZ_OK;
 }
@@ -193,13 +123,12 @@ static int sp_launch(SparseArgs& a, int Q, bool filter, hipStream_t st) {
 extern "C" int fz_sparse_dot_range_f32(const int64_t* toff, const int32_t* pdoc, const float* pw, const int64_t* slice_off, const int64_t* qoff,
                                        const int32_t* qterms, const float* qw, int Q, int N, int doc_lo, int doc_hi, float* scores, int lds,
                                        void* stream) {
-    if (Q < 0 || !sp_range_ok(N, doc_lo, doc_hi) || lds < doc_hi - doc_lo) return FZ_ERR_ARG;
+    if (Q < 0 || !range_ok(N, doc_lo, doc_hi, SP_SLICE) || lds < doc_hi - doc_lo) return FZ_ERR_ARG;
     if (Q == 0 || doc_hi == doc_lo) return FZ_OK;   // empty tensors carry null pointers
     if (!toff || !qoff || !scores) return FZ_ERR_ARG;
-    SparseArgs a{};
-    a.toff = toff; a.pdoc = pdoc; a.pw = pw; a.slice_off = slice_off; a.qoff = qoff; a.qterms = qterms; a.qw = qw;
-    a.N = N; a.doc_lo = doc_lo; a.doc_hi = doc_hi; a.scores = scores; a.lds = lds;
-    return sp_launch(a, Q, false, as_stream(stream));
+    SparseArgs a = sp_args(toff, pdoc, pw, slice_off, qoff, qterms, qw, N, doc_lo, doc_hi);
+    a.scores = scores; a.lds = lds;
+    return sp_launch<false>(a, Q, as_stream(stream));
 }
 
 extern "C" int fz_sparse_dot_f32(const int64_t* toff, const int32_t* pdoc, const float* pw, const int64_t* slice_off, const int64_t* qoff,
@@ -211,12 +140,10 @@ extern "C" int fz_sparse_dot_filter_f32(const int64_t* toff, const int32_t* pdoc
                                         const int32_t* qterms, const float* qw, int Q, int N, int doc_lo, int doc_hi, int64_t id_base,
                                         const float* tau, float* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow,
                                         void* stream) {
-    if (Q < 0 || !sp_range_ok(N, doc_lo, doc_hi) || cap <= 0) return FZ_ERR_ARG;
+    if (Q < 0 || !range_ok(N, doc_lo, doc_hi, SP_SLICE) || cap <= 0) return FZ_ERR_ARG;
     if (Q == 0 || doc_hi == doc_lo) return FZ_OK;
     if (!toff || !qoff || !tau || !cand_scores || !cand_ids || !cand_len || !overflow) return FZ_ERR_ARG;
-    SparseArgs a{};
-    a.toff = toff; a.pdoc = pdoc; a.pw = pw; a.slice_off = slice_off; a.qoff = qoff; a.qterms = qterms; a.qw = qw;
-    a.N = N; a.doc_lo = doc_lo; a.doc_hi = doc_hi;
-    a.tau = tau; a.cand_s = cand_scores; a.cand_i = cand_ids; a.cand_len = cand_len; a.overflow = overflow; a.cap = cap; a.id_base = id_base;
-    return sp_launch(a, Q, true, as_stream(stream));
+    SparseArgs a = sp_args(toff, pdoc, pw, slice_off, qoff, qterms, qw, N, doc_lo, doc_hi);
+    a.f = {tau, cand_scores, cand_ids, cand_len, overflow, cap, id_base};
+    return sp_launch<true>(a, Q, as_stream(stream));
 }

@@ -139,6 +139,57 @@ def test_filter_kernel_alone(name, table, corpus, ops):
             assert bool((st.cand_s[q, :c] > 0).all())
 
 
+def boundary_corpus(S, cap):
+    """S + 37 documents (one full slice and a ragged tail) and three one-word queries: every document holds "xx"; exactly cap hold "aa"
+    and cap + 1 hold "bb", both over the two slices.  Returns (docs, queries, the documents of "aa", of "bb")."""
+    N = S + 37
+    rng = np.random.default_rng(9)
+    hit1 = np.sort(np.concatenate([rng.choice(S, cap - 20, replace=False), S + rng.choice(37, 20, replace=False)]))
+    hit2 = np.sort(np.concatenate([rng.choice(S, cap - 24, replace=False), S + rng.choice(37, 25, replace=False)]))
+    words = [["xx"] * int(n) for n in rng.integers(1, 6, N)]
+    for d in hit1:
+        words[d].append("aa")
+    for d in hit2:
+        words[d] += ["bb", "bb"]
+    return [" ".join(w) for w in words], ["xx", "aa", "bb"], hit1, hit2
+
+
+@pytest.mark.parametrize("name", ["BM25", "TFIDF"])
+def test_filter_at_exactly_cap_and_one_past_it(name, ops):
+    """The filter epilogue at the capacity boundary.  Query 0's tau is its row maximum (ties do not enter: the rule is !(score <= tau)):
+    no survivor; query 1 has exactly cap survivors above tau = 0, query 2 cap + 1 over both slices.  With query 2 switched off (tau = inf)
+    every slot of query 1 is written and the flag stays 0; with it on the flag is 1, the count is cap + 1, and nothing lands at or past
+    cap (the guard behind the buffers)."""
+    S, cap, ID0 = ops.lexical_slice_docs("tfidf" if name == "TFIDF" else "pv"), 64, 2**34
+    docs, queries, hit1, hit2 = boundary_corpus(S, cap)
+    N, Q = len(docs), 3
+    m = make(name, docs)
+    full = m.scores(queries)
+    tau = torch.tensor([float(full[0].max()), 0.0, 0.0], dtype=torch.float64, device="cuda")
+    keep = [torch.nonzero(~(full[q] <= tau[q])).flatten().cpu().numpy() for q in range(Q)]
+    assert [len(x) for x in keep] == [0, cap, cap + 1] and np.array_equal(keep[1], hit1) and np.array_equal(keep[2], hit2)
+    assert hit2[0] < S <= hit2[-1] and hit1[0] < S <= hit1[-1]
+    qoff, flat = m._query_csr(queries)
+    src = ops._lexical_source(m, qoff, flat, ID0)
+    off = tau.clone(); off[2] = float("inf")
+    st, raw_s, raw_i = _filter_buffers(Q, cap, off, guard=cap)
+    src.filter(st, 0, N)
+    assert int(st.overflow) == 0 and st.cand_len.tolist() == [0, cap, 0]
+    order = torch.argsort(st.cand_i[1])
+    np.testing.assert_array_equal(st.cand_i[1][order].cpu().numpy(), hit1 + ID0)                     # every slot written
+    np.testing.assert_array_equal(bits(st.cand_s[1][order]), bits(full[1][torch.from_numpy(hit1).cuda()]))
+    assert bool((st.cand_s[[0, 2]] == -7.0).all()) and bool((raw_s[Q * cap:] == -7.0).all()) and bool((raw_i[Q * cap:] == -7).all())
+    st, raw_s, raw_i = _filter_buffers(Q, cap, tau, guard=cap)
+    src.filter(st, 0, N)
+    assert int(st.overflow) == 1 and st.cand_len.tolist() == [0, cap, cap + 1]
+    np.testing.assert_array_equal(st.cand_i[1].sort().values.cpu().numpy(), hit1 + ID0)
+    ids = (st.cand_i[2] - ID0).cpu().numpy()
+    assert len(set(ids.tolist())) == cap and set(ids.tolist()) <= set(hit2.tolist())                # cap distinct survivors ...
+    np.testing.assert_array_equal(bits(st.cand_s[2]), bits(full[2][torch.from_numpy(ids).cuda()]))  # ... each with its own score
+    assert bool((st.cand_s[0] == -7.0).all()) and bool((st.cand_i[0] == -7).all())
+    assert bool((raw_s[Q * cap:] == -7.0).all()) and bool((raw_i[Q * cap:] == -7).all())            # nothing at or past cap
+
+
 # ---- 3. streamed == plane route at the edges --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("size", ["head_plus_1", "three_heads", "40003"])
 @pytest.mark.parametrize("name", CLASSES)

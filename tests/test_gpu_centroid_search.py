@@ -161,6 +161,37 @@ def test_filter_overflow_sets_the_flag_and_writes_nothing_past_cap(ops, G):
         assert np.array_equal(cs[q].view(np.int32), ref[q, d].view(np.int32))
 
 
+def test_filter_at_exactly_cap_and_one_past_it(ops, G):
+    """One full slice and a ragged tail; query q probes centroid q alone.  Query 0 ties tau on every document (no survivor: the rule is
+    !(score <= tau)), query 1 has exactly cap survivors, query 2 cap + 1 over both slices.  With query 2 switched off (tau = inf) every
+    slot of query 1 is written and the flag stays 0; with it on the flag is 1, the count is cap + 1 and the guard row is untouched."""
+    N, cap, id_base = G + 37, 64, (1 << 35) + 3
+    rng = np.random.default_rng(7)
+    hit1 = np.sort(np.concatenate([rng.choice(G, 44, replace=False), G + rng.choice(37, 20, replace=False)])).astype(np.int32)
+    hit2 = np.sort(np.concatenate([rng.choice(G, 40, replace=False), G + rng.choice(37, 25, replace=False)])).astype(np.int32)
+    lists = [np.arange(N, dtype=np.int32), hit1, hit2]
+    pc_h = np.array([[0, -1], [1, -1], [-1, 2]], dtype=np.int32)
+    ps_h = np.array([[0.5, 9.0], [0.75, 9.0], [9.0, 0.75]], dtype=np.float32)
+    coff, cdoc = CC.index_from_lists(lists)
+    ref = CC.approx_plane(coff, cdoc, pc_h, ps_h, 1, 2, N)
+    tau_h = np.full(3, 0.5, dtype=np.float32)
+    keep = [np.flatnonzero(~(ref[q] <= tau_h[q])) for q in range(3)]
+    assert [len(x) for x in keep] == [0, cap, cap + 1] and keep[2][0] < G <= keep[2][-1] and keep[1][0] < G <= keep[1][-1]
+    index, _, _ = make_index(ops, lists, N)
+    pc, ps = dev(pc_h), dev(ps_h)
+    cs, ci, cl, ov = run_filter(ops, index, pc, ps, 1, 2, 0, N, id_base, dev(np.array([0.5, 0.5, np.inf], dtype=np.float32)), cap)
+    assert ov == 0 and cl.tolist() == [0, cap, 0]
+    assert np.array_equal(np.sort(ci[1]), keep[1] + id_base) and (cs[1] == 0.75).all()       # every slot written
+    assert (cs[[0, 2, 3]] == -7.0).all() and (ci[[0, 2, 3]] == -99).all()
+    cs, ci, cl, ov = run_filter(ops, index, pc, ps, 1, 2, 0, N, id_base, dev(tau_h), cap)
+    assert ov == 1 and cl.tolist() == [0, cap, cap + 1]
+    assert np.array_equal(np.sort(ci[1]), keep[1] + id_base) and (cs[1] == 0.75).all()
+    d = ci[2] - id_base
+    assert len(set(d.tolist())) == cap and set(d.tolist()) <= set(keep[2].tolist())          # cap distinct survivors ...
+    assert np.array_equal(cs[2].view(np.int32), ref[2, d].view(np.int32))                    # ... each with its own score
+    assert (cs[[0, 3]] == -7.0).all() and (ci[[0, 3]] == -99).all()                          # nothing for query 0, nothing past cap
+
+
 # ---- 3. shard search ---------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def shard(ops, G):

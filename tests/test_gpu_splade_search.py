@@ -227,6 +227,54 @@ def test_overflowing_windows_are_redone_exactly(ops):
     assert torch.equal(g_ids, e_ids) and torch.equal(g_sc, e_sc)
 
 
+# ---- 4b. the filter epilogue at the capacity boundary ------------------------------------------------------------------------------
+def test_filter_epilogue_at_exactly_cap_and_one_past_it(ops):
+    """One full slice and a ragged tail, three one-term queries whose scores are exact by construction (0.25 / 0.5 / 0.75 times 1.0):
+    query 0 ties tau everywhere (no survivor: the rule is !(score <= tau)), query 1 has exactly cap survivors, query 2 cap + 1 over both
+    slices.  With query 2 switched off (tau = inf) every slot of query 1 is written and the flag stays 0; with it on, the flag is 1, the
+    count runs to cap + 1, and nothing lands at or past cap (a guard row behind the buffers)."""
+    import types
+    N, Q, cap = S + 37, 3, 64
+    D = np.zeros((N, 4), dtype=np.float32)
+    D[:, 0] = 0.5
+    rng = np.random.default_rng(5)
+    hit1 = np.sort(np.concatenate([rng.choice(S, 44, replace=False), S + rng.choice(37, 20, replace=False)]))
+    hit2 = np.sort(np.concatenate([rng.choice(S, 40, replace=False), S + rng.choice(37, 25, replace=False)]))
+    D[hit1, 1] = 0.75
+    D[:, 2] = 0.25
+    D[hit2, 2] = 0.75
+    Qd = np.eye(3, 4, dtype=np.float32)
+    ref = Qd @ D.T                                                       # one exact product per entry
+    tau_h = np.full(3, 0.5, dtype=np.float32)
+    keep = [np.flatnonzero(~(ref[q] <= tau_h[q])) for q in range(Q)]
+    assert [len(x) for x in keep] == [0, cap, cap + 1] and keep[2][0] < S <= keep[2][-1] and keep[1][0] < S <= keep[1][-1]
+    idx = ops.sparse_index(torch.from_numpy(D).cuda())
+    ql = ops.sparse_rows(torch.from_numpy(Qd).cuda())
+    assert torch.equal(ops.sparse_dot(idx, *ql).cpu(), torch.from_numpy(ref))
+    src = ops._sparse_source(idx, *ql, BASE)
+
+    def run(tau):
+        cs = torch.full((Q + 1, cap), -7.0, dtype=torch.float32, device="cuda")        # row Q: the guard
+        ci = torch.full((Q + 1, cap), -99, dtype=torch.int64, device="cuda")
+        st = types.SimpleNamespace(rows=Q, cap=cap, tau=torch.from_numpy(tau).cuda(), cand_s=cs[:Q], cand_i=ci[:Q],
+                                   cand_len=torch.zeros(Q, dtype=torch.int32, device="cuda"), overflow=torch.zeros(1, dtype=torch.int32, device="cuda"))
+        src.filter(st, 0, N)
+        torch.cuda.synchronize()
+        return cs.cpu().numpy(), ci.cpu().numpy(), st.cand_len.cpu().numpy(), int(st.overflow.item())
+
+    cs, ci, cl, ov = run(np.array([0.5, 0.5, np.inf], dtype=np.float32))
+    assert ov == 0 and cl.tolist() == [0, cap, 0]
+    assert np.array_equal(np.sort(ci[1]), keep[1] + BASE) and (cs[1] == 0.75).all()           # every slot written
+    assert (cs[[0, 2, 3]] == -7.0).all() and (ci[[0, 2, 3]] == -99).all()
+    cs, ci, cl, ov = run(tau_h)
+    assert ov == 1 and cl.tolist() == [0, cap, cap + 1]
+    assert np.array_equal(np.sort(ci[1]), keep[1] + BASE) and (cs[1] == 0.75).all()
+    d = ci[2] - BASE
+    assert len(set(d.tolist())) == cap and set(d.tolist()) <= set(keep[2].tolist())            # cap distinct survivors ...
+    assert np.array_equal(cs[2].view(np.int32), ref[2, d].view(np.int32))                      # ... each with its own score
+    assert (cs[[0, 3]] == -7.0).all() and (ci[[0, 3]] == -99).all()                            # nothing for query 0, nothing past cap
+
+
 # ---- 5. shards ---------------------------------------------------------------------------------------------------------------------
 def sub_index(ops, idx, a, b):
     """The documents [a, b) of an index as an index of their own (documents renumbered from 0)."""
