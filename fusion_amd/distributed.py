@@ -80,13 +80,13 @@ class _ShardedIndex:
 
     def head_docs(self, k: int) -> int:
         """8,192 at k = 1000 (a 0.09 ms sort instead of 0.35, one fold more), rounded up to whole grains (sparse: 14,336)."""
-        return ops.round_up(min(self.HEAD, max(8192, -(-8 * k // 4096) * 4096)), self._grain)
+        return ops.stream_head_docs(k, self._grain, self.HEAD)
 
     def _streams(self, k: int, n: int) -> bool:
-        return k + self.CAP <= ops.sort_max_n() and k <= self.head_docs(k) // 8 and n > self.head_docs(k)
+        return ops.stream_fits(k, self.CAP, self.head_docs(k), n)
 
     def _chunk(self) -> int:
-        return max(self._grain, self.CHUNK // self._grain * self._grain)
+        return ops.stream_chunk(self.CHUNK, self._grain)
 
     def _topk(self, q: tuple, k: int, streaming: bool, mark):
         mark = mark or (lambda name: None)
@@ -94,15 +94,7 @@ class _ShardedIndex:
         self.last_overflow = 0
         if not (streaming and self._streams(k, src.n)):
             return self.two_pass_topk(q, k, mark)
-        head, chunk = self.head_docs(k), self._chunk()
-        S, _ = src.plane(0, head); mark(self.PLANE_MARK)
-        bs, bi = ops.topk_rows(S, k, id_base=self.id_base)
-        del S
-        stream = ops.TopkStream(bs, bi, seen=head, cap=self.CAP); mark("shard_topk_stream")
-        for c0 in range(head, src.n, chunk):
-            stream._feed(src, c0, min(src.n, c0 + chunk), mark)
-        best_s, best_i, _ = stream.result(); mark("shard_topk_stream")
-        self.last_overflow = stream.windows_redone
+        best_s, best_i, self.last_overflow = ops.stream_search(src, k, self.head_docs(k), self._chunk(), self.CAP, self.PLANE_MARK, mark)
         return best_s, best_i
 
     def two_pass_topk(self, q: tuple, k: int, mark=None):
@@ -116,6 +108,11 @@ class _ShardedIndex:
                 s, i = ops.topk_merge(torch.stack([best_s, s]), torch.stack([best_i, i]))
             best_s, best_i = s, i; mark("shard_topk_exact")
         return best_s, best_i
+
+    def _no_lists(self, Q: int, k: int, dev):
+        """An empty shard's (or no query's) lists: all padding, (-inf, -1)."""
+        self.last_overflow = 0
+        return torch.full((Q, k), float("-inf"), dtype=torch.float32, device=dev), torch.full((Q, k), -1, dtype=torch.int64, device=dev)
 
     def _search(self, q: tuple, k: int, mark):
         out = allgather_topk(*self.local_topk(*q, k, mark=mark), group=self.group)
@@ -189,29 +186,24 @@ class ShardedSparseIndex(_ShardedIndex):
         """[Q, k] (score desc, id asc) over this shard for the queries' term lists (ops.sparse_rows); short lists padded with (-inf, -1)."""
         Q = qoff.numel() - 1
         if self.index.N == 0 or Q == 0:
-            self.last_overflow = 0
-            return (torch.full((Q, k), float("-inf"), dtype=torch.float32, device=qoff.device),
-                    torch.full((Q, k), -1, dtype=torch.int64, device=qoff.device))
+            return self._no_lists(Q, k, qoff.device)
         return self._topk((qoff, qterms, qw), k, True, mark)
 
     def search(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, k: int = 1000, mark=None):
         return self._search((qoff, qterms, qw), k, mark)
 
 
-class ShardedLexicalIndex(_ShardedIndex):
+class ShardedLexicalIndex:
     """One rank's shard of a BM25 / AtireBM25 / TF-IDF corpus: a retrievers.bm25 model of the shard's documents built with the WHOLE corpus's
     statistics (`stats=LexicalStats.merge(...)`: global idf and avgdl) and its `id_base`, so every document scores what the whole index
     gives it, bit for bit.  local_topk is the model's own streamed (or plane) top-k in float64; the shards' lists are all-gathered and merged
-    by one stable float64 row sort (ops.topk_merge64): ties go to the ascending global id, whatever the number of shards.  Of _ShardedIndex
-    it takes the constants and last_overflow only: the float32 loops (_topk, two_pass_topk) are not for float64 lists."""
+    by one stable float64 row sort (ops.topk_merge64): ties go to the ascending global id, whatever the number of shards.  CAP, CHUNK and
+    HEAD are the model's."""
 
-    PLANE_MARK = "shard_lexical"
+    last_overflow = 0   # windows of the last local_topk that were redone exactly (the model's)
 
     def __init__(self, model, group=None):
         self.model, self.id_base, self.group = model, int(model.id_base), group
-        self.CAP, self.CHUNK = model.CAP, model.CHUNK
-
-    _grain = property(lambda self: ops.lexical_slice_docs(self.model.lexical_mode() or "pv"))
 
     def local_topk(self, queries: list[str], k: int, mark=None, streaming: bool | None = True):
         """([Q, k] float64 scores, [Q, k] int64 global ids), score desc / id asc, over this shard (k cut to the shard's size).  Marks:
@@ -264,9 +256,7 @@ class ShardedCentroidIndex(_ShardedIndex):
         streaming = self.STREAMING if streaming is None else bool(streaming)
         Q = pc.shape[0]
         if self.index.N == 0 or Q == 0:
-            self.last_overflow = 0
-            return (torch.full((Q, k), float("-inf"), dtype=torch.float32, device=pc.device),
-                    torch.full((Q, k), -1, dtype=torch.int64, device=pc.device))
+            return self._no_lists(Q, k, pc.device)
         return self._topk((pc, ps, Lq, nprobe), k, streaming, mark)
 
     def search(self, pc: torch.Tensor, ps: torch.Tensor, Lq: int, nprobe: int, k: int = 1000, mark=None):

@@ -1044,9 +1044,6 @@ def stream_pieces(lo: int, hi: int, seen: int, pending: int, k: int, cap: int, g
     return out
 
 
-sparse_pieces = stream_pieces   # its name while feed_sparse alone used it
-
-
 class _Source:
     """What a TopkStream is fed from: the scorer of n documents, [lo, hi) in its own numbering, for the stream's queries.  filter(stream, lo,
     hi) launches its filter kernel against the stream's thresholds and candidate buffers; plane(lo, hi) -> (scores [rows, hi - lo], id of
@@ -1099,21 +1096,26 @@ class TopkStream:
     (every window overflows) costs the exact search once, not a wasted streaming pass plus the exact search of the whole shard;
     `windows_redone` counts them.  That needs what the window was fed with: feed_gemm's and feed_sparse's pieces are views of their
     inputs (kept: no copies); feed()'s score buffers are kept only on request (hold=True) -- otherwise, and without exact_on_overflow,
-    the flag stays set and the caller redoes the search.  The three feeds differ only in their _Source; the loop is _feed's."""
+    the flag stays set and the caller redoes the search.  The feeds differ only in their _Source; the loop is _feed's.  The float64
+    ranking (TopkStream64) shares all of it, fold's overflow protocol included: a ranking is _alloc, _fold_candidates, plane_topk, _merge."""
+
+    dtype = torch.float32        # of the lists, the thresholds and the candidate scores
+    _fold_writes_tau = True      # fz_topk_fold_f32 rewrites tau and clears cand_len itself
+    _can_redo = True             # plane_topk is there for an overflowed window
+    _ranking = {}                # what plane_topk takes besides (plane, k, base)
 
     def __init__(self, run_scores: torch.Tensor, run_ids: torch.Tensor, seen: int, cap: int = 7168, exact_on_overflow: bool = True):
-        _dev(run_scores, torch.float32, "TopkStream(run_scores)"); _dev(run_ids, torch.int64, "TopkStream(run_ids)")
+        what = type(self).__name__
+        _dev(run_scores, self.dtype, f"{what}(run_scores)"); _dev(run_ids, torch.int64, f"{what}(run_ids)")
         rows, k = run_scores.shape
-        _need(tuple(run_ids.shape) == (rows, k) and seen > 0 and cap > 0, "TopkStream: lists [rows, k], seen > 0, cap > 0 expected")
+        _need(tuple(run_ids.shape) == (rows, k) and seen > 0 and cap > 0, f"{what}: lists [rows, k], seen > 0, cap > 0 expected")
         dev = run_scores.device
         self.rows, self.k, self.cap = rows, k, int(cap)
         self.best_s, self.best_i = run_scores.contiguous(), run_ids.contiguous()
-        # thresholds, padded to whole 128-query GEMM blocks with +inf (the fused GEMM reads its tile's 128 rows unconditionally)
-        self._tau_pad = torch.full((round_up(max(rows, 1), 128),), float("inf"), dtype=torch.float32, device=dev)
-        self.tau = self._tau_pad[:rows]
+        self._alloc(dev)
         self.tau.copy_(self.best_s[:, k - 1])
         self.unordered = False           # candidates appended by the fused feeds arrive in no particular order
-        self.cand_s = torch.empty((rows, cap), dtype=torch.float32, device=dev)
+        self.cand_s = torch.empty((rows, cap), dtype=self.dtype, device=dev)
         self.cand_i = torch.empty((rows, cap), dtype=torch.int64, device=dev)
         self.cand_len = torch.zeros(rows, dtype=torch.int32, device=dev)
         self.overflow = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -1123,10 +1125,32 @@ class TopkStream:
         self.windows_redone = 0
         self._pieces = []                # what the current window was fed with: (source, lo, hi)
         self._unheld = False             # ... and whether some of it was fed without being held (feed(hold=False))
-        self.unrepairable = False        # host latch: a window fed WITHOUT hold overflowed -- nothing the stream holds can repair it, the device
-                                         #   flag stays set and the caller redoes the search; later windows are neither read nor redone
-        wsb = int(_lib.lib().fz_topk_fold_workspace_bytes(rows, k, cap))
+        self.unrepairable = False        # host latch: a window fed WITHOUT hold (or with no plane_topk) overflowed -- nothing the stream holds can
+                                         #   repair it, the device flag stays set and the caller redoes the search; later windows are neither read nor redone
+
+    # -- the float32 ranking: the sort kernels' own top-k, fold and merge entries --
+    def _alloc(self, dev):
+        # tau [rows] and what _fold_candidates works in.  Thresholds are padded to whole 128-query GEMM blocks with +inf (the fused GEMM reads its tile's 128 rows unconditionally)
+        self._tau_pad = torch.full((round_up(max(self.rows, 1), 128),), float("inf"), dtype=torch.float32, device=dev)
+        self.tau = self._tau_pad[:self.rows]
+        wsb = int(_lib.lib().fz_topk_fold_workspace_bytes(self.rows, self.k, self.cap))
         self._ws, self._wsb = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev), wsb
+
+    def _fold_candidates(self):      # the window's candidates folded into the list -> the new (scores, ids)
+        ns, ni = torch.empty_like(self.best_s), torch.empty_like(self.best_i)
+        check(_lib.lib().fz_topk_fold_f32(_ptr(self.best_s), _ptr(self.best_i), self.rows, self.k, _ptr(self.cand_s), _ptr(self.cand_i),
+                                          _ptr(self.cand_len), self.cap, 1 if self.unordered else 0, _ptr(ns), _ptr(ni), _ptr(self.tau),
+                                          _ptr(self.overflow), _ptr(self._ws), self._wsb, _stream(self.best_s)), "fz_topk_fold_f32")
+        return ns, ni
+
+    @staticmethod
+    def plane_topk(scores, k: int, base: int):
+        """The exact top-k (scores, ids) of a plane whose column 0 has the id `base`: a search's head, a piece of an overflowed window."""
+        return topk_rows(scores, k, id_base=base)
+
+    @staticmethod
+    def _merge(s, i, ps, pi):    # a later piece's ranked list onto the running one (ties by ascending id, as everywhere)
+        return topk_merge(torch.stack([s, ps]), torch.stack([i, pi]))
 
     def _feed(self, source, lo: int, hi: int, mark=None):
         """The source's documents [lo, hi), cut at the fold windows (stream_pieces): one filter launch per piece, a fold where planned."""
@@ -1168,35 +1192,34 @@ class TopkStream:
         lists, nothing is copied."""
         Q = _sparse_queries(qoff, qterms, qw, "TopkStream.feed_sparse")
         _need(Q == self.rows, "TopkStream.feed_sparse: one query per running list")
-        doc_lo, doc_hi = _sparse_range(index, doc_lo, doc_hi, "TopkStream.feed_sparse")
+        doc_lo, doc_hi = _doc_range("TopkStream.feed_sparse", index.N, sparse_slice_docs(), doc_lo, doc_hi)
         self._feed(_sparse_source(index, qoff, qterms, qw, int(id_base)), doc_lo, doc_hi, mark)
 
     def fold(self):
         if self.pending == 0:
             return
-        ns, ni = torch.empty_like(self.best_s), torch.empty_like(self.best_i)
-        check(_lib.lib().fz_topk_fold_f32(_ptr(self.best_s), _ptr(self.best_i), self.rows, self.k, _ptr(self.cand_s), _ptr(self.cand_i),
-                                          _ptr(self.cand_len), self.cap, 1 if self.unordered else 0, _ptr(ns), _ptr(ni), _ptr(self.tau),
-                                          _ptr(self.overflow), _ptr(self._ws), self._wsb, _stream(self.best_s)), "fz_topk_fold_f32")
+        ns, ni = self._fold_candidates()
+        redone = False
         # The device flag is read at the fold (one small device -> host read per window) for as long as the search can still come out
-        # exact: once an UNHELD window has overflowed the caller redoes the whole search anyway, so later windows are neither read nor
-        # redone (ADVICE r5: with one sticky device flag every later held window ran the full exact redo for nothing).  Every earlier
-        # overflow was either repaired (flag cleared below) or latched, so a non-zero flag here is THIS window's.
+        # exact: once a window that cannot be redone has overflowed the caller redoes the whole search anyway, so later windows are neither
+        # read nor redone (ADVICE r5: with one sticky device flag every later held window ran the full exact redo for nothing).  Every
+        # earlier overflow was either repaired (flag cleared below) or latched, so a non-zero flag here is THIS window's.
         if self.exact_on_overflow and not self.unrepairable and int(self.overflow.item()) != 0:
-            if self._unheld:
-                self.unrepairable = True     # fed without hold: no exact redo for this window; the flag stays set
+            if self._unheld or not self._can_redo:
+                self.unrepairable = True     # nothing to redo the window from: the flag stays set
             else:
                 # a candidate list was cut short (or a tie run was too long to order): this window again, exactly, on top of the list as
-                # it stood before it -- per piece: scores -> fz_topk_rows_f32 -> merge (ties by ascending id, as everywhere)
+                # it stood before it -- per piece: scores -> plane_topk -> _merge
                 ns, ni = self.best_s, self.best_i
                 for source, lo, hi in self._pieces:
                     sc, base = source.plane(lo, hi)
-                    ps, pi = topk_rows(sc, self.k, id_base=base)
-                    ns, ni = topk_merge(torch.stack([ns, ps]), torch.stack([ni, pi]))
-                self.tau.copy_(ns[:, self.k - 1])
-                self.cand_len.zero_()
+                    ns, ni = self._merge(ns, ni, *self.plane_topk(sc, self.k, base, **self._ranking))
                 self.overflow.zero_()
                 self.windows_redone += 1
+                redone = True
+        if redone or not self._fold_writes_tau:
+            self.tau.copy_(ns[:, self.k - 1])
+            self.cand_len.zero_()
         self._pieces.clear()
         self._unheld = False
         self.best_s, self.best_i = ns, ni
@@ -1206,6 +1229,34 @@ class TopkStream:
     def result(self):
         self.fold()
         return self.best_s, self.best_i, self.overflow
+
+
+def stream_head_docs(k: int, grain: int, head_max: int) -> int:
+    """Leading documents that get the exact top-k: 8 k, at least 8,192 (a 0.09 ms sort instead of 0.35 at k = 1000, one fold more), whole grains."""
+    return round_up(min(head_max, max(8192, -(-8 * k // 4096) * 4096)), grain)
+
+
+def stream_fits(k: int, cap: int, head: int, n: int, dtype=torch.float32) -> bool:
+    """stream_search can run: list + candidates fit one sort row of the ranking's dtype, the head holds 8 k documents, more follow it."""
+    return k + cap <= sort_max_n(dtype) and k <= head // 8 and n > head
+
+
+def stream_chunk(chunk: int, grain: int) -> int:
+    return max(grain, chunk // grain * grain)     # documents per feed: whole grains, at least one
+
+
+def stream_search(src: _Source, k: int, head: int, chunk: int, cap: int, plane_mark: str, mark, cls=TopkStream, **ranking):
+    """The streamed search of src.n documents -> (scores [rows, k], ids, windows redone exactly): the first `head` are scored into a plane
+    and get the exact top-k, the rest goes through the source's filter in feeds of `chunk` (a stream of class `cls`; **ranking: what its
+    constructor and plane_topk take besides).  mark(name) after every launch group: plane_mark, src.mark, 'shard_topk_stream' (top-k work)."""
+    S, base = src.plane(0, head); mark(plane_mark)
+    bs, bi = cls.plane_topk(S, k, base, **ranking)
+    del S
+    stream = cls(bs, bi, seen=head, cap=cap, **ranking); mark("shard_topk_stream")
+    for c0 in range(head, src.n, chunk):
+        stream._feed(src, c0, min(src.n, c0 + chunk), mark)
+    best_s, best_i, _ = stream.result(); mark("shard_topk_stream")
+    return best_s, best_i, stream.windows_redone
 
 
 def topk_merge(in_scores: torch.Tensor, in_ids: torch.Tensor):
@@ -1233,23 +1284,59 @@ def bm25_doc_norms(doc_len: torch.Tensor, avgdl: float, k1: float, b: float) -> 
     return out
 
 
+# -- the host contract of the inverted-index entries (BM25 / TF-IDF, SPLADE, centroids: their kernels share csrc/slices.h) --
+def _n_slices(N: int, slice_docs: int) -> int:
+    """Slices of slice_docs documents in an index of N: the NS of its [rows, NS + 1] slice table."""
+    return max(1, -(-int(N) // int(slice_docs)))
+
+
+def _slice_table(what: str, slice_off, rows: int, N: int, kind: str):
+    """slice_off is the contiguous [rows, NS + 1] int64 table of ops.<kind>_slice_offsets for N documents."""
+    NS = _n_slices(N, getattr(_lib.lib(), f"fz_{kind}_slice_docs")())
+    _need(_dev(slice_off, torch.int64, f"{what}(slice_off)").is_contiguous() and tuple(slice_off.shape) == (rows, NS + 1),
+          f"{what}(slice_off): expected a contiguous [{rows}, {NS + 1}] table (ops.{kind}_slice_offsets)")
+
+
+def _slice_offsets(kind: str, off: torch.Tensor, doc: torch.Tensor, rows: int | None, N: int) -> torch.Tensor:
+    """[rows, NS + 1] int64: where every list (off [rows + 1] into doc, ascending inside a list) crosses the document slices one workgroup
+    scores (fz_<kind>_slice_offsets / fz_<kind>_slice_docs; built once per index, like an idf table)."""
+    what, lib = f"{kind}_slice_offsets", _lib.lib()
+    _dev(off, torch.int64, f"{what}(offsets)"); _dev(doc, torch.int32, f"{what}(documents)")
+    rows = off.numel() - 1 if rows is None else int(rows)
+    _need(off.is_contiguous() and doc.is_contiguous() and off.numel() == rows + 1 >= 1, f"{what}: contiguous offsets [{rows + 1}] and documents expected")
+    out = torch.empty((rows, _n_slices(N, getattr(lib, f"fz_{kind}_slice_docs")()) + 1), dtype=torch.int64, device=off.device)
+    check(getattr(lib, f"fz_{kind}_slice_offsets")(_ptr(off), _ptr(doc), rows, int(N), _ptr(out), _stream(off)), f"fz_{kind}_slice_offsets")
+    return out
+
+
+def _doc_range(what: str, N: int, grain: int, doc_lo: int, doc_hi: int | None):
+    """-> (doc_lo, doc_hi) of a range entry: it starts on a multiple of the walk's grain and ends on one or at N (the default)."""
+    doc_lo, doc_hi = int(doc_lo), int(N) if doc_hi is None else int(doc_hi)
+    _need(0 <= doc_lo <= doc_hi <= N and doc_lo % grain == 0 and (doc_hi % grain == 0 or doc_hi == N),
+          f"{what}: [doc_lo, doc_hi) = [{doc_lo}, {doc_hi}) must start on a multiple of {grain} and end on one or at N = {N}")
+    return doc_lo, doc_hi
+
+
+def _cand_buffers(what: str, dtype, Q: int, tau, cand_s, cand_i, cand_len, overflow) -> int:
+    """The buffers a filter entry appends to -> cap: cand_s (dtype) / cand_i int64 contiguous [Q, cap >= 1]; tau (dtype) and cand_len int32
+    hold at least Q entries (the kernels read the first Q: a caller's guard rows may follow), overflow int32 at least one."""
+    _dev(tau, dtype, f"{what}(tau)"); _dev(cand_s, dtype, f"{what}(cand_s)"); _dev(cand_i, torch.int64, f"{what}(cand_i)")
+    _dev(cand_len, torch.int32, f"{what}(cand_len)"); _dev(overflow, torch.int32, f"{what}(overflow)")
+    cap = cand_s.shape[1] if cand_s.dim() == 2 else 0
+    _need(cap >= 1 and cand_s.is_contiguous() and cand_i.is_contiguous() and tuple(cand_s.shape) == (Q, cap) and tuple(cand_i.shape) == (Q, cap)
+          and tau.numel() >= Q and cand_len.numel() >= Q and overflow.numel() >= 1,
+          f"{what}: tau [Q], cand_s / cand_i [Q, cap >= 1] contiguous, cand_len [Q], overflow [1] expected")
+    return cap
+
+
 def bm25_slice_table_bytes(V: int, N: int) -> int:
     """Device bytes of bm25_slice_offsets' table for V terms over N documents: V x (NS + 1) int64."""
-    NS = max(1, -(-int(N) // int(_lib.lib().fz_bm25_slice_docs())))
-    return int(V) * (NS + 1) * 8
+    return int(V) * (_n_slices(N, _lib.lib().fz_bm25_slice_docs()) + 1) * 8
 
 
 def bm25_slice_offsets(toff: torch.Tensor, pdoc: torch.Tensor, N: int) -> torch.Tensor:
-    """Per-index table [V, NS + 1] int64 for bm25_scores(slice_off=...): where every term's postings cross the document slices one
-    workgroup scores (fz_bm25_slice_offsets; built once per index, like the idf table)."""
-    _dev(toff, torch.int64, "bm25_slice_offsets(toff)"); _dev(pdoc, torch.int32, "bm25_slice_offsets(pdoc)")
-    _need(toff.is_contiguous() and pdoc.is_contiguous() and toff.numel() >= 1, "bm25_slice_offsets: contiguous toff [V + 1] and pdoc expected")
-    V = toff.numel() - 1
-    lib = _lib.lib()
-    NS = max(1, -(-int(N) // int(lib.fz_bm25_slice_docs())))
-    out = torch.empty((V, NS + 1), dtype=torch.int64, device=toff.device)
-    check(lib.fz_bm25_slice_offsets(_ptr(toff), _ptr(pdoc), V, int(N), _ptr(out), _stream(toff)), "fz_bm25_slice_offsets")
-    return out
+    """Per-index table [V, NS + 1] int64 for bm25_scores(slice_off=...) (fz_bm25_slice_offsets)."""
+    return _slice_offsets("bm25", toff, pdoc, None, N)
 
 
 def bm25_scores(toff, pdoc, ptf, idf, doc_len, avgdl: float, k1: float, b: float, qoff, qterms, Q: int, N: int,
@@ -1265,9 +1352,7 @@ def bm25_scores(toff, pdoc, ptf, idf, doc_len, avgdl: float, k1: float, b: float
             _need(_dev(t, dt, f"bm25_scores({what})").is_contiguous(), f"bm25_scores({what}) must be contiguous")
         _need(pval.numel() == pdoc.numel() and qoff.numel() == Q + 1, "bm25_scores: pval must hold one value per posting and qoff Q + 1 offsets")
         if slice_off is not None:
-            NS = max(1, -(-int(N) // int(_lib.lib().fz_bm25_slice_docs())))
-            _need(_dev(slice_off, torch.int64, "bm25_scores(slice_off)").is_contiguous() and tuple(slice_off.shape) == (toff.numel() - 1, NS + 1),
-                  f"bm25_scores(slice_off): expected a contiguous [{toff.numel() - 1}, {NS + 1}] table (ops.bm25_slice_offsets)")
+            _slice_table("bm25_scores", slice_off, toff.numel() - 1, N, "bm25")
         out = torch.empty((max(Q, 1), max(round_up(N, _PAD), _PAD)), dtype=torch.float64, device=dev)[:Q, :N]
         out32 = alloc_plane(Q, N, torch.float32, dev) if want_f32 else None
         check(_lib.lib().fz_bm25_scores_pv_f64_f32(_ptr(toff), _ptr(pdoc), _ptr(pval), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, _ptr(out),
@@ -1282,9 +1367,7 @@ def bm25_scores(toff, pdoc, ptf, idf, doc_len, avgdl: float, k1: float, b: float
     if doc_norm is not None:
         _need(_dev(doc_norm, torch.float64, "bm25_scores(doc_norm)").numel() == N and doc_norm.is_contiguous(), f"bm25_scores: doc_norm must hold {N} values")
     if slice_off is not None:
-        NS = max(1, -(-int(N) // int(_lib.lib().fz_bm25_slice_docs())))
-        _need(_dev(slice_off, torch.int64, "bm25_scores(slice_off)").is_contiguous() and tuple(slice_off.shape) == (idf.numel(), NS + 1),
-              f"bm25_scores(slice_off): expected a contiguous [{idf.numel()}, {NS + 1}] table (ops.bm25_slice_offsets)")
+        _slice_table("bm25_scores", slice_off, idf.numel(), N, "bm25")
     out = torch.empty((max(Q, 1), max(round_up(N, _PAD), _PAD)), dtype=torch.float64, device=dev)[:Q, :N]
     out32 = alloc_plane(Q, N, torch.float32, dev) if want_f32 else None
     check(_lib.lib().fz_bm25_scores_f64_f32(_ptr(toff), _ptr(pdoc), _ptr(ptf), _ptr(idf), _ptr(doc_len), _ptr(doc_norm), _ptr(slice_off), float(avgdl),
@@ -1316,9 +1399,7 @@ def tfidf_scores(toff, pdoc, ptf, idf, qoff, qterms, Q: int, N: int, slice_off: 
     _need(toff.numel() == idf.numel() + 1 and pdoc.numel() == ptf.numel() and qoff.numel() == Q + 1,
           "tfidf_scores: toff must hold V + 1 offsets for idf's V terms, pdoc / ptf one entry per posting, qoff Q + 1 offsets")
     if slice_off is not None:
-        NS = max(1, -(-int(N) // int(_lib.lib().fz_bm25_slice_docs())))
-        _need(_dev(slice_off, torch.int64, "tfidf_scores(slice_off)").is_contiguous() and tuple(slice_off.shape) == (idf.numel(), NS + 1),
-              f"tfidf_scores(slice_off): expected a contiguous [{idf.numel()}, {NS + 1}] table (ops.bm25_slice_offsets)")
+        _slice_table("tfidf_scores", slice_off, idf.numel(), N, "bm25")
     out = torch.empty((max(Q, 1), max(round_up(N, _PAD), _PAD)), dtype=torch.float64, device=dev)[:Q, :N]
     out32 = alloc_plane(Q, N, torch.float32, dev) if want_f32 else None
     check(_lib.lib().fz_tfidf_scores_f64(_ptr(toff), _ptr(pdoc), _ptr(ptf), _ptr(idf), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N,
@@ -1349,15 +1430,8 @@ def _lexical_args(what: str, mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: 
     if mode == "tfidf":
         _need(_dev(idf, torch.float64, f"{what}(idf)").is_contiguous() and idf.numel() == V, f"{what}: idf must hold one value per term")
     if slice_off is not None:
-        NS = max(1, -(-int(N) // int(_lib.lib().fz_bm25_slice_docs())))
-        _need(_dev(slice_off, torch.int64, f"{what}(slice_off)").is_contiguous() and tuple(slice_off.shape) == (V, NS + 1),
-              f"{what}(slice_off): expected a contiguous [{V}, {NS + 1}] table (ops.bm25_slice_offsets)")
-    S = lexical_slice_docs(mode)
-    doc_hi = int(N) if doc_hi is None else int(doc_hi)
-    doc_lo = int(doc_lo)
-    _need(0 <= doc_lo <= doc_hi <= N and doc_lo % S == 0 and (doc_hi % S == 0 or doc_hi == N),
-          f"{what}: [{doc_lo}, {doc_hi}) must start on a multiple of {S} documents and end on one or at N = {N}")
-    return doc_lo, doc_hi
+        _slice_table(what, slice_off, V, N, "bm25")     # the table's slices are fz_bm25_slice_docs wide, the range's lexical_slice_docs(mode)
+    return _doc_range(what, N, lexical_slice_docs(mode), doc_lo, doc_hi)
 
 
 def _range_plane64(Q: int, n: int, dev) -> torch.Tensor:
@@ -1392,13 +1466,7 @@ def lexical_filter(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: in
     past cap, nothing is stored there, `overflow` (int32 [1]) is set.  vals: pval ('pv') or ptf ('tfidf', with idf)."""
     what = "lexical_filter"
     doc_lo, doc_hi = _lexical_args(what, mode, toff, pdoc, vals, idf, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
-    _need(_dev(tau, torch.float64, f"{what}(tau)").is_contiguous() and tau.numel() == Q, f"{what}: tau must hold {Q} float64 thresholds")
-    _need(_dev(cand_s, torch.float64, f"{what}(cand_s)").is_contiguous() and _dev(cand_i, torch.int64, f"{what}(cand_i)").is_contiguous()
-          and cand_s.dim() == 2 and cand_s.shape[0] == Q and cand_s.shape[1] > 0 and cand_i.shape == cand_s.shape,
-          f"{what}: contiguous cand_s float64 / cand_i int64 [{Q}, cap] expected")
-    _need(_dev(cand_len, torch.int32, f"{what}(cand_len)").is_contiguous() and cand_len.numel() == Q
-          and _dev(overflow, torch.int32, f"{what}(overflow)").numel() >= 1, f"{what}: cand_len int32 [{Q}] and overflow int32 [1] expected")
-    cap, lib = cand_s.shape[1], _lib.lib()
+    cap, lib = _cand_buffers(what, torch.float64, Q, tau, cand_s, cand_i, cand_len, overflow), _lib.lib()
     if mode == "pv":
         check(lib.fz_bm25_filter_pv_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi, int(id_base),
                                         _ptr(tau), _ptr(cand_s), _ptr(cand_i), _ptr(cand_len), cap, _ptr(overflow), _stream(toff)), "fz_bm25_filter_pv_f64")
@@ -1446,68 +1514,44 @@ def _merge_ranked64(best_s, best_i, s, i, seq: torch.Tensor | None = None, seq_l
 
 
 class TopkStream64(TopkStream):
-    """TopkStream for float64 lists, thresholds and candidate scores (BM25 / TF-IDF: the ranking is decided in float64).  The feed loop, the
-    windows and their bookkeeping are TopkStream's own (_feed, stream_pieces); the buffers and the fold are this class's.  The fold needs no
+    """TopkStream for float64 lists, thresholds and candidate scores (BM25 / TF-IDF: the ranking is decided in float64).  The fold needs no
     sort kernel of its own: the running list holds only documents seen earlier -- every id in it is below every candidate's -- and is
     ordered (score desc, id asc); the window's candidates are put in ascending-id order (one argsort of the id slots, unwritten slots last)
     and the stable float64 row sort orders the row [best (k) | candidates (<= cap)] once: ties go to the ascending id, the rule of the full
-    ranking.  Same overflow / windows_redone / exact_on_overflow contract; an overflowed window is redone from its pieces' range planes
-    (`top_positions(plane, k)`: the exact stable top-k of a plane, TFIDF._top_positions)."""
+    ranking.  An overflowed window is redone from its pieces' range planes (`top_positions(plane, k)`: the exact stable top-k of a plane,
+    TFIDF._top_positions); without top_positions it cannot be."""
+
+    dtype = torch.float64
+    _fold_writes_tau = False     # the fold is torch ops and a row sort: the host rewrites tau and clears cand_len
 
     def __init__(self, run_scores: torch.Tensor, run_ids: torch.Tensor, seen: int, cap: int = 7168, exact_on_overflow: bool = True,
                  top_positions=None):
-        _dev(run_scores, torch.float64, "TopkStream64(run_scores)"); _dev(run_ids, torch.int64, "TopkStream64(run_ids)")
-        rows, k = run_scores.shape
-        _need(tuple(run_ids.shape) == (rows, k) and seen > 0 and cap > 0, "TopkStream64: lists [rows, k], seen > 0, cap > 0 expected")
-        _need(k + cap <= sort_max_n(torch.float64), f"TopkStream64: k + cap = {k + cap} exceeds one float64 sort row ({sort_max_n(torch.float64)})")
-        dev = run_scores.device
-        self.rows, self.k, self.cap = rows, k, int(cap)
-        self.best_s, self.best_i = run_scores.contiguous(), run_ids.contiguous()
-        self.tau = self.best_s[:, k - 1].clone()
-        self.unordered = False
-        self.cand_s = torch.empty((rows, cap), dtype=torch.float64, device=dev)
-        self.cand_i = torch.empty((rows, cap), dtype=torch.int64, device=dev)
-        self.cand_len = torch.zeros(rows, dtype=torch.int32, device=dev)
-        self.overflow = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.seen, self.pending = int(seen), 0
-        self.exact_on_overflow = bool(exact_on_overflow)
-        self.windows_redone = 0
-        self._pieces, self._unheld, self.unrepairable = [], False, False
-        self._top_positions = top_positions
-        self._slot = torch.arange(cap, dtype=torch.int32, device=dev)
+        self._ranking, self._can_redo = dict(top_positions=top_positions), top_positions is not None
+        super().__init__(run_scores, run_ids, seen, cap, exact_on_overflow)
+
+    def _alloc(self, dev):
+        W = sort_max_n(torch.float64)
+        _need(self.k + self.cap <= W, f"TopkStream64: k + cap = {self.k + self.cap} exceeds one float64 sort row ({W})")
+        self.tau = torch.empty(self.rows, dtype=torch.float64, device=dev)
+        self._slot = torch.arange(self.cap, dtype=torch.int32, device=dev)
+
+    def _fold_candidates(self):
+        n = torch.clamp(self.cand_len, max=self.cap)
+        live = self._slot[None, :] < n[:, None]
+        by_id = torch.argsort(torch.where(live, self.cand_i, torch.iinfo(torch.int64).max), dim=1)       # ascending ids, unwritten slots last
+        return _merge_ranked64(self.best_s, self.best_i, torch.where(live, self.cand_s, float("-inf")), self.cand_i, seq=by_id, seq_len=n)
+
+    @staticmethod
+    def plane_topk(scores, k: int, base: int, top_positions):
+        pos = top_positions(scores, min(k, scores.shape[1]))
+        return torch.gather(scores, 1, pos), pos + base
+
+    _merge = staticmethod(_merge_ranked64)      # the same [best | piece] stable sort
 
     def feed_lexical(self, model, qoff: torch.Tensor, qterms: torch.Tensor, doc_lo: int, doc_hi: int, id_base: int, mark=None):
         """Score documents [doc_lo, doc_hi) of a lexical model's index and keep what beats the thresholds, in one kernel per piece."""
         _need(qoff.numel() - 1 == self.rows, "TopkStream64.feed_lexical: one query per running list")
         self._feed(_lexical_source(model, qoff, qterms, int(id_base)), doc_lo, doc_hi, mark)
-
-    def fold(self):
-        if self.pending == 0:
-            return
-        n = torch.clamp(self.cand_len, max=self.cap)
-        live = self._slot[None, :] < n[:, None]
-        by_id = torch.argsort(torch.where(live, self.cand_i, torch.iinfo(torch.int64).max), dim=1)       # ascending ids, unwritten slots last
-        ns, ni = _merge_ranked64(self.best_s, self.best_i, torch.where(live, self.cand_s, float("-inf")), self.cand_i, seq=by_id, seq_len=n)
-        if self.exact_on_overflow and not self.unrepairable and int(self.overflow.item()) != 0:
-            if self._unheld or self._top_positions is None:
-                self.unrepairable = True     # nothing to redo the window from: the flag stays set
-            else:
-                # a candidate list was cut short: this window again, exactly, on top of the list as it stood before it -- per piece:
-                # range plane -> exact top-k of it -> the same [best | piece] stable sort
-                ns, ni = self.best_s, self.best_i
-                for source, lo, hi in self._pieces:
-                    sc, base = source.plane(lo, hi)
-                    pos = self._top_positions(sc, min(self.k, hi - lo))
-                    ns, ni = _merge_ranked64(ns, ni, torch.gather(sc, 1, pos), pos + base)
-                self.overflow.zero_()
-                self.windows_redone += 1
-        self.tau.copy_(ns[:, self.k - 1])
-        self.cand_len.zero_()
-        self._pieces.clear()
-        self._unheld = False
-        self.best_s, self.best_i = ns, ni
-        self.seen += self.pending
-        self.pending = 0
 
 
 def topk_merge64(in_scores: torch.Tensor, in_ids: torch.Tensor):
@@ -1567,12 +1611,7 @@ class SparseIndex:
 
 
 def sparse_slice_offsets(toff: torch.Tensor, pdoc: torch.Tensor, V: int, N: int) -> torch.Tensor:
-    _need(_dev(toff, torch.int64, "sparse_slice_offsets(toff)").is_contiguous() and toff.numel() == V + 1, f"sparse_slice_offsets: toff must hold {V + 1} offsets")
-    _need(_dev(pdoc, torch.int32, "sparse_slice_offsets(pdoc)").is_contiguous(), "sparse_slice_offsets(pdoc) must be contiguous")
-    NS = max(1, -(-int(N) // int(_lib.lib().fz_sparse_slice_docs())))
-    out = torch.empty((V, NS + 1), dtype=torch.int64, device=toff.device)
-    check(_lib.lib().fz_sparse_slice_offsets(_ptr(toff), _ptr(pdoc), V, int(N), _ptr(out), _stream(toff)), "fz_sparse_slice_offsets")
-    return out
+    return _slice_offsets("sparse", toff, pdoc, V, N)
 
 
 def density(X: torch.Tensor) -> float:
@@ -1643,21 +1682,13 @@ def sparse_slice_docs() -> int:
     return int(_lib.lib().fz_sparse_slice_docs())
 
 
-def _sparse_range(index: SparseIndex, doc_lo: int, doc_hi: int | None, what: str):
-    doc_hi = index.N if doc_hi is None else int(doc_hi)
-    S = sparse_slice_docs()
-    _need(0 <= doc_lo <= doc_hi <= index.N and doc_lo % S == 0 and (doc_hi % S == 0 or doc_hi == index.N),
-          f"{what}: [doc_lo, doc_hi) = [{doc_lo}, {doc_hi}) must start on a multiple of {S} and end on one or at N = {index.N}")
-    return int(doc_lo), doc_hi
-
-
 def sparse_dot(index: SparseIndex, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, out: torch.Tensor | None = None,
                doc_lo: int = 0, doc_hi: int | None = None) -> torch.Tensor:
     """scores[q][j] = sum over query q's terms of qw * (document doc_lo + j's weight of that term): [Q, doc_hi - doc_lo] float32 plane
     (default: all N documents).  doc_lo a multiple of sparse_slice_docs(), doc_hi one too or N; a range's columns are the full plane's, bit
     for bit."""
     Q = _sparse_queries(qoff, qterms, qw, "sparse_dot")
-    doc_lo, doc_hi = _sparse_range(index, doc_lo, doc_hi, "sparse_dot")
+    doc_lo, doc_hi = _doc_range("sparse_dot", index.N, sparse_slice_docs(), doc_lo, doc_hi)
     if out is None:
         out = alloc_plane(Q, doc_hi - doc_lo, torch.float32, qoff.device)
     else:
@@ -1769,16 +1800,11 @@ def kmeans_centroids(tokens: torch.Tensor, K: int, iters: int = 4, seed: int = 0
 
 
 def centroid_slice_table_bytes(K: int, N: int) -> int:
-    return int(K) * (max(1, -(-int(N) // centroid_slice_docs())) + 1) * 8
+    return int(K) * (_n_slices(N, centroid_slice_docs()) + 1) * 8
 
 
 def centroid_slice_offsets(coff: torch.Tensor, cdoc: torch.Tensor, K: int, N: int) -> torch.Tensor:
-    _need(_dev(coff, torch.int64, "centroid_slice_offsets(coff)").is_contiguous() and coff.numel() == K + 1, f"centroid_slice_offsets: coff must hold {K + 1} offsets")
-    _need(_dev(cdoc, torch.int32, "centroid_slice_offsets(cdoc)").is_contiguous(), "centroid_slice_offsets(cdoc) must be contiguous")
-    NS = max(1, -(-int(N) // centroid_slice_docs()))
-    out = torch.empty((K, NS + 1), dtype=torch.int64, device=coff.device)
-    check(_lib.lib().fz_centroid_slice_offsets(_ptr(coff), _ptr(cdoc), K, int(N), _ptr(out), _stream(coff)), "fz_centroid_slice_offsets")
-    return out
+    return _slice_offsets("centroid", coff, cdoc, K, N)
 
 
 def centroid_index(codes: torch.Tensor, Doff: torch.Tensor, K: int, slice_table_max_bytes: int | None = None) -> CentroidIndex:
@@ -1837,16 +1863,9 @@ def _centroid_args(what: str, index: CentroidIndex, pc, ps, Lq: int, nprobe: int
           f"{what}: pc and ps must be [Q, Lq * nprobe = {Lq * nprobe}]")
     _dev(index.coff, torch.int64, f"{what}(index.coff)"); _dev(index.cdoc, torch.int32, f"{what}(index.cdoc)")
     _need(index.coff.is_contiguous() and index.cdoc.is_contiguous() and index.coff.numel() == index.K + 1, f"{what}: index.coff must hold K + 1 offsets")
-    G = centroid_slice_docs()
     if index.slice_off is not None:
-        NS = max(1, -(-index.N // G))
-        _need(_dev(index.slice_off, torch.int64, f"{what}(index.slice_off)").is_contiguous() and tuple(index.slice_off.shape) == (index.K, NS + 1),
-              f"{what}(index.slice_off): expected a contiguous [{index.K}, {NS + 1}] table (ops.centroid_slice_offsets)")
-    doc_hi = index.N if doc_hi is None else int(doc_hi)
-    doc_lo = int(doc_lo)
-    _need(0 <= doc_lo <= doc_hi <= index.N and doc_lo % G == 0 and (doc_hi % G == 0 or doc_hi == index.N),
-          f"{what}: [doc_lo, doc_hi) = [{doc_lo}, {doc_hi}) must start on a multiple of {G} and end on one or at N = {index.N}")
-    return pc.shape[0], Lq, nprobe, doc_lo, doc_hi
+        _slice_table(what, index.slice_off, index.K, index.N, "centroid")
+    return (pc.shape[0], Lq, nprobe) + _doc_range(what, index.N, centroid_slice_docs(), doc_lo, doc_hi)
 
 
 def centroid_scores(index: CentroidIndex, pc: torch.Tensor, ps: torch.Tensor, Lq: int, nprobe: int, doc_lo: int = 0, doc_hi: int | None = None,
@@ -1872,12 +1891,7 @@ def centroid_filter(index: CentroidIndex, pc, ps, Lq: int, nprobe: int, doc_lo: 
     """fz_centroid_scores_filter_f32 on the buffers of a TopkStream (or a test's own): document d of [doc_lo, doc_hi) enters query q's
     candidates iff !(score <= tau[q]), as (score, id_base + d); cand_s / cand_i [Q, cap], cand_len [Q] int32, overflow [1] int32."""
     Q, Lq, nprobe, doc_lo, doc_hi = _centroid_args("centroid_filter", index, pc, ps, Lq, nprobe, doc_lo, doc_hi)
-    _dev(tau, torch.float32, "centroid_filter(tau)"); _dev(cand_s, torch.float32, "centroid_filter(cand_s)")
-    _dev(cand_i, torch.int64, "centroid_filter(cand_i)"); _dev(cand_len, torch.int32, "centroid_filter(cand_len)")
-    _dev(overflow, torch.int32, "centroid_filter(overflow)")
-    cap = cand_s.shape[1] if cand_s.dim() == 2 else 0
-    _need(cap >= 1 and cand_s.is_contiguous() and cand_i.is_contiguous() and tuple(cand_s.shape) == (Q, cap) and tuple(cand_i.shape) == (Q, cap)
-          and tau.numel() >= Q and cand_len.numel() >= Q and overflow.numel() >= 1, "centroid_filter: tau [Q], cand_s / cand_i [Q, cap >= 1] contiguous, cand_len [Q], overflow [1] expected")
+    cap = _cand_buffers("centroid_filter", torch.float32, Q, tau, cand_s, cand_i, cand_len, overflow)
     check(_lib.lib().fz_centroid_scores_filter_f32(_ptr(index.coff), _ptr(index.cdoc), _ptr(index.slice_off), _ptr(pc), _ptr(ps), Q, Lq, nprobe, index.N,
                                                    index.K, doc_lo, doc_hi, int(id_base), _ptr(tau), _ptr(cand_s), _ptr(cand_i), _ptr(cand_len), cap,
                                                    _ptr(overflow), _stream(pc)), "fz_centroid_scores_filter_f32")

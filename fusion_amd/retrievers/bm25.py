@@ -259,13 +259,12 @@ class TFIDF:
 
     def head_docs(self, k: int) -> int:
         """Leading documents that get the exact top-k: 8,192 at k = 1000, rounded up to whole slices of the walk (10,752 / 14,336)."""
-        return ops.round_up(min(self.HEAD, max(8192, -(-8 * k // 4096) * 4096)), ops.lexical_slice_docs(self.lexical_mode()))
+        return ops.stream_head_docs(k, ops.lexical_slice_docs(self.lexical_mode()), self.HEAD)
 
     def _streams(self, k: int) -> bool:
         if self.lexical_mode() is None or k <= 0:
             return False
-        head = self.head_docs(k)
-        return k + self.CAP <= ops.sort_max_n(torch.float64) and k <= head // 8 and self.corpus_size > head
+        return ops.stream_fits(k, self.CAP, self.head_docs(k), self.corpus_size, torch.float64)
 
     def _topk_device(self, queries: list[str], k: int, budget_bytes: int = DEVICE_BUDGET_BYTES, streaming: bool | None = None, mark=None):
         """search_topk's ([Q, k] float64 scores, [Q, k] int64 ids); mark(name): optional instrumentation hook, called after every launch
@@ -297,26 +296,17 @@ class TFIDF:
         return sc64, (pos + self.id_base if self.id_base else pos)
 
     def _stream_topk(self, queries: list[str], k: int, mark):
-        N, Q = self.corpus_size, len(queries)
-        head = self.head_docs(k)
-        grain = ops.lexical_slice_docs(self.lexical_mode())
-        chunk = max(grain, self.CHUNK // grain * grain)
+        Q = len(queries)
+        head, chunk = self.head_docs(k), ops.stream_chunk(self.CHUNK, ops.lexical_slice_docs(self.lexical_mode()))
         ids = torch.empty((Q, k), dtype=torch.int64, device=self.device)
         sc64 = torch.empty((Q, k), dtype=torch.float64, device=self.device)
         for lo in range(0, Q, self.STREAM_QUERIES):
             block = queries[lo:lo + self.STREAM_QUERIES]
             qoff, flat = self._query_csr(block)
             src = ops._lexical_source(self, qoff, flat, self.id_base)
-            S, base = src.plane(0, head); mark("shard_lexical")
-            pos = self._top_positions(S, k)
-            stream = ops.TopkStream64(torch.gather(S, 1, pos), pos + base, seen=head, cap=self.CAP, top_positions=self._top_positions)
-            del S
-            mark("shard_topk_stream")
-            for c0 in range(head, N, chunk):
-                stream._feed(src, c0, min(N, c0 + chunk), mark)
-            bs, bi, _ = stream.result(); mark("shard_topk_stream")
-            self.last_overflow += stream.windows_redone
-            sc64[lo:lo + len(block)], ids[lo:lo + len(block)] = bs, bi
+            sc64[lo:lo + len(block)], ids[lo:lo + len(block)], redone = ops.stream_search(
+                src, k, head, chunk, self.CAP, "shard_lexical", mark, ops.TopkStream64, top_positions=self._top_positions)
+            self.last_overflow += redone
         return sc64, ids
 
     def _query_step(self, k: int, budget_bytes: int) -> int:

@@ -215,6 +215,33 @@ def test_streamed_equals_plane_route(name, size, corpus, ops, monkeypatch):
             assert_same_lists(got, want, f"{name} N={N} k={k} CAP=256")
 
 
+@pytest.mark.parametrize("name,k", [("BM25", 100), ("TFIDF", 80)])
+def test_streamed_search_launches_one_kernel_per_planned_piece(name, k, corpus, ops):
+    """The marks of a streamed _topk_device are the ones the piece planner predicts (as for the dense and the sparse index): the head's
+    plane and the opening of the stream, one shard_lexical_filter per planned piece with a shard_topk_stream after every planned fold, the
+    closing fold.  Head + three slices + 17 documents in feeds of two slices, one block of queries; CAP = 256 and k make the first window
+    three slices long (128 * head / k rounded down to whole slices: 13,760 -> 10,752 for 'pv', 22,937 -> 21,504 for 'tfidf'), so the
+    second feed starts inside it."""
+    from helpers import planned_search_marks
+    docs, queries = corpus
+    S = ops.lexical_slice_docs("tfidf" if name == "TFIDF" else "pv")
+    head = {"TFIDF": 14_336}.get(name, 10_752)
+    N = head + 3 * S + 17
+    m = make(name, docs[:N])
+    m.CAP, m.CHUNK = 256, 2 * S
+    assert m.head_docs(k) == head and m._streams(k) and len(queries) <= m.STREAM_QUERIES
+    exp, folds, inside = planned_search_marks(ops, head, N, m.CHUNK, k, m.CAP, S, "shard_lexical", "shard_lexical_filter")
+    assert exp.pop() == "allgather_merge"
+    assert folds >= 1 and inside >= 1
+    marks = []
+    got_s, got_i = m._topk_device(queries, k, streaming=True, mark=marks.append)
+    assert m.last_path == "stream" and marks == exp
+    want_s, want_i = m._topk_device(queries, k, streaming=False)
+    assert m.last_path == "plane"
+    np.testing.assert_array_equal(got_i.cpu().numpy(), want_i.cpu().numpy())
+    np.testing.assert_array_equal(bits(got_s), bits(want_s))
+
+
 def test_stream_is_not_taken_where_it_cannot_run(corpus, ops):
     from fusion_amd.retrievers.bm25 import BM25
     docs, queries = corpus

@@ -16,6 +16,7 @@ import torch
 
 import centroid_cases as CC
 import maxsim_cases as M
+from helpers import planned_search_marks
 
 pytestmark = pytest.mark.gpu
 
@@ -262,6 +263,29 @@ def test_three_sub_indexes_merge_to_the_whole(ops, shard, k):
     whole, _, _ = make_index(ops, s["lists"], s["N"])
     one_s, one_i = ShardedCentroidIndex(whole, base).search(*q, k=k)         # one rank: the all-gather merge of a single list
     assert torch.equal(one_i, got_i) and torch.equal(bits(one_s), bits(got_s))
+
+
+def test_streamed_search_launches_one_kernel_per_planned_piece(ops, shard, G):
+    """The marks of a streamed ShardedCentroidIndex.local_topk are the ones the piece planner predicts (as for the dense and the sparse
+    index): the head's plane and the opening of the stream, one shard_centroid_filter per planned piece with a shard_topk_stream after
+    every planned fold, the closing fold.  Head + three slices + 11 documents in feeds of two slices; k = 100 with CAP = 256 makes the
+    first window three slices long (128 * 10,752 / 100, rounded down to whole slices), so the second feed starts inside it."""
+    from fusion_amd.distributed import ShardedCentroidIndex
+    s = shard
+    k, Q, id_base = 100, 3, (1 << 35) + 3
+    index, _, _ = make_index(ops, s["lists"], s["N"])
+    sh = ShardedCentroidIndex(index, id_base)
+    sh.CAP, sh.CHUNK = 256, 2 * G
+    head = sh.head_docs(k)
+    assert head == s["head"] == 3 * G and s["N"] == head + 3 * G + 11 and sh._streams(k, s["N"])
+    exp, folds, inside = planned_search_marks(ops, head, s["N"], sh.CHUNK, k, sh.CAP, G, "shard_centroid", "shard_centroid_filter")
+    assert exp.pop() == "allgather_merge"
+    assert folds >= 1 and inside >= 1
+    marks = []
+    got_s, got_i = sh.local_topk(dev(s["pc"][:Q]), dev(s["ps"][:Q]), s["Lq"], s["nprobe"], k, mark=marks.append, streaming=True)
+    assert marks == exp
+    want_s, want_i = CC.topk_ref(s["ref"][:Q], k, id_base)
+    assert torch.equal(got_i, dev(want_i)) and torch.equal(bits(got_s), bits(dev(want_s)))
 
 
 # ---- 4. assignment -----------------------------------------------------------------------------------------------------------------
