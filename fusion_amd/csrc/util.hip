@@ -1,7 +1,7 @@
 // util.hip -- status strings and small elementwise helpers.
 #include <dlfcn.h>
 
-#include "common.h"
+#include "sort.h"
 
 namespace fz {
 thread_local int g_last_hip_error = 0;
@@ -76,7 +76,7 @@ extern "C" int fz_topk_allgather(const float* local_scores, const int64_t* local
     if (Q < 0 || k <= 0 || world <= 0) return FZ_ERR_ARG;
     if (Q == 0) return FZ_OK;
     if (!local_scores || !local_ids || !out_scores || !out_ids || !rccl_comm) return FZ_ERR_ARG;
-    if ((long)world * k > 35840) return FZ_ERR_UNSUPPORTED;   // one merge row (fz_topk_merge)
+    if ((long)world * k > SORT_ROW_F32) return FZ_ERR_UNSUPPORTED;   // one merge row (fz_topk_merge)
     if (!workspace || workspace_bytes < fz_topk_allgather_workspace_bytes(world, Q, k)) return FZ_ERR_WORKSPACE;
     nccl_allgather_fn ag = find_allgather();
     if (!ag) return FZ_ERR_UNSUPPORTED;                         // no RCCL in the process and no librccl.so to load

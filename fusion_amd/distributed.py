@@ -6,7 +6,7 @@ this on one GPU, one query at a time (1.2 M launches for mMARCO).
 
   * the corpus-embedding matrix is row-sharded over the ranks (one process per GPU, 288 GB HBM each);
   * every rank scores ALL queries against its shard in document chunks: fp32-MFMA GEMM -> per-row top-k
-    (csrc/sort.hip) -> merge into the running top-k -- no host round trip;
+    (csrc/topk.hip) -> merge into the running top-k -- no host round trip;
   * ONE all-gather of the per-shard [Q, k] (score fp32, id int64) lists over RCCL/xGMI (8.2 MB + 8.2 MB per rank at
     Q = 1024, k = 1000: < 1 % of the GEMM time, SURVEY 5) and an identical local G-way merge on every rank;
   * the query ENCODER is data-parallel over the queries: every rank runs the transformer on its 1/G of the batch and the

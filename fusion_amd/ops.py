@@ -363,7 +363,7 @@ def select_topk(fused: torch.Tensor, pos: torch.Tensor | None, k: int, cap: int 
     fused = as_plane(fused)
     Q, N = fused.shape
     _need(k > 0, "select_topk: k must be positive")
-    if N > 28672 or Q == 0:
+    if N > sort_max_n(torch.float64) or Q == 0:
         return None
     if pos is not None:
         _dev(pos, torch.int32, "select_topk(pos)")

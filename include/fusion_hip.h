@@ -298,7 +298,7 @@ size_t fz_insertion_order_workspace_bytes(int Q, int N);
 int fz_insertion_order(const int32_t* const* orders_h, const int32_t* lens, int S, int Q, int N, int ld, int32_t* ins_order,
                        int32_t* U, int32_t* pos, void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- top-k + shard merge: sentence_transformers.py:346-364 (chunked score -> topk -> heap) */
+/* ---- top-k + shard merge (csrc/topk.hip): sentence_transformers.py:346-364 (chunked score -> topk -> heap) */
 /* k best of each row by (score desc, id asc); ids = id_base + column. out [rows][k]; rows with
  * fewer than k columns are padded with (-inf, -1).  k <= fz_topk_max_k(). */
 int fz_topk_max_k(void);

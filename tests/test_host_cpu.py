@@ -136,6 +136,210 @@ def test_workspace_planning_is_consistent():
     assert L.fz_segment_mean_f32(None, 1, None, 1, 768, None, 1, None) == ERR
 
 
+def test_sort_and_topk_return_codes_before_any_hip_call():
+    """The sort and top-k entry points at every argument branch that is decided before a HIP call: the exact code, and which check wins
+    when two fail.  The row capacities (35,840 float32 keys, 28,672 float64 keys) are probed from both sides."""
+    from fusion_amd import _lib
+    L = _lib.lib()
+    OK, ARG, UNS, WS = _lib.FZ_OK, _lib.FZ_ERR_ARG, _lib.FZ_ERR_UNSUPPORTED, _lib.FZ_ERR_WORKSPACE
+    p = C.c_void_p(64)                                             # (never dereferenced: no call below reaches a kernel launch)
+    N32, N64, KMAX = L.fz_sort_max_n(), L.fz_sort_max_n_f64(), L.fz_topk_max_k()
+    assert (N32, N64, KMAX) == (35840, 28672, 8192)
+
+    # fz_sort_workspace_bytes: nothing / one flag per float64 row / the long-row plan past one workgroup's row
+    def long_ws(bits, rows, n):
+        return rows * n * (bits // 8 + 4) * 2 + rows * -(-n // (N32 if bits == 32 else N64)) * 4 + 512
+    assert L.fz_sort_workspace_bytes(32, 0, 5) == 0 and L.fz_sort_workspace_bytes(64, 5, 0) == 0
+    assert L.fz_sort_workspace_bytes(32, 3, N32) == 0 and L.fz_sort_workspace_bytes(64, 3, N64) == 12
+    assert L.fz_sort_workspace_bytes(32, 3, N32 + 1) == long_ws(32, 3, N32 + 1)
+    assert L.fz_sort_workspace_bytes(64, 3, N64 + 1) == long_ws(64, 3, N64 + 1)
+    assert L.fz_sort_workspace_bytes(64, 2, 120000) == long_ws(64, 2, 120000)
+
+    # fz_sort_rows_desc(keys, key_bits, init_order, row_len, rows, n, ld, order, sorted_keys, rank, row_stats, stats_len, ws, ws_bytes, stream)
+    f = L.fz_sort_rows_desc
+    assert f(p, 16, None, None, 1, 4, 4, p, p, p, None, None, p, 64, None) == ARG
+    assert f(p, 32, None, None, -1, 4, 4, p, p, p, None, None, p, 64, None) == ARG
+    assert f(p, 32, None, None, 1, -1, 4, p, p, p, None, None, p, 64, None) == ARG
+    assert f(p, 32, None, None, 1, 5, 4, p, p, p, None, None, p, 64, None) == ARG               # ld < n
+    assert f(None, 16, None, None, 0, 4, 4, None, None, None, None, None, None, 0, None) == ARG  # key_bits before "nothing to do"
+    assert f(None, 64, None, None, 0, 4, 4, None, None, None, None, None, None, 0, None) == OK
+    assert f(None, 32, None, None, 3, 0, 0, None, None, None, None, None, None, 0, None) == OK
+    assert f(None, 32, None, None, 1, 4, 4, p, p, p, None, None, None, 0, None) == ARG           # no keys
+    assert f(p, 32, None, None, 1, 4, 4, p, p, p, None, p, None, 0, None) == ARG                 # stats_len without row_stats
+    assert f(p, 64, None, None, 1, 4, 4, p, p, p, p, p, None, 0, None) == UNS                    # stats_len with 64-bit keys (before the workspace)
+    assert f(p, 32, None, None, 1, N32 + 1, N32 + 1, p, p, p, p, None, None, 0, None) == UNS     # row_stats on a long row (before the workspace)
+    assert f(p, 64, None, None, 1, N64 + 1, N64 + 1, p, p, p, p, None, None, 0, None) == UNS
+    for bits, n in ((32, N32 + 1), (64, N64 + 1)):                                               # long rows: the chunk-sort workspace
+        assert f(p, bits, None, None, 2, n, n, p, p, p, None, None, None, 1 << 40, None) == WS
+        assert f(p, bits, None, None, 2, n, n, p, p, p, None, None, p, long_ws(bits, 2, n) - 1, None) == WS
+    for n in (4, N64):                                                                           # float64 rows of one workgroup: the row flags
+        assert f(p, 64, None, None, 3, n, n, p, p, p, None, None, None, 64, None) == WS
+        assert f(p, 64, None, None, 3, n, n, p, p, p, None, None, p, 11, None) == WS
+
+    # fz_sort_rows_desc_lexical(keys, row_len, rows, n, ld, order, sorted_keys, rank, row_stats, ws, ws_bytes, stream)
+    f = L.fz_sort_rows_desc_lexical
+    assert f(p, None, -1, 4, 4, p, p, p, None, p, 64, None) == ARG
+    assert f(p, None, 1, -1, 4, p, p, p, None, p, 64, None) == ARG
+    assert f(p, None, 1, 5, 4, p, p, p, None, p, 64, None) == ARG
+    assert f(None, None, 0, 20000, 20000, None, None, None, None, None, 0, None) == OK
+    assert f(None, None, 2, 0, 0, None, None, None, None, None, 0, None) == OK
+    assert f(None, None, 1, 20000, 20000, p, p, p, None, p, 64, None) == ARG
+    for n in (8192, 8193, 20000, N64):                             # its own rows (8,193 .. 28,672) and the ones it hands on: the row flags
+        assert f(p, None, 3, n, n, p, p, p, None, None, 64, None) == WS
+        assert f(p, None, 3, n, n, p, p, p, p, p, 11, None) == WS
+    assert f(p, None, 1, N64 + 1, N64 + 1, p, p, p, p, p, 1 << 40, None) == UNS                  # handed to fz_sort_rows_desc: long row with row_stats
+    assert f(p, None, 1, N64 + 1, N64 + 1, p, p, p, None, None, 0, None) == WS
+    assert f(p, None, 1, N64 + 1, N64 + 1, p, p, p, None, p, long_ws(64, 1, N64 + 1) - 1, None) == WS
+
+    # fz_sort_rows_desc_placed(keys, key_bits, init_rank, row_len, rows, n, ld, order, sorted_keys, rank, ws, ws_bytes, stream)
+    f = L.fz_sort_rows_desc_placed
+    assert f(p, 16, p, None, 1, 4, 4, p, p, p, p, 64, None) == ARG
+    assert f(p, 32, p, None, -1, 4, 4, p, p, p, p, 64, None) == ARG
+    assert f(p, 32, p, None, 1, -1, 4, p, p, p, p, 64, None) == ARG
+    assert f(p, 32, p, None, 1, 5, 4, p, p, p, p, 64, None) == ARG
+    assert f(None, 64, None, None, 0, 4, 4, None, None, None, None, 0, None) == OK
+    assert f(None, 32, None, None, 2, 0, 0, None, None, None, None, 0, None) == OK
+    assert f(None, 32, p, None, 1, 4, 4, p, p, p, p, 64, None) == ARG
+    assert f(p, 32, None, None, 1, 4, 4, p, p, p, p, 64, None) == ARG                            # no init_rank
+    for bits, n in ((32, N32 + 1), (64, N64 + 1)):
+        assert f(p, bits, p, None, 2, n, n, p, p, p, None, 1 << 40, None) == WS
+        assert f(p, bits, p, None, 2, n, n, p, p, p, p, long_ws(bits, 2, n) - 1, None) == WS
+    for n in (4, N64):
+        assert f(p, 64, p, None, 3, n, n, p, p, p, None, 64, None) == WS
+        assert f(p, 64, p, None, 3, n, n, p, p, p, p, 11, None) == WS
+
+    # fz_sort_rank_fused_desc(ranks, lens, S, method, init_order, init_rank, row_len, rows, n, ld, order, sorted_scores, rank, ws, ws_bytes, stream)
+    f = L.fz_sort_rank_fused_desc
+    planes = (C.c_void_p * 2)(64, 64)                              # a real host array of (never dereferenced) plane pointers
+    holed = (C.c_void_p * 2)(64, None)
+    assert f(planes, p, 0, 0, None, None, None, 1, 4, 4, p, p, p, p, 1 << 40, None) == ARG
+    assert f(planes, p, 9, 0, None, None, None, 1, 4, 4, p, p, p, p, 1 << 40, None) == ARG
+    assert f(planes, p, 2, 0, None, None, None, -1, 4, 4, p, p, p, p, 1 << 40, None) == ARG
+    assert f(planes, p, 2, 0, None, None, None, 1, -1, 4, p, p, p, p, 1 << 40, None) == ARG
+    assert f(planes, p, 2, 0, None, None, None, 1, 5, 4, p, p, p, p, 1 << 40, None) == ARG
+    assert f(planes, p, 2, 7, None, None, None, 1, 4, 4, p, p, p, p, 1 << 40, None) == ARG       # method
+    assert f(planes, p, 2, 0, p, p, None, 1, 4, 4, p, p, p, p, 1 << 40, None) == ARG             # both sequences
+    assert f(None, None, 2, 7, None, None, None, 0, 4, 4, None, None, None, None, 0, None) == ARG  # method before "nothing to do"
+    assert f(None, None, 2, 0, None, None, None, 0, 4, 4, None, None, None, None, 0, None) == OK
+    assert f(None, None, 2, 1, None, None, None, 2, 0, 0, None, None, None, None, 0, None) == OK
+    assert f(None, p, 2, 0, None, None, None, 1, 4, 4, p, p, p, p, 1 << 40, None) == ARG
+    assert f(planes, None, 2, 0, None, None, None, 1, 4, 4, p, p, p, p, 1 << 40, None) == ARG
+    assert f(holed, p, 2, 0, None, None, None, 1, N64 + 1, N64 + 1, p, p, p, p, 1 << 40, None) == UNS   # the row limit before the planes are read
+    assert f(planes, p, 2, 1, None, None, None, 1, N64 + 1, N64 + 1, p, p, p, None, 0, None) == UNS
+    assert f(holed, p, 2, 0, None, None, None, 1, N64, N64, p, p, p, None, 0, None) == ARG       # a null plane before the workspace
+    for n in (4, N64):
+        assert f(planes, p, 2, 0, None, None, None, 3, n, n, p, p, p, None, 1 << 40, None) == WS
+        assert f(planes, p, 2, 1, None, p, None, 3, n, n, p, p, p, p, 256 + 3 * n * 8 - 1, None) == WS
+    assert L.fz_sort_rank_fused_workspace_bytes(3, N64, N64) == 256 + 3 * N64 * 8
+
+    # fz_select_topk_f(fused, key_bits, pos, rows, n, ld, k, cap, cand_cols, cand_vals, cand_negpos, cand_len, overflow, stream)
+    f = L.fz_select_topk_f
+    assert f(p, 16, None, 1, 8, 8, 2, 4, p, p, p, p, p, None) == ARG
+    assert f(p, 32, None, -1, 8, 8, 2, 4, p, p, p, p, p, None) == ARG
+    assert f(p, 32, None, 1, -1, 8, 2, 4, p, p, p, p, p, None) == ARG
+    assert f(p, 32, None, 1, 9, 8, 2, 4, p, p, p, p, p, None) == ARG
+    assert f(p, 32, None, 1, 8, 8, 0, 4, p, p, p, p, p, None) == ARG
+    assert f(p, 32, None, 1, 8, 8, 5, 4, p, p, p, p, p, None) == ARG                             # cap < k
+    assert f(None, 64, None, 0, 8, 8, 2, 4, None, None, None, None, None, None) == OK
+    assert f(p, 32, None, 1, 8, 8, 2, 4, p, p, p, None, p, None) == ARG
+    assert f(p, 32, None, 1, 8, 8, 2, 4, p, p, p, p, None, None) == ARG
+    assert f(None, 32, None, 1, 8, 8, 2, 4, p, p, p, p, p, None) == ARG
+    assert f(p, 64, None, 1, 8, 8, 2, 4, None, p, p, p, p, None) == ARG
+    assert f(None, 32, None, 1, N64 + 1, N64 + 1, 2, 4, p, p, p, p, p, None) == ARG              # null planes before the row limit
+    for bits in (32, 64):
+        assert f(p, bits, None, 1, N64 + 1, N64 + 1, 1000, 2000, p, p, p, p, p, None) == UNS
+
+    # fz_topk_workspace_bytes: one sort row needs none; longer rows one (score, column) pair per survivor of every chunk-sort level
+    assert L.fz_topk_workspace_bytes(0, 100, 10) == 0 and L.fz_topk_workspace_bytes(1, 0, 10) == 0 and L.fz_topk_workspace_bytes(1, 100, 0) == 0
+    assert L.fz_topk_workspace_bytes(4, N32, 10) == 256
+    assert L.fz_topk_workspace_bytes(4, N32 + 1, 10) == 4 * 20 * 8 + 256                          # 2 chunks of 28,672 x 10 survivors
+    assert L.fz_topk_workspace_bytes(2, N32 + 1, KMAX) == 2 * 2 * KMAX * 8 + 256
+    assert L.fz_topk_workspace_bytes(3, 1105228, 1000) == 3 * (39000 + 2000) * 8 + 256            # 39 chunks -> 39,000 > 35,840 -> 2 chunks
+    assert L.fz_topk_workspace_bytes(1, 2 * N64 + 1, 1000) == 3000 * 8 + 256                      # the chunk is 28,672 wide: 3 of them
+
+    # fz_topk_rows_f32(scores, rows, n, ld, k, id_base, out_scores, out_ids, ws, ws_bytes, stream)
+    f = L.fz_topk_rows_f32
+    assert f(p, -1, 8, 8, 2, 0, p, p, None, 0, None) == ARG
+    assert f(p, 1, -1, 8, 2, 0, p, p, None, 0, None) == ARG
+    assert f(p, 1, 9, 8, 2, 0, p, p, None, 0, None) == ARG
+    assert f(p, 1, 8, 8, 0, 0, p, p, None, 0, None) == ARG
+    assert f(None, 0, 8, 8, KMAX + 1, 0, None, None, None, 0, None) == UNS                       # k before "nothing to do" and the null checks
+    assert f(None, 0, 8, 8, KMAX, 0, None, None, None, 0, None) == OK
+    assert f(p, 1, 8, 8, 2, 0, None, p, None, 0, None) == ARG
+    assert f(p, 1, 8, 8, 2, 0, p, None, None, 0, None) == ARG
+    assert f(None, 1, 8, 8, 2, 0, p, p, None, 0, None) == ARG
+    assert f(p, 2, N32 + 1, N32 + 1, 10, 0, p, p, None, 0, None) == WS
+    assert f(p, 2, N32 + 1, N32 + 1, 10, 0, p, p, p, 2 * 20 * 8 + 255, None) == WS
+    assert f(p, 2, N32 + 1, N32 + 1, 10, 0, p, p, None, 1 << 40, None) == WS                     # bytes promised, no workspace
+
+    # fz_topk_update_f32(scores, rows, n, ld, id_base, run_scores, run_ids, k, cap, new_scores, new_ids, overflow, ws, ws_bytes, stream)
+    def upd_ws(rows, k, cap):
+        return rows * (k + cap) * 12 + rows * 4 + 256
+    assert L.fz_topk_update_workspace_bytes(0, 10, 64) == 0 and L.fz_topk_update_workspace_bytes(2, 0, 64) == 0 and L.fz_topk_update_workspace_bytes(2, 10, 0) == 0
+    assert L.fz_topk_update_workspace_bytes(5, 1000, 7168) == upd_ws(5, 1000, 7168)
+    f = L.fz_topk_update_f32
+    assert f(p, -1, 8, 8, 0, p, p, 10, 64, p, p, p, p, 1 << 40, None) == ARG
+    assert f(p, 1, -1, 8, 0, p, p, 10, 64, p, p, p, p, 1 << 40, None) == ARG
+    assert f(p, 1, 9, 8, 0, p, p, 10, 64, p, p, p, p, 1 << 40, None) == ARG
+    assert f(p, 1, 8, 8, 0, p, p, 0, 64, p, p, p, p, 1 << 40, None) == ARG
+    assert f(p, 1, 8, 8, 0, p, p, 10, 0, p, p, p, p, 1 << 40, None) == ARG
+    assert f(None, 0, 8, 8, 0, None, None, 1000, N32 + 1 - 1000, None, None, None, None, 0, None) == UNS   # k + cap before "nothing to do"
+    assert f(None, 0, 8, 8, 0, None, None, 1000, N32 - 1000, None, None, None, None, 0, None) == OK
+    assert f(p, 1, 8, 8, 0, p, p, 1000, N32 + 1 - 1000, p, p, p, p, 1 << 40, None) == UNS
+    for hole in range(5):                                          # run_scores, run_ids, new_scores, new_ids, overflow
+        a = [p] * 5; a[hole] = None
+        assert f(p, 1, 8, 8, 0, a[0], a[1], 10, 64, a[2], a[3], a[4], p, 1 << 40, None) == ARG
+    assert f(None, 1, 8, 8, 0, p, p, 10, 64, p, p, p, p, 1 << 40, None) == ARG                   # no scores, n > 0
+    assert f(p, 2, 8, 8, 0, p, p, 1000, N32 - 1000, p, p, p, None, 1 << 40, None) == WS
+    assert f(p, 2, 8, 8, 0, p, p, 1000, N32 - 1000, p, p, p, p, upd_ws(2, 1000, N32 - 1000) - 1, None) == WS
+
+    # fz_topk_filter_append_f32(scores, rows, n, ld, id_base, tau, cand_scores, cand_ids, cand_len, cap, overflow, stream)
+    f = L.fz_topk_filter_append_f32
+    assert f(p, -1, 8, 8, 0, p, p, p, p, 64, p, None) == ARG
+    assert f(p, 1, -1, 8, 0, p, p, p, p, 64, p, None) == ARG
+    assert f(p, 1, 9, 8, 0, p, p, p, p, 64, p, None) == ARG
+    assert f(p, 1, 8, 8, 0, p, p, p, p, 0, p, None) == ARG
+    assert f(None, 0, 8, 8, 0, None, None, None, None, 64, None, None) == OK
+    assert f(None, 3, 0, 0, 0, None, None, None, None, 64, None, None) == OK
+    for hole in range(6):                                          # scores, tau, cand_scores, cand_ids, cand_len, overflow
+        a = [p] * 6; a[hole] = None
+        assert f(a[0], 1, 8, 8, 0, a[1], a[2], a[3], a[4], 64, a[5], None) == ARG
+
+    # fz_topk_fold_f32(run_scores, run_ids, rows, k, cand_scores, cand_ids, cand_len, cap, unordered, new_scores, new_ids, tau, overflow, ws, ws_bytes, stream)
+    def fold_ws(rows, k, cap):
+        return upd_ws(rows, k, cap) + rows * (k + 64) * 12 + 256
+    assert L.fz_topk_fold_workspace_bytes(0, 10, 64) == 0 and L.fz_topk_fold_workspace_bytes(2, 0, 64) == 0 and L.fz_topk_fold_workspace_bytes(2, 10, 0) == 0
+    assert L.fz_topk_fold_workspace_bytes(5, 1000, 7168) == fold_ws(5, 1000, 7168)
+    f = L.fz_topk_fold_f32
+    assert f(p, p, -1, 10, p, p, p, 64, 0, p, p, p, p, p, 1 << 40, None) == ARG
+    assert f(p, p, 1, 0, p, p, p, 64, 0, p, p, p, p, p, 1 << 40, None) == ARG
+    assert f(p, p, 1, 10, p, p, p, 0, 0, p, p, p, p, p, 1 << 40, None) == ARG
+    assert f(None, None, 0, 1000, None, None, None, N32 + 1 - 1000, 0, None, None, None, None, None, 0, None) == UNS
+    assert f(None, None, 0, 1000, None, None, None, N32 - 1000, 0, None, None, None, None, None, 0, None) == OK
+    assert f(p, p, 1, 1000, p, p, p, N32 + 1 - 1000, 1, p, p, p, p, p, 1 << 40, None) == UNS
+    for hole in range(7):                                          # run_scores, run_ids, cand_scores, cand_ids, cand_len, new_scores, new_ids
+        a = [p] * 7; a[hole] = None
+        assert f(a[0], a[1], 1, 10, a[2], a[3], a[4], 64, 0, a[5], a[6], p, p, p, 1 << 40, None) == ARG
+    assert f(p, p, 1, 10, p, p, p, 64, 1, p, p, p, None, p, 1 << 40, None) == ARG                # arrival order without an overflow flag
+    assert f(p, p, 2, 10, p, p, p, 64, 0, p, p, None, None, None, 1 << 40, None) == WS           # (tau and overflow are optional here)
+    assert f(p, p, 2, 1000, p, p, p, N32 - 1000, 1, p, p, p, p, p, fold_ws(2, 1000, N32 - 1000) - 1, None) == WS
+
+    # fz_topk_merge(in_scores, in_ids, G, rows, k, out_scores, out_ids, stream); 35,841 = 3 x 11,947
+    f = L.fz_topk_merge
+    assert f(p, p, 0, 1, 10, p, p, None) == ARG
+    assert f(p, p, 2, -1, 10, p, p, None) == ARG
+    assert f(p, p, 2, 1, 0, p, p, None) == ARG
+    for hole in range(4):
+        a = [p] * 4; a[hole] = None
+        assert f(a[0], a[1], 3, 1, 11947, a[2], a[3], None) == ARG                               # null lists before the row limit
+    assert f(p, p, 3, 1, 11947, p, p, None) == UNS
+    assert f(None, None, 3, 0, 11947, None, None, None) == UNS                                   # the row limit before "nothing to do"
+    assert f(None, None, 2, 0, N32 // 2, None, None, None) == OK
+    # its caller across ranks: fz_topk_allgather(local_scores, local_ids, Q, k, comm, world, out_scores, out_ids, ws, ws_bytes, stream)
+    assert L.fz_topk_allgather(p, p, 1, 11947, p, 3, p, p, p, 1 << 40, None) == UNS
+    assert L.fz_topk_allgather(p, p, 1, N32 // 2, p, 2, p, p, None, 1 << 40, None) == WS
+
+
 def test_integration_md_binding_matches_the_abi():
     """INTEGRATION.md's reference-side binding is executable documentation: its argtypes must be the binding table's
     (fusion_amd/_lib.py == include/fusion_hip.h) and every call in it must pass exactly that many arguments -- round 2's

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Ablation builds of sort.hip (diagnostics only).  Usage (build container): python tools/ablate/sort_variants.py
 Then on the GPU box: python tools/sort_pass_cost.py fusion_amd/libfusion_hip.so tools/ablate/libfusion_abl_sort_<name>.so"""
-import os, subprocess, sys
+import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CSRC = os.path.join(ROOT, "fusion_amd", "csrc")
 SRC = open(os.path.join(CSRC, "sort.hip")).read()
@@ -22,8 +22,14 @@ VARIANTS = {
 }
 
 
+def shipped_objects(replaced):
+    """The built objects of every source in the Makefile's SRCS except the one this build replaces."""
+    srcs = re.search(r"^SRCS := (.*)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).split()
+    return [os.path.join(CSRC, f[:-len(".hip")] + ".o") for f in srcs if f != replaced]
+
+
 def main():
-    objs = [os.path.join(CSRC, f) for f in "util.o fuse.o tables.o score.o maxsim.o bm25.o sparse.o tune.o encoder.o".split()]
+    objs = shipped_objects("sort.hip")
     for name, patches in VARIANTS.items():
         s = SRC
         for a, b in patches:

@@ -2,7 +2,7 @@
 """Ablation builds of tables.hip (diagnostics only; wrong results by design): each variant is a textual patch of the shipped source
 compiled into tools/ablate/libfusion_abl_<name>.so.  Usage (build container): python tools/ablate/tables_variants.py
 Then on the GPU box: python tools/run_tables_ab.py"""
-import os, subprocess, sys
+import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CSRC = os.path.join(ROOT, "fusion_amd", "csrc")
 SRC = open(os.path.join(CSRC, "tables.hip")).read()
@@ -32,9 +32,15 @@ VARIANTS = {
 }
 
 
+def shipped_objects(replaced):
+    """The built objects of every source in the Makefile's SRCS except the one this build replaces."""
+    srcs = re.search(r"^SRCS := (.*)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).split()
+    return [os.path.join(CSRC, f[:-len(".hip")] + ".o") for f in srcs if f != replaced]
+
+
 def main():
     os.makedirs(os.path.join(ROOT, "tools", "ablate"), exist_ok=True)
-    objs = [os.path.join(CSRC, f) for f in "util.o fuse.o sort.o score.o maxsim.o bm25.o sparse.o tune.o encoder.o".split()]
+    objs = shipped_objects("tables.hip")
     for name, patches in VARIANTS.items():
         if len(sys.argv) > 1 and name not in sys.argv[1:]:
             continue
