@@ -6,6 +6,8 @@
 //   fz_normalize_rows_f32   Y = X / max(||X||, 1e-12), one wave per row, fp64 norm
 //   fz_dot_scores_f32       S = Qn . Dn^T with v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulate:
 //                           the 1e-4 score contract rules out bf16/fp16 inputs, SURVEY 7 "hard parts")
+//   fz_dot_scores_filter_f32 / fz_splade_head_max_f32 / fz_dot_topn_f32
+//                           the same tile stream with an epilogue that writes no plane: threshold filter, segment max, per-row top-n
 //
 // GEMM structure: 128x128 output tile per 256-thread workgroup (2x2 waves, each 64x64 = 2x2 MFMA tiles, 64 accumulator
 // VGPRs), K-step 32, both operands K-contiguous ("NT").  The grid is persistent (two workgroups per CU) and each workgroup
@@ -86,9 +88,15 @@ struct GemmArgs {
     const int32_t* cu_rows;    // [nseq + 1] first packed row of every sequence
     int nseq;
     float* pool; int ldp;      // [nseq][ldp] zero-initialised: pool[s][v] = max over the sequence's rows of log1p(relu(logit))
+    // TOPN form (fz_dot_topn_f32): A = the centroids [K][lda] (Q = K), B = the token rows [rows][ldb] (N = rows) -- the product is S^T, a lane
+    // holds ONE token per MFMA column block and that token's centroids in its own accumulator registers; no plane
+    int tn_n, tn_per;          // entries per list (<= TOPN_CAP); 128-centroid blocks per centroid group
+    float* tn_s;               // [4 * groups][N][tn_n] partial lists, one per (centroid group, wave row, lane half) and token,
+    int32_t* tn_i;             //   in (score desc, id asc) order, (-inf, -1) padding
 };
 
-enum { EPI_STORE = 0, EPI_FILTER = 1, EPI_SPLADE = 2 };
+enum { EPI_STORE = 0, EPI_FILTER = 1, EPI_SPLADE = 2, EPI_TOPN = 3 };
+constexpr int TOPN_CAP = 8;    // fz_dot_topn_max(): 2 tokens x 8 (score, id) pairs per lane are carried through the whole tile stream
 
 // One workgroup's share of the tiles: ids first, first + step, ... below `end`, all of one shape (128 x BN).  The k-tiles of
 // ALL those tiles form one stream through the software pipeline: the operand loads of a tile's first two k-tiles are issued
@@ -96,7 +104,8 @@ enum { EPI_STORE = 0, EPI_FILTER = 1, EPI_SPLADE = 2 };
 // pays the pipeline fill once per launch, not once per tile.
 template <int BN, int MI /* 32-row MFMA blocks per wave */, int WN /* waves along the corpus side: 2 (2 x 2 waves) or 4 (1 x 4) */, bool RAGGED /* d is not a whole number of k-tile pairs */, int EPI,
           bool FLAT = false /* tile id b = corpus columns [b BN, (b + 1) BN) of the row band at row_origin (the 7-row-block cover) */,
-          int NSLAB = 0 /* the batch's last 1..8 rows ride along as NSLAB 4-row slabs on v_mfma_f32_4x4x1_16b_f32 (64-row tail tiles only) */>
+          int NSLAB = 0 /* the batch's last 1..8 rows ride along as NSLAB 4-row slabs on v_mfma_f32_4x4x1_16b_f32 (64-row tail tiles only) */,
+          bool WALK = false /* FLAT with the sides exchanged: tile id b = query rows [b BMT, (b + 1) BMT) of the corpus columns at row_origin (EPI_TOPN) */>
 __device__ __forceinline__ void gemm_stream(const GemmArgs& g, float* lds, int first, const int end, const int step, const int qblocks, const int row_origin) {
     constexpr int WM = 4 / WN;           // waves along the query side
     constexpr int BMT = 32 * MI * WM;    // tile height: 128 (whole query blocks: 2 x 2 waves, MI = 2), 64 (MI = 1) or 32 (1 x 4 waves, MI = 1)
@@ -118,11 +127,20 @@ __device__ __forceinline__ void gemm_stream(const GemmArgs& g, float* lds, int f
     // [stage][A: 128 rows | B: BN rows | straggler rows][LDT]
     constexpr int BUF = (BMT + BN + SROWS) * LDT;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wr = w / WN, wc = w % WN;
+    // (EPI_TOPN carries 32 registers of lists through the stream: its wave coordinates are scalars, and its epilogue takes the lane number
+    // afresh instead of keeping registers derived from it alive across the k-loops)
+    const int ws = EPI == EPI_TOPN ? __builtin_amdgcn_readfirstlane(w) : w;
+    const int wr = ws / WN, wc = ws % WN;
+    [[maybe_unused]] auto fresh_lane = [] {
+        int l;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+        return l;
+    };
 
     // tile id -> (query row, corpus column) of its corner; ids of the XCD padding decode to nothing
     auto decode = [&](int b, int& row0, int& col0) -> bool {
         if constexpr (FLAT) { row0 = row_origin; col0 = b * BN; return col0 < g.N; }
+        if constexpr (WALK) { row0 = b * BMT; col0 = row_origin; return row0 < g.Q; }
         int half = 0;
         if (BN == 64) {   // workgroup i of the half-tile round: tile (i/16)*8 + i%8 (same XCD as i), half (i/8)%2
             const int h = b - g.full;
@@ -284,6 +302,25 @@ __device__ __forceinline__ void gemm_stream(const GemmArgs& g, float* lds, int f
         fmma(f1);
     };
 
+    // EPI_TOPN: the running lists of this lane's NI tokens, carried across all the tiles of the walk.  TOPN_CAP slots per token, best first;
+    // a list of n < TOPN_CAP entries lives in the LAST n slots behind +inf blockers, which no score displaces (nothing is > +inf, and a tie
+    // goes behind): the n-th best is always slot TOPN_CAP - 1 and the insertion is one fixed sink through the slots for every n.  An empty slot is
+    // (NaN, -1): `!(s <= NaN)` holds for every s, so whatever comes first fills the list.
+    static_assert(EPI != EPI_TOPN || (WALK && BN == 128 && MI == 2 && WN == 2 && !SLAB), "the top-n epilogue runs on whole 128 x 128 tiles of 2 x 2 waves");
+    constexpr int TL = EPI == EPI_TOPN ? TOPN_CAP : 1;
+    [[maybe_unused]] float tl_s[NI][TL];
+    [[maybe_unused]] int32_t tl_i[NI][TL];
+    if constexpr (EPI == EPI_TOPN) {
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+            for (int j = 0; j < TL; ++j) {
+                const bool blocker = j < TL - g.tn_n;
+                tl_s[ni][j] = blocker ? INFINITY : __uint_as_float(0x7fc00000u);
+                tl_i[ni][j] = blocker ? -2 : -1;
+            }
+    }
+
     constexpr std::true_type EDGE{};
     constexpr std::false_type PLAIN{};
     point_at(crow, ccol);
@@ -392,6 +429,50 @@ __device__ __forceinline__ void gemm_stream(const GemmArgs& g, float* lds, int f
             if (ccol + BN <= g.N && crow + BMT <= g.Q) passes(std::false_type{});   // workgroup-uniform
             else passes(std::true_type{});
             if (over) atomicExch(g.overflow, 1);
+        } else if constexpr (EPI == EPI_TOPN) {
+            // Top-n selection in the epilogue.  The lane's token (one per ni) meets 32 centroids of this tile in the lane's own registers, in
+            // ascending id order (mi, then r), and the walk visits the tiles in ascending id order: a score enters the token's list iff it is
+            // GREATER than the list's last entry -- a tie has the larger id and loses -- and goes behind every entry it does not beat.  After
+            // the first tiles that is rare: 16 scores are first tested by their maximum, one ballot per (ni, mi); only where some lane's
+            // maximum beats its list are the 16 looked at one by one, and only where one beats does the wave run the sink.  Compared as floats: for
+            // the finite scores of the contract (an fma chain from +0.0 never gives -0.0) that is the order of desc_key_f32; a NaN would enter first.
+            const int el = fresh_lane();
+            const int cw = crow + wr * (32 * MI) + 4 * (el >> 5);       // + mi*32 + (r&3) + 8*(r>>2): the centroid
+            const int tw = ccol + wc * (BN / WN) + (el & 31);           // + ni*32: the token
+            auto passes = [&](auto edge) __attribute__((always_inline)) {
+#pragma unroll
+                for (int ni = 0; ni < NI; ++ni) {
+                    [[maybe_unused]] const bool tok = tw + ni * 32 < g.N;
+#pragma unroll
+                    for (int mi = 0; mi < MI; ++mi) {
+                        if constexpr (!decltype(edge)::value) {
+                            float m = acc[mi][ni][0];
+#pragma unroll
+                            for (int r = 1; r < 16; ++r) m = fmaxf(m, acc[mi][ni][r]);
+                            if (__ballot(!(m <= tl_s[ni][TL - 1])) == 0ull) continue;     // wave-uniform
+                        }
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const float s = acc[mi][ni][r];
+                            const int c = cw + mi * 32 + (r & 3) + 8 * (r >> 2);
+                            bool beats = !(s <= tl_s[ni][TL - 1]);
+                            if constexpr (decltype(edge)::value) beats = beats && tok && c < g.Q;
+                            if (__ballot(beats) == 0ull) continue;                         // wave-uniform
+                            // s sinks to its place: from the first entry it beats on, every entry moves one slot down
+                            float cs = s; int32_t ci = c; bool sw = false;
+#pragma unroll
+                            for (int j = 0; j < TL; ++j) {
+                                sw = sw || (beats && !(cs <= tl_s[ni][j]));
+                                const float ts = tl_s[ni][j]; const int32_t ti = tl_i[ni][j];
+                                tl_s[ni][j] = sw ? cs : ts; tl_i[ni][j] = sw ? ci : ti;
+                                cs = sw ? ts : cs; ci = sw ? ti : ci;
+                            }
+                        }
+                    }
+                }
+            };
+            if (ccol + BN <= g.N && crow + BMT <= g.Q) passes(std::false_type{});   // workgroup-uniform
+            else passes(std::true_type{});
         } else if constexpr (EPI == EPI_SPLADE) {
             // SPLADE-max pooling as the epilogue of the vocabulary projection (splade/splade.py:88-99: amax over the tokens of
             // log1p(relu(logits))): the [T, V] logits are never written.  log1p o relu is monotone, so the max over a sequence's rows is
@@ -470,6 +551,24 @@ __device__ __forceinline__ void gemm_stream(const GemmArgs& g, float* lds, int f
         if (nxt < 0) break;
         cur_b = nxt; crow = lrow; ccol = lcol;
     }
+    if constexpr (EPI == EPI_TOPN) {
+        // the lists leave the registers once, at the end of the walk: list (group, wave row, lane half) of every token of the tile
+        const int el = fresh_lane();
+        const size_t list = (size_t)((first / g.tn_per) * 2 + wr) * 2 + (el >> 5);
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) {
+            const int t = row_origin + wc * (BN / WN) + ni * 32 + (el & 31);
+            if (t < g.N) {
+                float* os = g.tn_s + (list * g.N + t) * g.tn_n;
+                int32_t* oi = g.tn_i + (list * g.N + t) * g.tn_n;
+#pragma unroll
+                for (int j = 0; j < TL; ++j) {
+                    const int p = j - (TL - g.tn_n);
+                    if (p >= 0) { os[p] = tl_i[ni][j] < 0 ? -INFINITY : tl_s[ni][j]; oi[p] = tl_i[ni][j]; }
+                }
+            }
+        }
+    }
 }
 
 // Workgroup -> tile map.  The grid is PERSISTENT: two workgroups per CU (LDS-bound), workgroup i takes tile ids i, i + grid, ...
@@ -522,6 +621,52 @@ __global__ __launch_bounds__(256, 1) void dot_scores_cover7_kernel(GemmArgs g, i
     const int b = (int)blockIdx.x;
     if (b < nP) gemm_stream<192, 2, 2, RAGGED, EPI_STORE, true>(g, lds, b, b + 1, 1, 1, 0);
     else gemm_stream<256, 3, 4, RAGGED, EPI_STORE, true>(g, lds, b - nP, b - nP + 1, 1, 1, 128);
+}
+
+// fz_dot_topn_f32: workgroup (t, gi) takes the 128 token rows of tile t and walks the 128-centroid blocks of group gi for them.
+template <bool RAGGED>
+__global__ __launch_bounds__(256, 2) void dot_topn_kernel(GemmArgs g, int TT) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int t = (int)blockIdx.x % TT, b0 = ((int)blockIdx.x / TT) * g.tn_per;
+    gemm_stream<128, 2, 2, RAGGED, EPI_TOPN, false, 0, true>(g, lds, b0, min((g.Q + BM - 1) / BM, b0 + g.tn_per), 1, 1, t * 128);
+}
+
+// The `lists` partial lists of a token -> its n best, one wave per token.  Every lane folds the lists lane, lane + 64, ... into a sorted list
+// of its own -- 64-bit keys (desc_key_f32(score), id), smaller = better, all ones = padding -- then n rounds of a wave-wide minimum pop the
+// winners.  (score, id) is a total order and the ids of a token are distinct: the result does not depend on how the lists were cut.
+__global__ __launch_bounds__(256) void dot_topn_merge_kernel(const float* __restrict__ ls, const int32_t* __restrict__ li, int lists, int rows, int n,
+                                                             float* __restrict__ out_s, int32_t* __restrict__ out_i) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    uint64_t best[TOPN_CAP];
+#pragma unroll
+    for (int j = 0; j < TOPN_CAP; ++j) best[j] = ~0ull;
+    for (int l = lane; l < lists; l += 64) {
+        const size_t at = ((size_t)l * rows + row) * n;
+        for (int e = 0; e < n; ++e) {
+            const int32_t id = li[at + e];
+            if (id < 0) break;                                       // padding ends a list
+            const uint64_t key = (uint64_t)desc_key_f32(ls[at + e]) << 32 | (uint32_t)id;
+            if (key >= best[TOPN_CAP - 1]) break;                    // ... and so does an entry that no longer enters: the rest is worse
+#pragma unroll
+            for (int j = TOPN_CAP - 1; j >= 0; --j)
+                best[j] = key < best[j] ? (j > 0 && key < best[j > 0 ? j - 1 : 0] ? best[j > 0 ? j - 1 : 0] : key) : best[j];
+        }
+    }
+    for (int r = 0; r < n; ++r) {
+        uint64_t m = best[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const uint64_t x = __shfl_xor(m, o, 64); m = x < m ? x : m; }
+        if (m != ~0ull && best[0] == m) {                            // the one lane that holds the winner pops it
+#pragma unroll
+            for (int j = 0; j + 1 < TOPN_CAP; ++j) best[j] = best[j + 1];
+            best[TOPN_CAP - 1] = ~0ull;
+        }
+        if (lane == 0) {
+            out_s[(size_t)row * n + r] = m == ~0ull ? -INFINITY : desc_key_f32_inv((uint32_t)(m >> 32));
+            out_i[(size_t)row * n + r] = m == ~0ull ? -1 : (int32_t)(uint32_t)m;
+        }
+    }
 }
 
 }  // namespace fz
@@ -654,4 +799,66 @@ extern "C" int fz_splade_head_max_f32(const float* X, int ldx, const float* W, i
     g.Q = T; g.N = V; g.d = d;
     g.bias = bias; g.cu_rows = cu_rows; g.nseq = nseq; g.pool = pool; g.ldp = ldp;
     return launch_gemm(g, EPI_SPLADE, as_stream(stream));
+}
+
+// ---- top-n of every row of X . C^T without the plane (ColBERT centroid probes / assignment / k-means) -------------------------------------
+// The plan is a pure function of the shape -- not of the device -- so that the workspace can be sized, and every argument judged, before any
+// HIP call: TT token tiles of 128 rows; with fewer of them than the 512 workgroups an MI355X holds (2 per CU), the KB centroid blocks are
+// cut into G groups of `per`.  (score, id) is a total order: the result is the same for every plan.
+constexpr long TOPN_SLOTS = 512;
+static void topn_plan(int rows, int K, long* TT, int* per, int* G) {
+    *TT = ((long)rows + BM - 1) / BM;
+    const long KB = ((long)K + BM - 1) / BM;
+    long g = std::max(1L, std::min(KB, TOPN_SLOTS / std::max(1L, *TT)));
+    *per = (int)std::max(1L, (KB + g - 1) / g);
+    *G = (int)((KB + *per - 1) / *per);                    // no empty group
+}
+
+extern "C" int fz_dot_topn_max(void) { return TOPN_CAP; }
+
+extern "C" size_t fz_dot_topn_workspace_bytes(int rows, int K, int n) {
+    if (rows <= 0 || K <= 0 || n <= 0) return 0;
+    // TT * G <= min(KB * TT, max(TT, slots)), which -- unlike TT * G itself -- never shrinks when rows or K grow
+    const size_t TT = ((size_t)rows + BM - 1) / BM, KB = ((size_t)K + BM - 1) / BM;
+    const size_t cells = std::min(KB * TT, std::max(TT, (size_t)TOPN_SLOTS));
+    return cells * BM * 4 * (size_t)n * 8 + 256;           // 4 lists per (token, group), float32 score + int32 id per entry
+}
+
+extern "C" int fz_dot_topn_f32(const float* X, int ldx, const float* C, int ldc, int rows, int K, int d, int n, float* out_scores,
+                               int32_t* out_ids, void* workspace, size_t workspace_bytes, void* stream) {
+    if (rows < 0 || K < 0 || d <= 0 || ldx < d || ldc < d || n <= 0) return FZ_ERR_ARG;
+    if (rows == 0) return FZ_OK;
+    if (!X || !out_scores || !out_ids || (!C && K > 0)) return FZ_ERR_ARG;
+    if (n > TOPN_CAP) return FZ_ERR_UNSUPPORTED;
+    if ((d % 4) || (ldx % 4) || (ldc % 4) || ((uintptr_t)X % 16) || ((uintptr_t)C % 16)) return FZ_ERR_UNSUPPORTED;
+    // per-lane offsets are signed 32-bit byte offsets inside one 128-row operand tile
+    if (128.0 * ldx * 4 >= 2147483648.0 || 128.0 * ldc * 4 >= 2147483648.0) return FZ_ERR_UNSUPPORTED;
+    const size_t need = fz_dot_topn_workspace_bytes(rows, K, n);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return FZ_ERR_WORKSPACE;
+    long TT; int per, G;
+    topn_plan(rows, K, &TT, &per, &G);
+    if (TT * G > 0x3fffffffL) return FZ_ERR_UNSUPPORTED;
+    hipStream_t st = as_stream(stream);
+    GemmArgs g{};
+    g.A = C; g.lda = ldc; g.B = X; g.ldb = ldx;
+    g.Q = K; g.N = rows; g.d = d;
+    g.tn_n = n; g.tn_per = per;
+    const size_t entries = (size_t)4 * G * rows * n;
+    g.tn_s = reinterpret_cast<float*>(workspace);
+    g.tn_i = reinterpret_cast<int32_t*>(g.tn_s + entries);
+    if (K > 0) {
+        constexpr size_t lds_db = 2 * (BM + 128) * LDT * sizeof(float);
+        static unsigned long long lds_set[2] = {0ull, 0ull};
+        if (d % (2 * BK) != 0) {
+            if (int rc = raise_lds_limit((const void*)dot_topn_kernel<true>, lds_db, lds_set[1])) return rc;
+            dot_topn_kernel<true><<<(unsigned)(TT * G), 256, lds_db, st>>>(g, (int)TT);
+        } else {
+            if (int rc = raise_lds_limit((const void*)dot_topn_kernel<false>, lds_db, lds_set[0])) return rc;
+            dot_topn_kernel<false><<<(unsigned)(TT * G), 256, lds_db, st>>>(g, (int)TT);
+        }
+        FZ_LAUNCH_CHECK();
+    }
+    dot_topn_merge_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(g.tn_s, g.tn_i, K > 0 ? 4 * G : 0, rows, n, out_scores, out_ids);
+    FZ_LAUNCH_CHECK();
+    return FZ_OK;
 }

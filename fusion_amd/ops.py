@@ -183,6 +183,34 @@ def dot_scores(Qn: torch.Tensor, Dn: torch.Tensor, out: torch.Tensor | None = No
     return out
 
 
+def dot_topn_max() -> int:
+    """Largest n of dot_topn: the lists are carried in registers through the GEMM."""
+    return int(_lib.lib().fz_dot_topn_max())
+
+
+def dot_topn(X: torch.Tensor, C: torch.Tensor, n: int):
+    """The n best columns of every row of X @ C.T by (score desc, id asc) -> (scores [rows, n] float32, ids [rows, n] int32), (-inf, -1)
+    padding when n > K: bit for bit topk_rows(dot_scores(X, C), n), but the selection is the GEMM's epilogue and the [rows, K] plane is never
+    written.  n <= dot_topn_max(); X and C finite."""
+    _dev(X, torch.float32, "dot_topn(X)")
+    _dev(C, torch.float32, "dot_topn(C)")
+    _need(X.dim() == 2 and C.dim() == 2, "dot_topn: X [rows, d] and C [K, d] expected")
+    n = int(n)
+    _need(1 <= n <= dot_topn_max(), f"dot_topn: n = {n} outside 1 .. {dot_topn_max()} (dot_topn_max)")
+    X, C = pad_dim(X), pad_dim(C)
+    if X.shape[1] != C.shape[1]:
+        raise ValueError(f"embedding dims differ: {X.shape[1]} vs {C.shape[1]}")
+    rows, K, d = X.shape[0], C.shape[0], X.shape[1]
+    os_ = torch.empty((rows, n), dtype=torch.float32, device=X.device)
+    oi = torch.empty((rows, n), dtype=torch.int32, device=X.device)
+    lib = _lib.lib()
+    wsb = int(lib.fz_dot_topn_workspace_bytes(rows, K, n))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=X.device)
+    check(lib.fz_dot_topn_f32(_ptr(X), X.stride(0) if rows > 1 else d, _ptr(C), C.stride(0) if K > 1 else d, rows, K, d, n, _ptr(os_), _ptr(oi),
+                              _ptr(ws), wsb, _stream(X)), "fz_dot_topn_f32")
+    return os_, oi
+
+
 def cos_scores(Qe: torch.Tensor, De: torch.Tensor) -> torch.Tensor:
     """util.cos_sim as called at hybrid.py:103."""
     return dot_scores(normalize_rows(Qe), normalize_rows(De))
@@ -1714,7 +1742,9 @@ def sparse_cos_scores(Qe: torch.Tensor, index: SparseIndex, max_query_density: f
 # ---------------------------------------------------------------------------------------
 # K2 at corpus scale, first stage: candidates from token centroids (csrc/centroid.hip)
 # ---------------------------------------------------------------------------------------
-CENTROID_BLOCK_BYTES = 256 << 20            # float32 score blocks of centroid_assign / centroid_probes / kmeans_centroids stay below this
+CENTROID_BLOCK_BYTES = 256 << 20            # what centroid_assign / centroid_probes / kmeans_centroids allocate per block of rows stays below this:
+#                                             the float32 score block of the two-kernel route, the float32 rows + list workspace of the fused one
+CENTROID_FUSED = True                       # fused=None: dot_topn (selection in the GEMM's epilogue) wherever n <= dot_topn_max(); False: dot_scores + topk_rows
 CENTROID_SLICE_TABLE_MAX_BYTES = 1 << 30    # centroid_index builds the [K, NS + 1] slice table only below this size (as retrievers.bm25 does)
 
 
@@ -1737,10 +1767,30 @@ def _f32_rows(X: torch.Tensor, what: str) -> torch.Tensor:
     return X.float().contiguous()
 
 
-def _nearest(X32: torch.Tensor, C32: torch.Tensor) -> torch.Tensor:
-    """Row-wise argmax of X32 @ C32.T, ties to the lowest id, in blocks of CENTROID_BLOCK_BYTES of scores: dot_scores + topk_rows(1)."""
+def _centroid_fused(fused, n: int, what: str) -> bool:
+    """The route of one call: fused=True demands dot_topn, False the two kernels, None follows CENTROID_FUSED where dot_topn takes n."""
+    if fused is None:
+        return bool(CENTROID_FUSED) and n <= dot_topn_max()
+    if fused:
+        _need(n <= dot_topn_max(), f"{what}: fused=True takes at most {dot_topn_max()} entries per row (dot_topn_max), got {n}")
+    return bool(fused)
+
+
+def _topn_block_rows(dim: int, n: int) -> int:
+    """Rows per block of the fused route: their float32 copy and dot_topn's workspace (4 lists of n (score, id) pairs per row; below 65,536
+    rows it has a floor of that many rows' worth) within CENTROID_BLOCK_BYTES."""
+    return max(1, CENTROID_BLOCK_BYTES // (4 * round_up(dim, 4) + 32 * n))
+
+
+def _nearest(X32: torch.Tensor, C32: torch.Tensor, fused=None) -> torch.Tensor:
+    """Row-wise argmax of X32 @ C32.T, ties to the lowest id, in blocks of CENTROID_BLOCK_BYTES: dot_topn(.., 1), or dot_scores + topk_rows(1)."""
     n, K = X32.shape[0], C32.shape[0]
     out = torch.empty(n, dtype=torch.int32, device=X32.device)
+    if _centroid_fused(fused, 1, "kmeans_centroids"):
+        rows = _topn_block_rows(X32.shape[1], 1)
+        for r0 in range(0, n, rows):
+            out[r0: r0 + rows] = dot_topn(X32[r0: r0 + rows], C32, 1)[1][:, 0]
+        return out
     rows = max(1, CENTROID_BLOCK_BYTES // (4 * round_up(max(K, 1), _PAD)))
     for r0 in range(0, n, rows):
         _, ids = topk_rows(dot_scores(X32[r0: r0 + rows], C32), 1)
@@ -1748,16 +1798,21 @@ def _nearest(X32: torch.Tensor, C32: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def centroid_assign(Dtok: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
+def centroid_assign(Dtok: torch.Tensor, C: torch.Tensor, fused=None) -> torch.Tensor:
     """codes [sumL] int32: for every token row of Dtok [sumL, dim] the centroid of C [K, dim] with the largest dot product, ties to the
-    lowest id.  Chunked over token rows by a byte budget; the float32 MFMA GEMM (dot_scores) on the float32 copies, then topk_rows(.., 1):
-    bit-reproducible."""
+    lowest id.  Chunked over token rows by a byte budget; the float32 MFMA GEMM on the float32 copies with the selection in its epilogue
+    (dot_topn(.., 1); fused: see centroid_probes) or dot_scores, then topk_rows(.., 1) -- the same codes either way: bit-reproducible."""
     _dev(Dtok, None, "centroid_assign(Dtok)"); _dev(C, None, "centroid_assign(C)")
     _need(Dtok.dim() == 2 and C.dim() == 2 and C.shape[0] >= 1 and Dtok.shape[1] == C.shape[1], "centroid_assign: Dtok [sumL, dim] and C [K >= 1, dim] expected")
     _need(Dtok.dtype in (torch.float16, torch.float32), "centroid_assign(Dtok): float16 or float32 expected")
     C32 = _f32_rows(C, "centroid_assign(C)")
     n = Dtok.shape[0]
     out = torch.empty(n, dtype=torch.int32, device=Dtok.device)
+    if _centroid_fused(fused, 1, "centroid_assign"):
+        rows = _topn_block_rows(Dtok.shape[1], 1)
+        for r0 in range(0, n, rows):
+            out[r0: r0 + rows] = dot_topn(Dtok[r0: r0 + rows].float().contiguous(), C32, 1)[1][:, 0]
+        return out
     rows = max(1, CENTROID_BLOCK_BYTES // (4 * round_up(C.shape[0], _PAD)))
     for r0 in range(0, n, rows):     # the float32 copy of one block of token rows at a time
         _, ids = topk_rows(dot_scores(Dtok[r0: r0 + rows].float().contiguous(), C32), 1)
@@ -1765,11 +1820,12 @@ def centroid_assign(Dtok: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def kmeans_centroids(tokens: torch.Tensor, K: int, iters: int = 4, seed: int = 0, sample: int | None = None) -> torch.Tensor:
+def kmeans_centroids(tokens: torch.Tensor, K: int, iters: int = 4, seed: int = 0, sample: int | None = None, fused=None) -> torch.Tensor:
     """K unit-norm centroids [K, dim] float16 of the token rows (tokens [n, dim] float16 / float32 on the device, n >= K): seeded Lloyd
     iterations for the dot product (spherical k-means, what colbert-ai trains).  The start is K rows drawn by a generator seeded with
-    `seed`, `sample` (optional) trains on that many drawn rows; every step is dot_scores / topk_rows / a one-hot dot_scores -- no float
-    atomics -- so the result is deterministic for a given seed on a given device.  A cluster that loses all its rows keeps its centroid.
+    `seed`, `sample` (optional) trains on that many drawn rows; every step is dot_topn (fused: see centroid_probes; or dot_scores /
+    topk_rows) / a one-hot dot_scores -- no float atomics -- so the result is deterministic for a given seed on a given device, the same
+    by either route.  A cluster that loses all its rows keeps its centroid.
     Multi-rank callers train on ONE rank and broadcast the centroids (torch.distributed.broadcast): every shard must assign against the
     same table; no collective is built in here."""
     _dev(tokens, None, "kmeans_centroids(tokens)")
@@ -1784,7 +1840,7 @@ def kmeans_centroids(tokens: torch.Tensor, K: int, iters: int = 4, seed: int = 0
     dim = X.shape[1]
     blk = max(4, CENTROID_BLOCK_BYTES // (4 * K) // 4 * 4)     # rows per one-hot block [K, blk]
     for _ in range(int(iters)):
-        codes = _nearest(X, C).long()
+        codes = _nearest(X, C, fused).long()
         sums = torch.zeros((K, dim), dtype=torch.float32, device=X.device)
         for r0 in range(0, m, blk):
             r1 = min(m, r0 + blk)
@@ -1833,11 +1889,14 @@ def centroid_index(codes: torch.Tensor, Doff: torch.Tensor, K: int, slice_table_
     return CentroidIndex(coff, cdoc, N, K, slice_off)
 
 
-def centroid_probes(Qtok: torch.Tensor, C: torch.Tensor, nprobe: int):
+def centroid_probes(Qtok: torch.Tensor, C: torch.Tensor, nprobe: int, fused=None):
     """(pc [Q, Lq * nprobe] int32, ps [Q, Lq * nprobe] float32): per query token its nprobe best centroids by (score desc, id asc) and
-    their scores <q_i, C_c>, token-major.  dot_scores on the float32 copies + topk_rows over query blocks sized by a byte budget (the whole
-    [Q * Lq, K] float32 plane is 17 GB at Q = 1024, K = 65,536).  nprobe > K pads with (pc = -1, ps = -inf): the kernels skip a negative
-    id.  Query tokens must be finite: a non-finite probe score is outside the candidate score's contract."""
+    their scores <q_i, C_c>, token-major.  fused=True: dot_topn on the float32 copies -- the selection is the GEMM's epilogue and no score
+    plane exists (ValueError when nprobe > dot_topn_max()); fused=False: dot_scores + topk_rows over query blocks sized by a byte budget (the
+    whole [Q * Lq, K] float32 plane is 17 GB at Q = 1024, K = 65,536); None: CENTROID_FUSED, and the two kernels for an nprobe dot_topn does
+    not take.  Same bits by either route.  nprobe > K pads with (pc = -1, ps = -inf): the kernels skip a negative id.  Query tokens must
+    be finite: a non-finite probe score is outside the candidate score's contract."""
+    use_topn = _centroid_fused(fused, int(nprobe), "centroid_probes")
     _dev(Qtok, torch.float16, "centroid_probes(Qtok)"); _dev(C, None, "centroid_probes(C)")
     _need(Qtok.dim() == 3 and C.dim() == 2 and C.shape[0] >= 1 and Qtok.shape[2] == C.shape[1] and int(nprobe) >= 1,
           "centroid_probes: Qtok [Q, Lq, dim], C [K >= 1, dim] and nprobe >= 1 expected")
@@ -1848,9 +1907,10 @@ def centroid_probes(Qtok: torch.Tensor, C: torch.Tensor, nprobe: int):
     flat = Qtok.reshape(rowsT, dim)
     pc = torch.empty((rowsT, nprobe), dtype=torch.int32, device=Qtok.device)
     ps = torch.empty((rowsT, nprobe), dtype=torch.float32, device=Qtok.device)
-    rows = max(1, CENTROID_BLOCK_BYTES // (4 * round_up(K, _PAD)))
+    rows = _topn_block_rows(dim, nprobe) if use_topn else max(1, CENTROID_BLOCK_BYTES // (4 * round_up(K, _PAD)))
     for r0 in range(0, rowsT, rows):
-        s, i = topk_rows(dot_scores(flat[r0: r0 + rows].float().contiguous(), C32), nprobe)
+        X = flat[r0: r0 + rows].float().contiguous()
+        s, i = dot_topn(X, C32, nprobe) if use_topn else topk_rows(dot_scores(X, C32), nprobe)
         ps[r0: r0 + rows] = s
         pc[r0: r0 + rows] = i
     return pc.view(Q, Lq * nprobe), ps.view(Q, Lq * nprobe)

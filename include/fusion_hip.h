@@ -75,6 +75,21 @@ int fz_dot_scores_filter_f32(const float* Qn, int ldq, const float* Dn, int ldd,
                              const float* tau_padded, float* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap,
                              int32_t* overflow, void* stream);
 
+/* (ABI 20, additive) The same GEMM with a top-n selection as its epilogue: out_scores / out_ids [rows][n] = the n best columns of every row
+ * of X . C^T by (score desc, id asc), (-inf, -1) padding when n > K -- bit for bit fz_topk_rows_f32(fz_dot_scores_f32(X, C), n), with no
+ * [rows][K] plane written or read (the ColBERT centroid probes, the centroid assignment and k-means' nearest-centroid step; K = 65,536 there).
+ * X [rows][ldx], C [K][ldc] float32, finite.  The token rows ride on the GEMM's corpus side: a lane then owns one token per MFMA column
+ * block with the centroids in its own accumulator registers, carries the token's running list across the whole walk over the centroid
+ * blocks and writes it once; the 4 (or, with few rows, 4 x groups) partial lists of a token meet in one small merge.  No float atomics;
+ * (score, id) is a total order, so the result does not depend on the grid, on arrival order or on the device.
+ * n <= fz_dot_topn_max() (8), d % 4 == 0 and 16-byte aligned rows, else FZ_ERR_UNSUPPORTED; negative sizes, d <= 0, ld < d, n <= 0 or a null
+ * pointer where there is work -> FZ_ERR_ARG; rows == 0 -> FZ_OK, nothing touched; workspace below fz_dot_topn_workspace_bytes(rows, K, n)
+ * (0 for an empty problem; never shrinks when rows, K or n grow) -> FZ_ERR_WORKSPACE.  All decided before any HIP call. */
+int fz_dot_topn_max(void);
+size_t fz_dot_topn_workspace_bytes(int rows, int K, int n);
+int fz_dot_topn_f32(const float* X, int ldx, const float* C, int ldc, int rows, int K, int d, int n, float* out_scores, int32_t* out_ids,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- K2: ColBERT late interaction, hybrid.py:108-137 (exact MaxSim) ------ */
 /* scores[q][j] = sum_{i<Lq} max_{t in doc j} <Qtok[q][i], Dtok[t]>.
  * Qtok [Q][Lq][dim] fp16; Dtok packed ragged [sumL][dim] fp16, doc j owns rows [Doff[j], Doff[j+1]);

@@ -16,7 +16,14 @@ Two sizes, one corpus:
     recall@{10, 100, 1000} of the search's list against the exact all-pairs top-k (ops.maxsim + ops.topk_rows, timed too): the yardstick.
 The record is rewritten after every stage, so a run that is cut short leaves what it measured.
 
-Usage: python tools/bench_colbert_search.py [--out profiles/r13_colbert_search.json]"""
+--routes measures, instead of all that, the two routes of the centroid GEMM's selection on the same inputs: centroid_probes (Q = --queries,
+Lq = --lq, K = --centroids, nprobe 1, 2, 4, 8) and centroid_assign (--assign-rows token rows) by ops.dot_topn (fused=True: the selection is
+the GEMM's epilogue) and by dot_scores + topk_rows (fused=False), alternated call by call -- 5 each after a warm-up call for the probes --
+with equal results asserted; -> --routes-out.  Its centroids are K token rows of the corpus distribution (the start of k-means): the times
+depend on the shapes, not on how well the centroids are trained.
+
+Usage: python tools/bench_colbert_search.py [--out profiles/r13_colbert_search.json]
+       python tools/bench_colbert_search.py --routes [--routes-out profiles/r14_centroid_probes.json]"""
 import argparse
 import json
 import os
@@ -141,6 +148,40 @@ def recall_at(got_ids, want_ids, r):
     return round(float((hit / r).mean()), 4)
 
 
+def centroid_routes(a):
+    """The record of --routes (see the header)."""
+    g = torch.Generator(device="cuda").manual_seed(7)
+    centres = torch.randn((a.centres, 128), generator=g, device="cuda")
+    centres /= centres.norm(dim=1, keepdim=True)
+    draw = lambda n: topic_tokens(centres, torch.randint(0, a.centres, (n,), generator=g, device="cuda"), a.noise, g)
+    C, Qtok, Dtok = draw(a.centroids), draw(a.queries * a.lq).view(a.queries, a.lq, 128), draw(a.assign_rows)
+    rec = dict(what="centroid_probes and centroid_assign by the fused route (ops.dot_topn: top-n selection in the GEMM's epilogue) and by the two-kernel "
+                    "route (dot_scores + topk_rows) on the same inputs, alternated call by call after a warm-up call of each; HIP events",
+               device=torch.cuda.get_device_properties(0).name, queries=a.queries, Lq=a.lq, centroids=a.centroids, dot_topn_max=ops.dot_topn_max(),
+               block_bytes=ops.CENTROID_BLOCK_BYTES, default_fused=ops.CENTROID_FUSED, probes={})
+
+    def dump():
+        with open(a.routes_out, "w") as f:
+            json.dump(rec, f, indent=1)
+
+    for nprobe in (1, 2, 4, 8):
+        f1, f0 = ops.centroid_probes(Qtok, C, nprobe, fused=True), ops.centroid_probes(Qtok, C, nprobe, fused=False)
+        same = bool(torch.equal(f1[0], f0[0]) and torch.equal(f1[1].view(torch.int32), f0[1].view(torch.int32)))
+        t1, t0 = event_ms_alternating(lambda: ops.centroid_probes(Qtok, C, nprobe, fused=True), lambda: ops.centroid_probes(Qtok, C, nprobe, fused=False), a.reps)
+        rec["probes"][f"nprobe{nprobe}"] = dict(fused=t1, two_kernels=t0, same_bits=same, speedup=round(t0["median_ms"] / t1["median_ms"], 2))
+        print(json.dumps({f"nprobe{nprobe}": rec["probes"][f"nprobe{nprobe}"]}), flush=True)
+        dump()
+        assert same, f"the routes differ at nprobe = {nprobe}"
+    small = Dtok[: 1 << 16]
+    assert torch.equal(ops.centroid_assign(small, C, fused=True), ops.centroid_assign(small, C, fused=False))
+    t1, t0 = event_ms_alternating(lambda: ops.centroid_assign(Dtok, C, fused=True), lambda: ops.centroid_assign(Dtok, C, fused=False), 2)
+    rec["assign"] = dict(rows=a.assign_rows, fused=t1, two_kernels=t0, speedup=round(t0["median_ms"] / t1["median_ms"], 2),
+                         fused_us_per_1000_rows=round(1e3 * t1["median_ms"] / a.assign_rows * 1e3, 3),
+                         two_kernels_us_per_1000_rows=round(1e3 * t0["median_ms"] / a.assign_rows * 1e3, 3))
+    print(json.dumps({"assign": rec["assign"]}), flush=True)
+    dump()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_105_228)
@@ -156,9 +197,15 @@ def main():
     ap.add_argument("--kmeans-sample", type=int, default=2_000_000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r13_colbert_search.json"))
+    ap.add_argument("--routes", action="store_true", help="only the fused / two-kernel comparison of centroid_probes and centroid_assign")
+    ap.add_argument("--assign-rows", type=int, default=1 << 21)
+    ap.add_argument("--routes-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r14_centroid_probes.json"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_colbert_search.py measures on the GPU: no device found")
+    if a.routes:
+        os.makedirs(os.path.dirname(os.path.abspath(a.routes_out)), exist_ok=True)
+        return centroid_routes(a)
     assert a.recall_docs <= a.docs
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     rec = dict(what="ColBERT first-stage search on a clustered synthetic corpus: HIP events, median of %d calls after one warm-up call of the same "
