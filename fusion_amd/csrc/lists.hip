@@ -10,18 +10,9 @@
 // so the stable row sort on out_scores with row_len = out_len breaks ties exactly as the reference's sorted() does.  The fused
 // score of a column is 0 + c_s1 + c_s2 + ... over the systems that list the id, added in system order.
 //
-// Per system, per chunk of T = 1024 entries (one entry per thread, kept in registers), three barriers:
-//   1. look the id up (read only, but for one atomic OR on a hit: bit 16 + s of the slot = "system s listed this column";
-//      finding the own system's bit already set is a duplicate id inside the list)
-//   2. ballot + block scan of the "new" flags -> column = base + exclusive prefix; the id goes to LDS and to out_ids
-//   3. the new ids are inserted: compare-and-swap on the slot (EMPTY -> column | own system bit), linear probing; a failed
-//      swap onto a slot that holds the same id is a duplicate as well
-//   4. accumulate: a new column is written (0 + c), a hit column is read, added to and written back -- entries of one system
-//      hit distinct columns, and the barrier that closes the chunk orders the systems.  The accumulators live in the output row.
-// Columns never depend on the arrival order of the atomics: two runs give the same bytes.
-//
-// LDS: ids [cap] int64 + table [2 * cap rounded up to a power of two] uint32 + 16 wave totals, cap = min(sum of the list widths,
-// 8,192) of the CALL: 128 KB + 64 B at the capacity (one workgroup per CU), 56 KB for three lists of 1,000 (two per CU).
+// The walk that turns the lists into columns (steps 1-3, the LDS layout) is lists.h's.  This kernel's step 4, accumulate: a new
+// column is written (0 + c), a hit column is read, added to and written back -- entries of one system hit distinct columns, and
+// the barrier that closes the chunk orders the systems.  The accumulators live in the output row.
 #include "lists.h"
 
 namespace fz {
@@ -41,82 +32,26 @@ struct JoinArgs {
 template <int METHOD, typename ACC>
 __global__ __launch_bounds__(LJ_T) void lists_join_kernel(JoinArgs a, int64_t* __restrict__ out_ids, ACC* __restrict__ out_scores,
                                                           int32_t* __restrict__ out_len, int32_t* __restrict__ dup_flag) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lj_smem[];
-    constexpr int NW = LJ_T / 64;
-    int64_t* uid = reinterpret_cast<int64_t*>(lj_smem);                       // [cap] ids in column order
-    uint32_t* table = reinterpret_cast<uint32_t*>(uid + a.cap);               // [table_size]
-    uint32_t* wtot = table + a.table_size;                                    // [NW]
     const int q = blockIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-
-    // the table only needs twice the ROW's entries: short rows clear (and probe) a short table
-    int total = 0;
-    for (int s = 0; s < a.S; ++s) total += min(max(a.lens[s][q], 0), a.n[s]);
-    if (total == 0) {
+    LjRow j = lj_open(a, q);
+    if (j.total == 0) {
         if (threadIdx.x == 0) out_len[q] = 0;
         return;
     }
-    uint32_t tsize = 64;
-    while (tsize < 2u * (uint32_t)total) tsize <<= 1;   // <= table_size: total <= cap
-    const uint32_t mask = tsize - 1;
-    for (uint32_t i = threadIdx.x; i < tsize; i += LJ_T) table[i] = LJ_EMPTY;
-    __syncthreads();
-
     int64_t* __restrict__ orow = out_ids + (size_t)q * a.ld_out;
     ACC* __restrict__ srow = out_scores + (size_t)q * a.ld_out;
     const unsigned narrow_eff = a.narrow_mask & ~a.f64_mask;
     int base = 0;
     bool dup = false;
     for (int s = 0; s < a.S; ++s) {
-        const int len = min(max(a.lens[s][q], 0), a.n[s]);
+        const int len = lj_len(a, s, q);
         const int64_t* __restrict__ idrow = a.ids[s] + (size_t)q * a.ld[s];
-        const uint32_t sbit = 1u << (16 + s);
         for (int r0 = 0; r0 < len; r0 += LJ_T) {
             const int r = r0 + threadIdx.x;
             const bool live = r < len;
-            int64_t id = 0;
-            int col = -1;
-            uint32_t slot = 0, before = 0;   // before: the systems that listed the column ahead of this one
-            if (live) {
-                id = idrow[r];
-                slot = lj_hash(id, mask);
-                for (;;) {
-                    const uint32_t v = table[slot];
-                    if (v == LJ_EMPTY) break;
-                    if (uid[v & LJ_COL] == id) {
-                        col = (int)(v & LJ_COL);
-                        const uint32_t old = atomicOr(&table[slot], sbit);
-                        if (old & sbit) dup = true;
-                        before = (old >> 16) & 0xffu;
-                        break;
-                    }
-                    slot = (slot + 1) & mask;
-                }
-            }
-            const bool isnew = live && col < 0;
-            const unsigned long long bal = __ballot(isnew);
-            const int below = __popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) wtot[wv] = (uint32_t)__popcll(bal);
-            __syncthreads();
-            int woff = 0, tot = 0;
-#pragma unroll
-            for (int i = 0; i < NW; ++i) { const int c = (int)wtot[i]; if (i < wv) woff += c; tot += c; }
-            if (isnew) {
-                col = base + woff + below;      // < total <= cap: every live entry is counted in total
-                uid[col] = id;
-                orow[col] = id;
-            }
-            base += tot;
-            __syncthreads();
-            if (isnew) {
-                const uint32_t mine = (uint32_t)col | sbit;
-                for (;;) {      // the table is at most half full: an empty slot is always reached
-                    const uint32_t old = atomicCAS(&table[slot], LJ_EMPTY, mine);
-                    if (old == LJ_EMPTY) break;
-                    if (uid[old & LJ_COL] == id) { dup = true; break; }   // the same id twice in this chunk: it keeps its own column, unlisted
-                    slot = (slot + 1) & mask;
-                }
-            }
+            const LjPlaced p = lj_place(j, live, live ? idrow[r] : 0, 1u << (16 + s), orow, base, dup);
+            const int col = p.col;
+            const bool isnew = p.isnew;
             if (live) {
                 if constexpr (METHOD == FZ_LISTS_RRF || METHOD == FZ_LISTS_BCF) {
                     double c;
@@ -135,7 +70,7 @@ __global__ __launch_bounds__(LJ_T) void lists_join_kernel(JoinArgs a, int64_t* _
                     const double w = narrow ? (double)(float)a.w[s] : a.w[s];
                     double prod = v * w;
                     if (narrow) prod = (double)(float)prod;
-                    const bool wide = !narrow || (before & ~narrow_eff) != 0u;
+                    const bool wide = !narrow || (p.before & ~narrow_eff) != 0u;
                     double acc = (isnew ? 0.0 : srow[col]) + prod;
                     if (!wide) acc = (double)(float)acc;
                     srow[col] = acc;
@@ -157,19 +92,14 @@ using namespace fz;
 // =====================================================================================
 extern "C" int fz_lists_max_entries(void) { return LJ_MAX_ENTRIES; }
 
-extern "C" size_t fz_lists_join_workspace_bytes(int S, int Q) {
-    if (S <= 0 || S > FZ_MAX_SYSTEMS || Q < 0) return 0;
-    return 16;   // the duplicate flag (int32 at offset 0)
-}
+extern "C" size_t fz_lists_join_workspace_bytes(int S, int Q) { return lj_workspace_bytes(S, Q); }
 
 template <int METHOD, typename ACC>
 static int launch_join(const JoinArgs& a, int Q, int64_t* out_ids, void* out_scores, int32_t* out_len, int32_t* flag, size_t lds,
                        hipStream_t st) {
     static unsigned long long done = 0ull;
-    if (lds > 48 * 1024) {
-        const int rc = raise_lds_limit((const void*)lists_join_kernel<METHOD, ACC>, 160 * 1024, done);
-        if (rc != FZ_OK) return rc;
-    }
+    const int rc = lj_prepare((const void*)lists_join_kernel<METHOD, ACC>, lds, done, flag, st);
+    if (rc != FZ_OK) return rc;
     lists_join_kernel<METHOD, ACC><<<Q, LJ_T, lds, st>>>(a, out_ids, reinterpret_cast<ACC*>(out_scores), out_len, flag);
     FZ_LAUNCH_CHECK();
     return FZ_OK;
@@ -179,22 +109,18 @@ extern "C" int fz_lists_join(const int64_t* const* ids_h, const int32_t* const* 
                              const int32_t* value_is_f64_h, const double* w_h, const int32_t* narrow_h, const int32_t* n_h,
                              const int32_t* ld_h, int S, int Q, int method, int64_t* out_ids, void* out_scores, int32_t* out_len,
                              int ld_out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (S <= 0 || S > FZ_MAX_SYSTEMS || Q < 0 || !n_h || !ld_h) return FZ_ERR_ARG;
+    // (the method before the plan: an unknown method is FZ_ERR_ARG whatever the lists hold)
     if (method != FZ_LISTS_RRF && method != FZ_LISTS_BCF && method != FZ_LISTS_WSUM_F32 && method != FZ_LISTS_WSUM_F64) return FZ_ERR_ARG;
     const bool wsum = method == FZ_LISTS_WSUM_F32 || method == FZ_LISTS_WSUM_F64;
-    long long total = 0;
-    for (int s = 0; s < S; ++s) {
-        if (n_h[s] < 0 || ld_h[s] < n_h[s]) return FZ_ERR_ARG;
-        total += n_h[s];
-    }
-    if (total > LJ_MAX_ENTRIES) return FZ_ERR_UNSUPPORTED;
-    if (ld_out < total) return FZ_ERR_ARG;
+    LjPlan plan;
+    const int rc = lj_plan(n_h, ld_h, S, Q, ld_out, plan);
+    if (rc != FZ_OK) return rc;
     if (wsum && !w_h) return FZ_ERR_ARG;
-    if (Q == 0 || total == 0) return FZ_OK;       // nothing to join: empty tensors carry null pointers, out_len keeps the caller's zeros
+    if (Q == 0 || plan.cap == 0) return FZ_OK;    // nothing to join: empty tensors carry null pointers, out_len keeps the caller's zeros
     if (!ids_h || !lens_h || !out_ids || !out_scores || !out_len || (wsum && !values_h)) return FZ_ERR_ARG;
     if (!workspace || workspace_bytes < fz_lists_join_workspace_bytes(S, Q)) return FZ_ERR_WORKSPACE;
     JoinArgs a{};
-    a.S = S; a.ld_out = ld_out;
+    a.S = S; a.ld_out = ld_out; a.cap = plan.cap; a.table_size = plan.table_size;
     for (int s = 0; s < S; ++s) {
         if (!lens_h[s] || (n_h[s] > 0 && (!ids_h[s] || (wsum && !values_h[s])))) return FZ_ERR_ARG;
         a.ids[s] = ids_h[s]; a.lens[s] = lens_h[s];
@@ -208,14 +134,9 @@ extern "C" int fz_lists_join(const int64_t* const* ids_h, const int32_t* const* 
             return FZ_ERR_ARG;                    // the float32 accumulation takes float32 planes
         }
     }
-    a.cap = (int)total;
-    int ts = 64;
-    while (ts < 2 * a.cap) ts <<= 1;
-    a.table_size = ts;
-    const size_t lds = (size_t)a.cap * 8 + (size_t)ts * 4 + (LJ_T / 64) * 4;
     int32_t* flag = reinterpret_cast<int32_t*>(workspace);
     hipStream_t st = as_stream(stream);
-    FZ_HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
+    const size_t lds = plan.lds;                  // launch_join raises the kernel's LDS limit where needed and zeroes the flag
     switch (method) {
         case FZ_LISTS_RRF: return launch_join<FZ_LISTS_RRF, double>(a, Q, out_ids, out_scores, out_len, flag, lds, st);
         case FZ_LISTS_BCF: return launch_join<FZ_LISTS_BCF, double>(a, Q, out_ids, out_scores, out_len, flag, lds, st);

@@ -8,10 +8,8 @@
 // are scattered to its own plane over those columns.  gold_ranks_kernel / tune_metrics_kernel then run unchanged, on rows of at
 // most S x k columns.
 //
-// Same shape as lists_join_kernel (lists.hip): ONE 1,024-THREAD WORKGROUP PER QUERY, the union's ids in LDS in column order, the
-// open-addressing table with the system bits, columns from a ballot + block scan of the "new" flags -- never from the arrival
-// order of the atomics.  Where the join sums contributions into one row, this kernel writes, per query (ld_out = one row stride
-// for all planes):
+// The walk is lists_join_kernel's (lists.h: one workgroup per query, steps 1-3, the LDS layout).  Where the join sums contributions
+// into one row, this kernel writes, per query (ld_out = one row stride for all planes):
 //   out_ids [ld_out] int64   the union's ids in column order, -1 from out_len on      (fz_lists_join's bytes over a -1 fill)
 //   T_s     [ld_out] float32 values_s[r] in the column of ids_s[r], r < len_s; +0.0 everywhere else
 //   pos     [ld_out] int32   c for c < out_len, -1 beyond (the column IS the first-insertion position: the tie-break)
@@ -19,9 +17,6 @@
 // EVERY element has exactly one writer, so no output needs a pre-fill and two runs give the same bytes: a lister writes its value
 // into its column while the chunk is in registers; the closing pass -- the thread of column c looks uid[c] up and reads the slot's
 // system bits -- writes the zeros of the systems that do not list c, and everything from out_len on.
-//
-// LDS: the join's -- ids [cap] int64 + table [2 * cap rounded up to a power of two] uint32 + 16 wave totals: 128 KB + 64 B at the
-// capacity; the table is sized to the ROW's entries.
 #include "lists.h"
 
 namespace fz {
@@ -40,78 +35,21 @@ struct ColumnsArgs {
 
 __global__ __launch_bounds__(LJ_T) void lists_columns_kernel(ColumnsArgs a, int64_t* __restrict__ out_ids, int32_t* __restrict__ pos,
                                                              int32_t* __restrict__ out_len, int32_t* __restrict__ dup_flag) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lc_smem[];
-    constexpr int NW = LJ_T / 64;
-    int64_t* uid = reinterpret_cast<int64_t*>(lc_smem);                       // [cap] ids in column order
-    uint32_t* table = reinterpret_cast<uint32_t*>(uid + a.cap);               // [table_size]
-    uint32_t* wtot = table + a.table_size;                                    // [NW]
     const int q = blockIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-
-    int total = 0;
-    for (int s = 0; s < a.S; ++s) total += min(max(a.lens[s][q], 0), a.n[s]);
-    uint32_t tsize = 64;
-    while (tsize < 2u * (uint32_t)total) tsize <<= 1;   // <= table_size: total <= cap
-    const uint32_t mask = tsize - 1;
-    if (total > 0) {                                    // block-uniform; an empty row touches no LDS at all
-        for (uint32_t i = threadIdx.x; i < tsize; i += LJ_T) table[i] = LJ_EMPTY;
-        __syncthreads();
-    }
-
+    LjRow j = lj_open(a, q);
     const size_t orow_off = (size_t)q * a.ld_out;
     int64_t* __restrict__ orow = out_ids + orow_off;
     int base = 0;
     bool dup = false;
     for (int s = 0; s < a.S; ++s) {
-        const int len = min(max(a.lens[s][q], 0), a.n[s]);
+        const int len = lj_len(a, s, q);
         const int64_t* __restrict__ idrow = a.ids[s] + (size_t)q * a.ld[s];
-        const uint32_t sbit = 1u << (16 + s);
         for (int r0 = 0; r0 < len; r0 += LJ_T) {
             const int r = r0 + threadIdx.x;
             const bool live = r < len;
-            int64_t id = 0;
-            int col = -1;
-            uint32_t slot = 0;
-            if (live) {
-                id = idrow[r];
-                slot = lj_hash(id, mask);
-                for (;;) {
-                    const uint32_t v = table[slot];
-                    if (v == LJ_EMPTY) break;
-                    if (uid[v & LJ_COL] == id) {
-                        col = (int)(v & LJ_COL);
-                        if (atomicOr(&table[slot], sbit) & sbit) dup = true;
-                        break;
-                    }
-                    slot = (slot + 1) & mask;
-                }
-            }
-            const bool isnew = live && col < 0;
-            const unsigned long long bal = __ballot(isnew);
-            const int below = __popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) wtot[wv] = (uint32_t)__popcll(bal);
-            __syncthreads();
-            int woff = 0, tot = 0;
-#pragma unroll
-            for (int i = 0; i < NW; ++i) { const int c = (int)wtot[i]; if (i < wv) woff += c; tot += c; }
-            if (isnew) {
-                col = base + woff + below;      // < total <= cap <= ld_out: every live entry is counted in total
-                uid[col] = id;
-                orow[col] = id;
-            }
-            base += tot;
-            __syncthreads();
-            if (isnew) {
-                const uint32_t mine = (uint32_t)col | sbit;
-                for (;;) {      // the table is at most half full: an empty slot is always reached
-                    const uint32_t old = atomicCAS(&table[slot], LJ_EMPTY, mine);
-                    if (old == LJ_EMPTY) break;
-                    if (uid[old & LJ_COL] == id) { dup = true; break; }   // the same id twice in this chunk: it keeps its own column, unlisted
-                    slot = (slot + 1) & mask;
-                }
-            }
+            const LjPlaced p = lj_place(j, live, live ? idrow[r] : 0, 1u << (16 + s), orow, base, dup);
             // the lister is the one writer of (system s, column col): entries of one system hit distinct columns
-            if (live && a.has_values) a.T[s][orow_off + col] = a.values[s][(size_t)q * a.ld[s] + r];
+            if (live && a.has_values) a.T[s][orow_off + p.col] = a.values[s][(size_t)q * a.ld[s] + r];
             __syncthreads();   // the inserts of this chunk are in place before the next one (and the closing pass) looks them up
         }
     }
@@ -119,18 +57,10 @@ __global__ __launch_bounds__(LJ_T) void lists_columns_kernel(ColumnsArgs a, int6
     // closing pass, one thread per column of the row: the zeros no lister wrote, the positions, the tail from out_len on
     for (int c = threadIdx.x; c < a.ld_out; c += LJ_T) {
         uint32_t listed = 0u;                           // bit s: system s wrote T_s[c]
-        if (c < base) {
-            const int64_t id = uid[c];
-            uint32_t slot = lj_hash(id, mask);
-            for (;;) {                                  // the id is in the table (under its own or, for a duplicate, its twin's column)
-                const uint32_t v = table[slot];
-                if (v == LJ_EMPTY) break;
-                if (uid[v & LJ_COL] == id) {
-                    if ((int)(v & LJ_COL) == c) listed = (v >> 16) & 0xffu;
-                    break;
-                }
-                slot = (slot + 1) & mask;
-            }
+        if (c < base) {                                 // the id is in the table (under its own or, for a duplicate, its twin's column)
+            uint32_t slot;
+            const uint32_t v = lj_find(j, j.uid[c], slot);
+            if (v != LJ_EMPTY && (int)(v & LJ_COL) == c) listed = (v >> 16) & 0xffu;
         } else {
             orow[c] = -1;
         }
@@ -143,14 +73,10 @@ __global__ __launch_bounds__(LJ_T) void lists_columns_kernel(ColumnsArgs a, int6
     for (int g = threadIdx.x; g < a.G; g += LJ_T) {
         const int64_t id = a.gold_ids[(size_t)q * a.G + g];
         int col = -1;
-        if (id >= 0 && total > 0) {
-            uint32_t slot = lj_hash(id, mask);
-            for (;;) {
-                const uint32_t v = table[slot];
-                if (v == LJ_EMPTY) break;
-                if (uid[v & LJ_COL] == id) { col = (int)(v & LJ_COL); break; }
-                slot = (slot + 1) & mask;
-            }
+        if (id >= 0 && j.total > 0) {
+            uint32_t slot;
+            const uint32_t v = lj_find(j, id, slot);
+            if (v != LJ_EMPTY) col = (int)(v & LJ_COL);
         }
         a.gold_col[(size_t)q * a.G + g] = col;
     }
@@ -165,28 +91,22 @@ using namespace fz;
 // =====================================================================================
 // C ABI
 // =====================================================================================
-extern "C" size_t fz_lists_columns_workspace_bytes(int S, int Q) {
-    if (S <= 0 || S > FZ_MAX_SYSTEMS || Q < 0) return 0;
-    return 16;   // the duplicate flag (int32 at offset 0)
-}
+extern "C" size_t fz_lists_columns_workspace_bytes(int S, int Q) { return lj_workspace_bytes(S, Q); }
 
 extern "C" int fz_lists_columns(const int64_t* const* ids_h, const int32_t* const* lens_h, const float* const* values_h,
                                 const int32_t* n_h, const int32_t* ld_h, int S, int Q, const int64_t* gold_ids, int G,
                                 int64_t* out_ids, float* const* T_h, int32_t* pos, int32_t* out_len, int32_t* gold_col, int ld_out,
                                 void* workspace, size_t workspace_bytes, void* stream) {
-    if (S <= 0 || S > FZ_MAX_SYSTEMS || Q < 0 || G < 0 || !n_h || !ld_h) return FZ_ERR_ARG;
-    long long total = 0;
-    for (int s = 0; s < S; ++s) {
-        if (n_h[s] < 0 || ld_h[s] < n_h[s]) return FZ_ERR_ARG;
-        total += n_h[s];
-    }
-    if (total > fz_lists_max_entries()) return FZ_ERR_UNSUPPORTED;
-    if (ld_out < total) return FZ_ERR_ARG;
-    if (Q == 0 || total == 0) return FZ_OK;       // nothing to join: empty tensors carry null pointers, the outputs keep the caller's fill
+    if (G < 0) return FZ_ERR_ARG;
+    LjPlan plan;
+    int rc = lj_plan(n_h, ld_h, S, Q, ld_out, plan);
+    if (rc != FZ_OK) return rc;
+    if (Q == 0 || plan.cap == 0) return FZ_OK;    // nothing to join: empty tensors carry null pointers, the outputs keep the caller's fill
     if (!ids_h || !lens_h || !out_ids || !pos || !out_len || (values_h && !T_h) || (G > 0 && (!gold_ids || !gold_col))) return FZ_ERR_ARG;
     if (!workspace || workspace_bytes < fz_lists_columns_workspace_bytes(S, Q)) return FZ_ERR_WORKSPACE;
     ColumnsArgs a{};
     a.S = S; a.G = G; a.ld_out = ld_out; a.has_values = values_h ? 1 : 0;
+    a.cap = plan.cap; a.table_size = plan.table_size;
     a.gold_ids = gold_ids; a.gold_col = gold_col;
     for (int s = 0; s < S; ++s) {
         if (!lens_h[s] || (n_h[s] > 0 && (!ids_h[s] || (values_h && !values_h[s]))) || (values_h && !T_h[s])) return FZ_ERR_ARG;
@@ -195,20 +115,12 @@ extern "C" int fz_lists_columns(const int64_t* const* ids_h, const int32_t* cons
         a.T[s] = values_h ? T_h[s] : nullptr;
         a.n[s] = n_h[s]; a.ld[s] = ld_h[s];
     }
-    a.cap = (int)total;
-    int ts = 64;
-    while (ts < 2 * a.cap) ts <<= 1;
-    a.table_size = ts;
-    const size_t lds = (size_t)a.cap * 8 + (size_t)ts * 4 + (LJ_T / 64) * 4;
-    if (lds > 48 * 1024) {
-        static unsigned long long done = 0ull;
-        const int rc = raise_lds_limit((const void*)lists_columns_kernel, 160 * 1024, done);
-        if (rc != FZ_OK) return rc;
-    }
+    static unsigned long long done = 0ull;
     int32_t* flag = reinterpret_cast<int32_t*>(workspace);
     hipStream_t st = as_stream(stream);
-    FZ_HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
-    lists_columns_kernel<<<Q, LJ_T, lds, st>>>(a, out_ids, pos, out_len, flag);
+    rc = lj_prepare((const void*)lists_columns_kernel, plan.lds, done, flag, st);
+    if (rc != FZ_OK) return rc;
+    lists_columns_kernel<<<Q, LJ_T, plan.lds, st>>>(a, out_ids, pos, out_len, flag);
     FZ_LAUNCH_CHECK();
     return FZ_OK;
 }

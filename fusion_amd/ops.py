@@ -827,6 +827,45 @@ def lists_max_entries() -> int:
     return int(_lib.lib().fz_lists_max_entries())
 
 
+def _lists_args(what: str, ids, lens, values, f64_ok: bool = False):
+    """What lists_join and lists_columns check and marshal alike: S systems' ids [Q, k_s] int64, lens [Q] int32 and (None: no values)
+    value planes of the ids' shapes, float32 (or float64 where f64_ok).  A system whose ids and values differ in row stride is made
+    contiguous: the C ABI takes one stride per system.  -> (ids, lens, values, Q, total = sum of k_s, n_h, ld_h)."""
+    S = len(ids)
+    _max_systems(S, what)
+    _need(S >= 1, f"{what}: no system")
+    _need(len(lens) == S, f"{what}: {S} id lists but {len(lens)} length vectors")
+    _need(values is None or len(values) == S, f"{what}: needs {S} value planes")
+    ids = [_dev(t, torch.int64, f"{what}(ids)") for t in ids]
+    Q = ids[0].shape[0]
+    for t in ids:
+        _need(t.dim() == 2 and t.shape[0] == Q, f"{what}(ids): every system needs a [{Q}, k] tensor, got {tuple(t.shape)}")
+    total = sum(int(t.shape[1]) for t in ids)
+    cap = lists_max_entries()
+    _need(total <= cap, f"{what}: the lists of one query hold up to {total} entries, a join takes at most {cap} (fz_lists_max_entries)")
+    lens = [_dev(t, torch.int32, f"{what}(lens)").contiguous() for t in lens]
+    for t in lens:
+        _need(t.numel() == Q, f"{what}(lens): expected {Q} lengths, got {t.numel()}")
+    if values is not None:
+        values = list(values)
+        for s, v in enumerate(values):
+            _dev(v, None, f"{what}(values)")
+            if v.dtype != torch.float32 and not (f64_ok and v.dtype == torch.float64):
+                raise TypeError(f"{what}: value planes must be float32{' or float64' if f64_ok else ''}, got {v.dtype}")
+            _need(tuple(v.shape) == tuple(ids[s].shape), f"{what}(values): system {s} has ids {tuple(ids[s].shape)} but values {tuple(v.shape)}")
+            if _ld(v) != _ld(ids[s]):       # one row stride per system: ids and values side by side
+                ids[s], values[s] = ids[s].contiguous(), v.contiguous()
+    n_h = (C.c_int32 * S)(*[int(t.shape[1]) for t in ids])
+    ld_h = (C.c_int32 * S)(*[max(_ld(t), int(t.shape[1])) for t in ids])
+    return ids, lens, values, Q, total, n_h, ld_h
+
+
+def _lists_no_duplicate(what: str, ws: torch.Tensor):
+    """The one flag read of a list join (int32 at offset 0 of its workspace): set where a list holds an id twice."""
+    if int(ws[:4].view(torch.int32).item()) != 0:
+        raise ValueError(f"{what}: a list holds the same id twice (ids inside one system's list must be distinct)")
+
+
 def lists_join(ids: list[torch.Tensor], lens: list[torch.Tensor], method: str, values: list[torch.Tensor] | None = None,
                weights=None, narrow=None):
     """Per-query id join of S systems' top-k lists (fz_lists_join; hybrid.py:293-307 on lists of any int64 ids).
@@ -836,35 +875,13 @@ def lists_join(ids: list[torch.Tensor], lens: list[torch.Tensor], method: str, v
     Returns (out_ids [Q, n] int64, out_scores [Q, n], out_len [Q] int32), n = sum of k_s, the columns in the fused dict's
     first-insertion order: sort_rows_desc(out_scores, row_len=out_len) ranks them with the reference's tie rule.  Columns past
     out_len hold (-1, -inf).  An id listed twice inside one list raises ValueError (one flag read per call)."""
-    S = len(ids)
-    _max_systems(S, "lists_join")
-    _need(S >= 1, "lists_join: no system")
     _need(method in LISTS_METHODS, f"lists_join: unknown method {method!r} (one of {sorted(LISTS_METHODS)})")
-    _need(len(lens) == S, f"lists_join: {S} id lists but {len(lens)} length vectors")
+    S = len(ids)
     wsum = method in ("wsum32", "wsum64")
     if wsum:
         _need(values is not None and len(values) == S, f"lists_join({method}): needs {S} value planes")
         _need(weights is not None and len(weights) == S, f"lists_join({method}): needs {S} weights")
-    ids = [_dev(t, torch.int64, "lists_join(ids)") for t in ids]
-    Q = ids[0].shape[0]
-    for t in ids:
-        _need(t.dim() == 2 and t.shape[0] == Q, f"lists_join(ids): every system needs a [{Q}, k] tensor, got {tuple(t.shape)}")
-    total = sum(int(t.shape[1]) for t in ids)
-    cap = lists_max_entries()
-    _need(total <= cap, f"lists_join: the lists of one query hold up to {total} entries, a join takes at most {cap} (fz_lists_max_entries)")
-    lens = [_dev(t, torch.int32, "lists_join(lens)").contiguous() for t in lens]
-    for t in lens:
-        _need(t.numel() == Q, f"lists_join(lens): expected {Q} lengths, got {t.numel()}")
-    vals = [None] * S
-    if wsum:
-        for s, v in enumerate(values):
-            _dev(v, None, "lists_join(values)")
-            if v.dtype != torch.float32 and not (method == "wsum64" and v.dtype == torch.float64):
-                raise TypeError(f"lists_join({method}): value planes must be float32{' or float64' if method == 'wsum64' else ''}, got {v.dtype}")
-            _need(tuple(v.shape) == tuple(ids[s].shape), f"lists_join(values): system {s} has ids {tuple(ids[s].shape)} but values {tuple(v.shape)}")
-            if _ld(v) != _ld(ids[s]):       # one row stride per system: ids and values side by side
-                ids[s], v = ids[s].contiguous(), v.contiguous()
-            vals[s] = v
+    ids, lens, vals, Q, total, n_h, ld_h = _lists_args("lists_join", ids, lens, values if wsum else None, f64_ok=method == "wsum64")
     dev = ids[0].device
     ld_out = max(round_up(total, _PAD), _PAD)
     f32 = method == "wsum32"
@@ -874,16 +891,14 @@ def lists_join(ids: list[torch.Tensor], lens: list[torch.Tensor], method: str, v
     lib = _lib.lib()
     wsb = int(lib.fz_lists_join_workspace_bytes(S, Q))
     ws = torch.zeros(max(wsb, 4), dtype=torch.uint8, device=dev)
-    n_h = (C.c_int32 * S)(*[int(t.shape[1]) for t in ids])
-    ld_h = (C.c_int32 * S)(*[max(_ld(t), int(t.shape[1])) for t in ids])
     w = (C.c_double * S)(*[float(x) for x in weights]) if wsum else None
     v64 = (C.c_int32 * S)(*[int(v.dtype == torch.float64) for v in vals]) if wsum else None
     nr = (C.c_int32 * S)(*[int(bool(x)) for x in (narrow if narrow is not None else [False] * S)]) if method == "wsum64" else None
     check(lib.fz_lists_join(_ptr_array(ids), _ptr_array(lens), _ptr_array(vals) if wsum else None, v64, w, nr, n_h, ld_h, S, Q,
                             LISTS_METHODS[method], _ptr(out_ids), _ptr(out_scores), _ptr(out_len), ld_out, _ptr(ws), ws.numel(),
                             _stream(ids[0])), "fz_lists_join")
-    if Q > 0 and total > 0 and int(ws[:4].view(torch.int32).item()) != 0:
-        raise ValueError("lists_join: a list holds the same id twice (ids inside one system's list must be distinct)")
+    if Q > 0 and total > 0:
+        _lists_no_duplicate("lists_join", ws)
     return out_ids, out_scores, out_len
 
 
@@ -897,30 +912,8 @@ def lists_columns(ids: list[torch.Tensor], lens: list[torch.Tensor], values: lis
     fused dict's first-insertion order: out_ids holds the id (-1 beyond out_len), T[s] system s's value for it (+0.0 where s does
     not list it, and beyond out_len), pos holds c (-1 beyond); gold_col holds the column of each gold id, -1 for padding or an id in
     no list.  An id listed twice inside one list raises ValueError (one flag read per call)."""
+    ids, lens, vals, Q, total, n_h, ld_h = _lists_args("lists_columns", ids, lens, values)
     S = len(ids)
-    _max_systems(S, "lists_columns")
-    _need(S >= 1, "lists_columns: no system")
-    _need(len(lens) == S, f"lists_columns: {S} id lists but {len(lens)} length vectors")
-    _need(values is None or len(values) == S, f"lists_columns: needs {S} value planes")
-    ids = [_dev(t, torch.int64, "lists_columns(ids)") for t in ids]
-    Q = ids[0].shape[0]
-    for t in ids:
-        _need(t.dim() == 2 and t.shape[0] == Q, f"lists_columns(ids): every system needs a [{Q}, k] tensor, got {tuple(t.shape)}")
-    total = sum(int(t.shape[1]) for t in ids)
-    cap = lists_max_entries()
-    _need(total <= cap, f"lists_columns: the lists of one query hold up to {total} entries, a join takes at most {cap} (fz_lists_max_entries)")
-    lens = [_dev(t, torch.int32, "lists_columns(lens)").contiguous() for t in lens]
-    for t in lens:
-        _need(t.numel() == Q, f"lists_columns(lens): expected {Q} lengths, got {t.numel()}")
-    vals = None
-    if values is not None:
-        vals = []
-        for s, v in enumerate(values):
-            _dev(v, torch.float32, "lists_columns(values)")
-            _need(tuple(v.shape) == tuple(ids[s].shape), f"lists_columns(values): system {s} has ids {tuple(ids[s].shape)} but values {tuple(v.shape)}")
-            if _ld(v) != _ld(ids[s]):       # one row stride per system: ids and values side by side
-                ids[s], v = ids[s].contiguous(), v.contiguous()
-            vals.append(v)
     dev = ids[0].device
     if gold_ids is None:
         gold_ids = torch.empty((Q, 0), dtype=torch.int64, device=dev)
@@ -939,14 +932,11 @@ def lists_columns(ids: list[torch.Tensor], lens: list[torch.Tensor], values: lis
     ld_out = _same_ld(out_ids, pos, *(T or []))
     lib = _lib.lib()
     ws = torch.empty(max(int(lib.fz_lists_columns_workspace_bytes(S, Q)), 4), dtype=torch.uint8, device=dev)
-    n_h = (C.c_int32 * S)(*[int(t.shape[1]) for t in ids])
-    ld_h = (C.c_int32 * S)(*[max(_ld(t), int(t.shape[1])) for t in ids])
     check(lib.fz_lists_columns(_ptr_array(ids), _ptr_array(lens), _ptr_array(vals) if vals is not None else None, n_h, ld_h, S, Q,
                                _ptr(gold_ids) if G else None, G, _ptr(out_ids), _ptr_array(T) if T is not None else None, _ptr(pos),
                                _ptr(out_len), _ptr(gold_col) if G else None, ld_out, _ptr(ws), ws.numel(), _stream(ids[0])),
           "fz_lists_columns")
-    if int(ws[:4].view(torch.int32).item()) != 0:
-        raise ValueError("lists_columns: a list holds the same id twice (ids inside one system's list must be distinct)")
+    _lists_no_duplicate("lists_columns", ws)
     return out_ids, T, pos, out_len, gold_col
 
 

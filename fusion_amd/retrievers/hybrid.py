@@ -364,9 +364,39 @@ class Aggregator:
     last_topk_path = None     # "select" | "sort": which of the two the last fuse_device(topk=...) took (tests pin it)
     last_rank_fused_sort = None   # True: the last rrf / bcf fusion ran as the load phase of the final sort (one kernel, no float64 plane)
 
+    # the normalisations that transform the scores (hybrid.py:254-278); any other string leaves them raw (:280)
+    TRANSFORMS = ("min-max", "z-score", "arctan", "percentile-rank", "normal-curve-equivalent")
+
     @classmethod
     def _wide(cls, w) -> bool:
         return cls.NUMPY1_PROMOTION or ops.is_wide_weight(w)
+
+    @staticmethod
+    def _same_queries(counts) -> int:
+        """The query count all systems share; the reference's assertion (its message verbatim) where they differ."""
+        counts = list(counts)
+        assert all(c == counts[0] for c in counts), (
+            "Ranked results from different retrieval systems have varying lenghts across systems (i.e., some systems have been run on more queries).")
+        return counts[0]
+
+    @classmethod
+    def _nsf_weights(cls, names, linear_weights, percentile_distributions):
+        """nsf's preamble, with the reference's errors in the reference's order -> (weights in system order, which of them are wide)."""
+        if percentile_distributions is None:            # the reference calls .get() on it for every system (hybrid.py:213)
+            raise AttributeError("'NoneType' object has no attribute 'get'")
+        w = [linear_weights[n] for n in names]          # KeyError when a system has no weight (hybrid.py:214)
+        return w, [cls._wide(x) for x in w]             # np.float64 weights (the tuning grid): NumPy promotes to float64
+
+    @classmethod
+    def _sweep_weights(cls, names, normalization, weight_combinations, dev):
+        """The grid as the sweep kernels' [W, S] weight tensor, or None where it takes the generic route: 'none' / unknown normalisations,
+        more than 4 systems, a grid that mixes the two kinds of weight.  NumPy promotion (hybrid.py:291,304): the reference's grid
+        (np.arange, :405-409) holds np.float64 weights -> float64 products and sums; a grid of Python floats fuses in float32."""
+        kinds = {cls._wide(x) for w in weight_combinations for x in w.values()}
+        if normalization not in cls.TRANSFORMS or len(names) > 4 or len(kinds) > 1:
+            return None
+        W = torch.tensor([[float(w[n]) for n in names] for w in weight_combinations], dtype=torch.float64)   # KeyError as hybrid.py:214
+        return W.reshape(len(weight_combinations), len(names)).to(torch.float64 if kinds == {True} else torch.float32).to(dev)
 
     @classmethod
     def fuse(cls, ranked_lists: dict, method: str, normalization: str = None, linear_weights: dict[str, float] = None,
@@ -389,9 +419,7 @@ class Aggregator:
         names = list(systems.keys())
         ops._max_systems(len(names), "Aggregator.fuse_device")
         S = [systems[n] for n in names]
-        Q = S[0].Q
-        assert all(s.Q == Q for s in S), (
-            "Ranked results from different retrieval systems have varying lenghts across systems (i.e., some systems have been run on more queries).")
+        Q = cls._same_queries(s.Q for s in S)
         N = S[0].N
         if any(s.N != N for s in S):
             raise ValueError("device systems must be planes over the same corpus")
@@ -410,11 +438,8 @@ class Aggregator:
             rank_fused_sort = 0 < N <= ops.sort_max_n(torch.float64) and Q > 0
             fused = None if rank_fused_sort else ops.fuse_rank([s.rank for s in S], lens, method)
         elif method == "nsf":
-            if percentile_distributions is None:            # the reference calls .get() on it for every system (hybrid.py:213)
-                raise AttributeError("'NoneType' object has no attribute 'get'")
-            w = [linear_weights[n] for n in names]          # KeyError when a system has no weight (hybrid.py:214)
-            wide = [cls._wide(x) for x in w]                # np.float64 weights (the tuning grid): NumPy promotes to float64
-            if normalization in ("min-max", "z-score", "arctan", "percentile-rank", "normal-curve-equivalent"):
+            w, wide = cls._nsf_weights(names, linear_weights, percentile_distributions)
+            if normalization in cls.TRANSFORMS:
                 distr = None
                 if normalization in ("percentile-rank", "normal-curve-equivalent"):
                     distr = [cls._table(percentile_distributions.get(n), dev) for n in names]
@@ -476,19 +501,14 @@ class Aggregator:
         names = list(systems.keys())
         ops._max_systems(len(names), "Aggregator.fuse_topk")
         S = [systems[n] for n in names]
-        Q = S[0].Q
-        assert all(s.Q == Q for s in S), (
-            "Ranked results from different retrieval systems have varying lenghts across systems (i.e., some systems have been run on more queries).")
+        Q = cls._same_queries(s.Q for s in S)
         ids, lens = [s.ids for s in S], [s.lens for s in S]
         raw = [s.scores if s.scores64 is None else s.scores64 for s in S]
         if method in ("bcf", "rrf"):
             joined = ops.lists_join(ids, lens, method)
         elif method == "nsf":
-            if percentile_distributions is None:            # the reference calls .get() on it for every system (hybrid.py:213)
-                raise AttributeError("'NoneType' object has no attribute 'get'")
-            w = [linear_weights[n] for n in names]          # KeyError when a system has no weight (hybrid.py:214)
-            wide = [cls._wide(x) for x in w]
-            if normalization in ("min-max", "z-score", "arctan", "percentile-rank", "normal-curve-equivalent"):
+            w, wide = cls._nsf_weights(names, linear_weights, percentile_distributions)
+            if normalization in cls.TRANSFORMS:
                 T = cls._normalised_lists(names, S, normalization, percentile_distributions)
                 if any(wide):
                     joined = ops.lists_join(ids, lens, "wsum64", T, w, narrow=[not x for x in wide])
@@ -546,48 +566,35 @@ class Aggregator:
         systems = cls._to_device(ranked_lists)
         names = list(systems.keys())
         S = [systems[n] for n in names]
-        # NumPy promotion (hybrid.py:291,304): the reference's grid (np.arange, :405-409) holds np.float64 weights -> float64
-        # products and sums; a grid of Python floats fuses in float32.  A grid that mixes the two kinds goes the generic way.
-        kinds = {cls._wide(x) for w in weight_combinations for x in w.values()}
-        if (normalization not in ("min-max", "z-score", "arctan", "percentile-rank", "normal-curve-equivalent") or len(S) > 4
-                or len(kinds) > 1):
-            return cls._tune_by_fusing(systems, normalization, weight_combinations, labels, percentile_distributions)
-        wide = kinds == {True}
-        Q, N = S[0].Q, S[0].N
         dev = S[0].scores.device
-        all_full = all(s.full for s in S)
+        weights = cls._sweep_weights(names, normalization, weight_combinations, dev)
+        if weights is None:
+            return cls._tune_by_fusing(systems, normalization, weight_combinations, labels, percentile_distributions)
+        Q, N = S[0].Q, S[0].N
         distr = None
         if normalization in ("percentile-rank", "normal-curve-equivalent"):
             distr = [cls._table(percentile_distributions.get(n), dev) for n in names]
         st = [s.stats(normalization) for s in S] if normalization in ("min-max", "z-score") else None
         T = cls._normalised_planes(S, normalization, distr, st, zero_unlisted=True)   # the very planes fuse_device's float64 path sums
-        if all_full:
+        if all(s.full for s in S):
             pos = S[0].rank
         else:
             lens = torch.stack([s.lens for s in S]).contiguous()
             ins, U, pos = ops.insertion_order([s.order for s in S], lens, N, want_pos=True)
-        weights = torch.tensor([[float(w[n]) for n in names] for w in weight_combinations],      # KeyError as hybrid.py:214
-                               dtype=torch.float64).to(torch.float64 if wide else torch.float32).to(dev)
         id2pos = {cid: j for j, cid in enumerate(S[0].ids.tolist())}
         gold_pos = [[id2pos.get(g, -1) for g in dict.fromkeys(gl)] for gl in labels]   # unique, order kept
         G = int(ops._lib.lib().fz_tune_max_gold())
         Gmax = max((len(g) for g in gold_pos), default=0)
-        W = len(weight_combinations)
         n_gold = np.array([len(gl) for gl in labels], dtype=np.int64)          # the reference divides by len(ground_truths)
         if Gmax <= G:
             # every gold list fits one counting launch: ranks -> metrics stay on the device (csrc/tune.hip, tune_metrics_kernel);
             # [W, 15] float64 come back instead of [W, Q, G] ranks and a NumPy evaluation that cost more than the sweep itself
-            from ..utils.metrics import MAP_KS, MRR_KS, NDCG_KS, RECALL_KS, gold_rank_tables
             gold = np.full((Q, G), -1, dtype=np.int32)
             for q, gl in enumerate(gold_pos):
                 gold[q, :len(gl)] = gl
             gold_dev = torch.from_numpy(gold).to(dev)
-            table, idcg, mnames = gold_rank_tables(n_gold)
-            rk = ops.gold_ranks(T, pos, weights, gold_dev)
-            means = ops.tune_metrics(rk, gold_dev, pos, torch.from_numpy(n_gold.astype(np.int32)).to(dev), torch.from_numpy(idcg).to(dev),
-                                     torch.from_numpy(table).to(dev), dict(recall=RECALL_KS, map=MAP_KS, mrr=MRR_KS, ndcg=NDCG_KS)).cpu().numpy()
-            return [dict(zip(mnames, row)) for row in means.tolist()]   # Python floats, as run_evaluation returns
-        ranks = np.full((W, Q, max(Gmax, 1)), np.iinfo(np.int64).max, dtype=np.int64)
+            return cls._metrics_of_gold_ranks(ops.gold_ranks(T, pos, weights, gold_dev), gold_dev, pos, n_gold, dev)
+        ranks = np.full((len(weight_combinations), Q, max(Gmax, 1)), np.iinfo(np.int64).max, dtype=np.int64)
         pos_host = None
         for g0 in range(0, Gmax, G):
             gold = np.full((Q, G), -1, dtype=np.int32)
@@ -642,7 +649,7 @@ class Aggregator:
 
     @staticmethod
     def _metrics_of_gold_ranks(rk, gold_col, pos, n_gold, dev):
-        """run_evaluation's metrics per weight vector from [W, Q, G] gold ranks on the device (tune's own tail) -> list of dicts."""
+        """run_evaluation's metrics per weight vector from [W, Q, G] gold ranks on the device (the tail tune, tune_topk and evaluate_topk share) -> list of dicts."""
         from ..utils.metrics import MAP_KS, MRR_KS, NDCG_KS, RECALL_KS, gold_rank_tables
         table, idcg, mnames = gold_rank_tables(n_gold)
         means = ops.tune_metrics(rk, gold_col, pos, torch.from_numpy(n_gold.astype(np.int32)).to(dev), torch.from_numpy(idcg).to(dev),
@@ -665,23 +672,17 @@ class Aggregator:
         names = list(systems.keys())
         ops._max_systems(len(names), "Aggregator.tune_topk")
         S = [systems[n] for n in names]
-        Q = S[0].Q
-        assert all(s.Q == Q for s in S), (
-            "Ranked results from different retrieval systems have varying lenghts across systems (i.e., some systems have been run on more queries).")
-        kinds = {cls._wide(x) for w in weight_combinations for x in w.values()}
-        if (normalization not in ("min-max", "z-score", "arctan", "percentile-rank", "normal-curve-equivalent") or len(S) > 4
-                or len(kinds) > 1):
+        Q = cls._same_queries(s.Q for s in S)
+        dev = S[0].ids.device
+        weights = cls._sweep_weights(names, normalization, weight_combinations, dev)
+        if weights is None:
             out = []
             for w in weight_combinations:      # generic path, as _tune_by_fusing: one device fusion + evaluation per weight vector
                 fused = cls.fuse_topk(systems, "nsf", normalization, w, percentile_distributions, topk=1000)   # every cut-off is <= 1000
                 perf = run_evaluation(fused.predictions(1000), labels, print2console=False)
                 out.append({k: float(v) for k, v in perf.items()})   # Python floats, as the fast path returns (nDCG comes as np.float64)
             return out
-        wide = kinds == {True}
-        dev = S[0].ids.device
-        weights = torch.tensor([[float(w[n]) for n in names] for w in weight_combinations],      # KeyError as hybrid.py:214
-                               dtype=torch.float64).reshape(len(weight_combinations), len(names)).to(torch.float64 if wide else torch.float32).to(dev)
-        Tn = cls._normalised_lists(names, S, normalization, percentile_distributions)
+        Tn =cls._normalised_lists(names, S, normalization, percentile_distributions)
         gold_dev, Gmax, n_gold = cls._gold_ids(labels, Q, dev)
         _, T, pos, out_len, gold_col = ops.lists_columns([s.ids for s in S], [s.lens for s in S], Tn, gold_dev)
         G = int(ops._lib.lib().fz_tune_max_gold())
@@ -727,9 +728,7 @@ class Aggregator:
         if isinstance(first, RankedSystem):
             return ranked_lists
         dev = _device()
-        Q = len(first)
-        assert all(len(v) == Q for v in ranked_lists.values()), (
-            "Ranked results from different retrieval systems have varying lenghts across systems (i.e., some systems have been run on more queries).")
+        Aggregator._same_queries(len(v) for v in ranked_lists.values())
         ids, N, packed = pack_ranked_lists(ranked_lists)
         out = {}
         t = lambda a: torch.from_numpy(a).to(dev)[:, :N]
@@ -754,7 +753,7 @@ class Aggregator:
             return {pid: (n - idx + 1) / n for idx, pid in enumerate(results.keys())}
         if transformation == "reciprocal-rank":
             return {pid: 1 / (60 + idx + 1) for idx, pid in enumerate(results.keys())}
-        if transformation not in ("min-max", "z-score", "arctan", "percentile-rank", "normal-curve-equivalent"):
+        if transformation not in Aggregator.TRANSFORMS:
             return results
         dev = _device()
         plane = ops.alloc_plane(1, n, torch.float32, dev)
@@ -913,7 +912,7 @@ def analyze_score_distributions(args, results: dict[str, RankedSystem], corpus: 
     transformed, in_list_order = {}, {}
     for n in names:
         rs = results[n]
-        if args.normalization in ("min-max", "z-score", "arctan", "percentile-rank", "normal-curve-equivalent"):
+        if args.normalization in Aggregator.TRANSFORMS:
             d = [Aggregator._table(distr.get(n), dev)] if n in distr else None
             t = ops.fuse_nsf([rs.scores], None if rs.full else [rs.rank], [1.0], args.normalization, d)
         else:

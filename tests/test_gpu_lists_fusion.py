@@ -210,7 +210,7 @@ def check_edge(oracle, lens_sq, widths, relation="overlap", id_of=None, seed=0, 
     return systems
 
 
-@pytest.mark.parametrize("total", [1, 63, 64, 65])
+@pytest.mark.parametrize("total", [1, 63, 64, 65, 1024, 1025, 2049])   # a wave's and a chunk's edges, as the columns test has them
 def test_join_total_entries_around_one_wave(total, oracle):
     a = (total + 1) // 2
     check_edge(oracle, [[a, total], [total - a, 0]], [max(a, total), max(total - a, 1)], seed=total)
