@@ -271,10 +271,19 @@ class ShardedTokenIndex:
     not own gets -inf, so the shards' [Q, k] planes combine by ONE all_reduce(MAX), and one stable descending row sort turns the plane
     into lists (ties keep candidate-list order, whatever the number of shards).  No host synchronisation on the single-rank path.
     With build_centroids the shard also generates its own candidates (ShardedCentroidIndex) and `search` is a first-stage search:
-    candidates from token centroids, every returned score exact.  The token matrix stays uncompressed."""
+    candidates from token centroids, every returned score exact.
+    Storage: the float16 token matrix (256 B per token), or after `compress` / from `build_compressed` the residual code of
+    include/fusion_hip.h 'Residual-compressed token rows' (the centroid id of the candidate stage + 2 or 4 bits per dimension: 36 or 68 B
+    per token).  Decompression is a fixed function of the stored bytes, and fz_maxsim_pairs_residual_f16 scores a compressed shard with the
+    bits ops.maxsim_pairs gives over the decompressed matrix: everything above holds for either storage, with D = the decompressed rows."""
 
     centroids = None        # [K, dim] float16, the same table on every rank (build_centroids)
     candidates = None       # the ShardedCentroidIndex of this shard
+    codes = None            # [sumL] int32: every token row's centroid (build_centroids keeps them: half of the compressed index)
+    packed = None           # [sumL, 16 * nbits] uint8: the residual buckets (compress / build_compressed)
+    cutoffs = None          # [2^nbits - 1] float32, the same on every rank
+    weights = None          # [2^nbits] float16, the same on every rank
+    nbits = None
 
     def __init__(self, Dtok_local: torch.Tensor, Doff_local: torch.Tensor, id_base: int, group=None, max_doc_len: int = 512):
         self.Dtok, self.Doff, self.id_base, self.group, self.max_doc_len = Dtok_local, Doff_local, int(id_base), group, int(max_doc_len)
@@ -285,8 +294,81 @@ class ShardedTokenIndex:
         if codes is None:
             codes = ops.centroid_assign(self.Dtok, C)
         self.centroids = C
+        self.codes = codes.to(torch.int32).contiguous()
         self.candidates = ShardedCentroidIndex(ops.centroid_index(codes, self.Doff, C.shape[0]), self.id_base, group=self.group)
         return self
+
+    def compress(self, nbits: int = 2, cutoffs: torch.Tensor | None = None, weights: torch.Tensor | None = None, keep_tokens: bool = False):
+        """Replace the float16 token matrix by its residual code against the centroid table of build_centroids: train the buckets on this
+        shard's rows unless (cutoffs, weights) are given (ops.residual_buckets; multi-rank callers train on ONE rank and broadcast both, as
+        for the centroids), pack every row (ops.residual_compress) and drop Dtok (None) unless keep_tokens.  From here on every score is the
+        exact MaxSim over the DECOMPRESSED rows (ops.residual_decompress), the same for any number of shards."""
+        if self.candidates is None or self.codes is None:
+            raise ValueError("ShardedTokenIndex.compress: no centroid index (call build_centroids first)")
+        if (cutoffs is None) != (weights is None):
+            raise ValueError("ShardedTokenIndex.compress: give both cutoffs and weights, or neither")
+        if self.Dtok is None:
+            raise ValueError("ShardedTokenIndex.compress: the token matrix is gone (already compressed)")
+        nbits = ops._residual_nbits("ShardedTokenIndex.compress", nbits)
+        C = self.centroids.to(torch.float16).contiguous()
+        ops.residual_check_codes(self.codes, C.shape[0])
+        if cutoffs is None:
+            cutoffs, weights = ops.residual_buckets(self.Dtok, C, self.codes, nbits)
+        self.packed = ops.residual_compress(self.Dtok, self.codes, C, cutoffs, nbits)
+        self.centroids, self.cutoffs, self.weights, self.nbits = C, cutoffs, weights.contiguous(), nbits
+        if not keep_tokens:
+            self.Dtok = None
+        return self
+
+    @classmethod
+    def build_compressed(cls, blocks, Doff: torch.Tensor, C: torch.Tensor, cutoffs: torch.Tensor, weights: torch.Tensor, nbits: int, id_base: int,
+                         group=None, max_doc_len: int = 512, device=None):
+        """A compressed shard from an ITERATOR of token-row blocks ([rows_i, 128] float16, in corpus order, together the Doff[N] rows of the
+        shard; as ops.sparse_index_from_blocks takes its blocks): every block is moved to the device, assigned (ops.centroid_assign) and
+        packed (ops.residual_compress) into its rows of the shard's arrays, then dropped -- the float16 matrix of the shard is never
+        resident.  C, cutoffs and weights are the tables every rank shares.  The result equals build_centroids(C) + compress(nbits, cutoffs,
+        weights) of the whole matrix: the same codes, bytes and candidate index."""
+        nbits = ops._residual_nbits("ShardedTokenIndex.build_compressed", nbits)
+        if device is None:
+            device = C.device if C.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        C = C.to(device=device, dtype=torch.float16).contiguous()
+        cutoffs, weights, Doff = cutoffs.to(device), weights.to(device).contiguous(), Doff.to(device)
+        sumL = int(Doff[-1]) if Doff.numel() else 0
+        codes = torch.empty(sumL, dtype=torch.int32, device=device)
+        packed = torch.empty((sumL, 16 * nbits), dtype=torch.uint8, device=device)
+        at = 0
+        for blk in blocks:
+            blk = blk.to(device=device, dtype=torch.float16).contiguous()
+            n = blk.shape[0]
+            if at + n > sumL:
+                raise ValueError(f"ShardedTokenIndex.build_compressed: the blocks hold more than Doff[N] = {sumL} token rows")
+            if n:
+                codes[at: at + n] = ops.centroid_assign(blk, C)
+                ops.residual_compress(blk, codes[at: at + n], C, cutoffs, nbits, out=packed[at: at + n])
+            at += n
+        if at != sumL:
+            raise ValueError(f"ShardedTokenIndex.build_compressed: the blocks hold {at} token rows, Doff[N] = {sumL}")
+        self = cls(None, Doff, id_base, group=group, max_doc_len=max_doc_len)
+        self.centroids, self.codes = C, codes
+        self.candidates = ShardedCentroidIndex(ops.centroid_index(codes, Doff, C.shape[0]), self.id_base, group=group)
+        self.packed, self.cutoffs, self.weights, self.nbits = packed, cutoffs, weights, nbits
+        return self
+
+    def decompressed(self, row_lo: int = 0, row_hi: int | None = None) -> torch.Tensor:
+        """Rows [row_lo, row_hi) of the matrix a compressed shard scores against ([rows, 128] float16; ops.residual_decompress)."""
+        if self.packed is None:
+            raise ValueError("ShardedTokenIndex.decompressed: the shard is not compressed")
+        return ops.residual_decompress(self.packed, self.codes, self.centroids, self.weights, row_lo, row_hi)
+
+    def memory_bytes(self) -> dict:
+        """Resident bytes by part: the float16 tokens, the codes, the packed residuals, the candidate index (lists + slice table), and their
+        total.  The centroid and bucket tables are shared by every shard and not counted."""
+        size = lambda t: 0 if t is None else t.numel() * t.element_size()      # noqa: E731
+        ix = None if self.candidates is None else self.candidates.index
+        out = dict(tokens=size(self.Dtok), codes=size(self.codes), packed=size(self.packed),
+                   candidates=0 if ix is None else size(ix.coff) + size(ix.cdoc) + size(ix.slice_off))
+        out["total"] = sum(out.values())
+        return out
 
     @staticmethod
     def search_defaults(k: int) -> tuple[int, int]:
@@ -330,7 +412,10 @@ class ShardedTokenIndex:
 
     def local_scores(self, Qtok: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
         """[Q, k] float32: exact MaxSim of query q and candidate cand_ids[q, r]; -inf for a slot this shard does not own (r >= cand_len[q],
-        a negative id, a document of another shard)."""
+        a negative id, a document of another shard).  A compressed shard scores its decompressed rows (also when compress kept the tokens)."""
+        if self.packed is not None:
+            return ops.maxsim_pairs_residual(Qtok, self.packed, self.codes, self.centroids, self.weights, self.Doff, cand_ids, cand_len,
+                                             id_base=self.id_base, max_doc_len=self.max_doc_len)
         return ops.maxsim_pairs(Qtok, self.Dtok, self.Doff, cand_ids, cand_len, id_base=self.id_base, max_doc_len=self.max_doc_len)
 
     def rerank(self, Qtok: torch.Tensor, candidates, k: int | None = None):

@@ -1955,6 +1955,153 @@ def _centroid_source(index: CentroidIndex, pc, ps, Lq: int, nprobe: int, id_base
                    grain=centroid_slice_docs(), mark="shard_centroid_filter")
 
 
+# ---------------------------------------------------------------------------------------
+# K2c residual-compressed token rows (csrc/rerank_residual.hip; include/fusion_hip.h 'Residual-compressed token rows')
+# ---------------------------------------------------------------------------------------
+RESIDUAL_NBITS = (2, 4)
+RESIDUAL_SAMPLE = 131072     # token rows residual_buckets trains on by default
+
+
+def _residual_nbits(what: str, nbits) -> int:
+    nbits = int(nbits)
+    _need(nbits in RESIDUAL_NBITS, f"{what}: nbits must be one of {RESIDUAL_NBITS}, got {nbits}")
+    return nbits
+
+
+def _residual_table(what: str, C: torch.Tensor, codes: torch.Tensor, n: int) -> tuple[torch.Tensor, torch.Tensor]:
+    _dev(C, torch.float16, f"{what}(C)"); _dev(codes, torch.int32, f"{what}(codes)")
+    _need(C.dim() == 2 and C.shape[0] >= 1 and C.shape[1] == 128, f"{what}: C must be [K >= 1, 128], got {tuple(C.shape)}")
+    _need(codes.dim() == 1 and codes.numel() == n, f"{what}: codes must be [{n}] (one per token row), got {tuple(codes.shape)}")
+    return C.contiguous(), codes.contiguous()
+
+
+def _residual_packed(what: str, packed: torch.Tensor, weights: torch.Tensor) -> int:
+    _dev(packed, torch.uint8, f"{what}(packed)"); _dev(weights, torch.float16, f"{what}(weights)")
+    _need(packed.dim() == 2 and packed.shape[1] in (32, 64) and packed.is_contiguous(),
+          f"{what}: packed must be a contiguous [sumL, 16 * nbits] uint8 tensor, got {tuple(packed.shape)}")
+    nbits = packed.shape[1] // 16
+    _need(weights.dim() == 1 and weights.numel() == 1 << nbits and weights.is_contiguous(),
+          f"{what}: weights must be [{1 << nbits}] for rows of {packed.shape[1]} bytes, got {tuple(weights.shape)}")
+    return nbits
+
+
+def residual_check_codes(codes: torch.Tensor, K: int) -> None:
+    """ValueError unless every code lies in [0, K): done ONCE when an index is built (one host read).  The kernels clamp a stored code into
+    the table in any case, so a bad code can give a wrong score but never a wild address."""
+    if codes.numel():
+        lo, hi = int(codes.min()), int(codes.max())
+        _need(0 <= lo and hi < int(K), f"residual index: codes must lie in [0, {int(K)}), found {lo} .. {hi}")
+
+
+def residual_buckets(tokens: torch.Tensor, C: torch.Tensor, codes: torch.Tensor, nbits: int = 2, sample: int | None = None, seed: int = 0):
+    """(cutoffs [B - 1] float32, weights [B] float16), B = 2^nbits: the buckets of the residual code, trained on the float32 residuals
+    tok - C[code] of a seeded sample of token rows (default min(n, RESIDUAL_SAMPLE), drawn as kmeans_centroids draws its sample).  The m
+    sample values are sorted; cutoffs[i - 1] = sorted[(i m) // B - 1] (equal-population cuts: the 16-bucket cutoffs contain the 4-bucket
+    ones); weights[b] = the float64 mean of the sample values the bucket rule sends to b -- a contiguous run of the sorted sample --
+    rounded to float16; an empty bucket takes its lower cutoff, bucket 0 the upper one.  torch ops on the device, no float atomics:
+    deterministic for a given seed on a given device.  Multi-rank callers train on ONE rank and broadcast, as for the centroids."""
+    nbits = _residual_nbits("residual_buckets", nbits)
+    _dev(tokens, None, "residual_buckets(tokens)")
+    _need(tokens.dim() == 2 and tokens.shape[1] == 128 and tokens.dtype in (torch.float16, torch.float32) and tokens.shape[0] >= 1,
+          f"residual_buckets: tokens must be [n >= 1, 128] float16 or float32, got {tuple(tokens.shape)}")
+    n = tokens.shape[0]
+    C, codes = _residual_table("residual_buckets", C, codes, n)
+    gen = torch.Generator(device=tokens.device)
+    gen.manual_seed(int(seed))
+    perm = torch.randperm(n, generator=gen, device=tokens.device)
+    rows = perm[: min(n, RESIDUAL_SAMPLE if sample is None else max(1, int(sample)))]
+    code = codes[rows].long().clamp_(0, C.shape[0] - 1)
+    r = (tokens[rows].float() - C[code].float()).flatten()
+    r = r[~torch.isnan(r)]
+    srt, _ = torch.sort(r)
+    m, B = srt.numel(), 1 << nbits
+    _need(m >= B, f"residual_buckets: {m} sample values cannot train {B} buckets")
+    at = torch.tensor([(i * m) // B - 1 for i in range(1, B)], dtype=torch.int64, device=srt.device)
+    cutoffs = srt[at].contiguous()
+    # values with bucket <= i are those <= cutoffs[i]: the runs' ends in the sorted sample
+    ends = torch.searchsorted(srt, cutoffs, right=True).tolist()
+    bounds = [0] + ends + [m]
+    weights = torch.empty(B, dtype=torch.float64, device=srt.device)
+    for b in range(B):
+        s, e = bounds[b], bounds[b + 1]
+        weights[b] = srt[s:e].double().mean() if e > s else cutoffs[max(b - 1, 0)].double()
+    return cutoffs, weights.to(torch.float16)
+
+
+def residual_compress(tokens: torch.Tensor, codes: torch.Tensor, C: torch.Tensor, cutoffs: torch.Tensor, nbits: int = 2,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+    """packed [n, 16 * nbits] uint8 (fz_residual_compress_f16): per token row and dimension the bucket of float32(tok) - float32(C[code]),
+    bucket(r) = the number of cutoffs c with r > c, stored fragment-major (include/fusion_hip.h).  tokens [n, 128] float16, codes [n] int32
+    (centroid_assign), C [K, 128] float16, cutoffs [2^nbits - 1] float32 non-decreasing.  `out`: n rows of a larger packed tensor."""
+    nbits = _residual_nbits("residual_compress", nbits)
+    _dev(tokens, torch.float16, "residual_compress(tokens)")
+    _need(tokens.dim() == 2 and tokens.shape[1] == 128, f"residual_compress: tokens must be [n, 128], got {tuple(tokens.shape)}")
+    n = tokens.shape[0]
+    C, codes = _residual_table("residual_compress", C, codes, n)
+    _dev(cutoffs, torch.float32, "residual_compress(cutoffs)")
+    _need(cutoffs.dim() == 1 and cutoffs.numel() == (1 << nbits) - 1, f"residual_compress: cutoffs must be [{(1 << nbits) - 1}], got {tuple(cutoffs.shape)}")
+    tokens, cutoffs = tokens.contiguous(), cutoffs.contiguous()
+    if out is None:
+        out = torch.empty((n, 16 * nbits), dtype=torch.uint8, device=tokens.device)
+    else:
+        _dev(out, torch.uint8, "residual_compress(out)")
+        _need(tuple(out.shape) == (n, 16 * nbits) and out.is_contiguous(), f"residual_compress(out): a contiguous {(n, 16 * nbits)} tensor expected")
+    check(_lib.lib().fz_residual_compress_f16(_ptr(tokens), _ptr(codes), _ptr(C), _ptr(cutoffs), n, C.shape[0], 128, nbits, _ptr(out),
+                                              _stream(tokens)), "fz_residual_compress_f16")
+    return out
+
+
+def residual_decompress(packed: torch.Tensor, codes: torch.Tensor, C: torch.Tensor, weights: torch.Tensor, row_lo: int = 0,
+                        row_hi: int | None = None) -> torch.Tensor:
+    """D [row_hi - row_lo, 128] float16 (fz_residual_decompress_f16): D[t][j] = the float16 sum of C[code[t]][j] and weights[bucket[t][j]],
+    rows [row_lo, row_hi) of the shard (default: all).  ops.maxsim_pairs over D is, bit for bit, maxsim_pairs_residual over the bytes."""
+    nbits = _residual_packed("residual_decompress", packed, weights)
+    n = packed.shape[0]
+    C, codes = _residual_table("residual_decompress", C, codes, n)
+    row_lo, row_hi = int(row_lo), n if row_hi is None else int(row_hi)
+    _need(0 <= row_lo <= row_hi <= n, f"residual_decompress: rows [{row_lo}, {row_hi}) outside 0 .. {n}")
+    out = torch.empty((row_hi - row_lo, 128), dtype=torch.float16, device=packed.device)
+    check(_lib.lib().fz_residual_decompress_f16(_ptr(packed), _ptr(codes), _ptr(C), _ptr(weights), n, row_lo, row_hi, C.shape[0], 128, nbits,
+                                                _ptr(out), _stream(packed)), "fz_residual_decompress_f16")
+    return out
+
+
+def maxsim_pairs_residual(Qtok: torch.Tensor, packed: torch.Tensor, codes: torch.Tensor, C: torch.Tensor, weights: torch.Tensor,
+                          Doff: torch.Tensor, cand: torch.Tensor, cand_len: torch.Tensor | None = None, *, id_base: int = 0,
+                          max_doc_len: int = 512, out: torch.Tensor | None = None) -> torch.Tensor:
+    """maxsim_pairs over a residual-compressed shard (fz_maxsim_pairs_residual_f16): out[q, r] = what maxsim_pairs gives over
+    residual_decompress(packed, codes, C, weights), bit for bit, without that matrix ever existing.  packed [sumL, 16 * nbits] uint8,
+    codes [sumL] int32, C [K, 128] float16, weights [2^nbits] float16; everything else as maxsim_pairs.  No host synchronisation."""
+    what = "maxsim_pairs_residual"
+    _dev(Qtok, torch.float16, f"{what}(Qtok)")
+    nbits = _residual_packed(what, packed, weights)
+    sumL = packed.shape[0]
+    C, codes = _residual_table(what, C, codes, sumL)
+    _dev(Doff, torch.int64, f"{what}(Doff)")
+    _dev(cand, torch.int64, f"{what}(cand)")
+    _need(Qtok.dim() == 3, f"{what}: Qtok must be [Q, Lq, dim]")
+    Qtok, Doff = Qtok.contiguous(), Doff.contiguous()
+    Q, Lq, dim = Qtok.shape
+    N = Doff.numel() - 1
+    _need(dim == 128, f"{what}: Qtok must be [Q, Lq, 128]")
+    _need(Doff.dim() == 1 and N >= 0, f"{what}: Doff must hold N + 1 offsets")
+    _need(cand.dim() == 2 and cand.shape[0] == Q, f"{what}: cand must be [Q = {Q}, k], got {tuple(cand.shape)}")
+    k = cand.shape[1]
+    if cand_len is not None:
+        _dev(cand_len, torch.int32, f"{what}(cand_len)")
+        _need(tuple(cand_len.shape) == (Q,), f"{what}(cand_len): expected shape {(Q,)}, got {tuple(cand_len.shape)}")
+    if out is None:
+        out = alloc_plane(Q, k, torch.float32, Qtok.device)
+    else:
+        _dev(out, torch.float32, f"{what}(out)")
+        _need(tuple(out.shape) == (Q, k), f"{what}(out): expected shape {(Q, k)}, got {tuple(out.shape)}")
+    _need(int(max_doc_len) >= 1, f"{what}: max_doc_len must be at least 1")
+    check(_lib.lib().fz_maxsim_pairs_residual_f16(_ptr(Qtok), _ptr(packed), _ptr(codes), _ptr(C), _ptr(weights), C.shape[0], nbits, _ptr(Doff),
+                                                  sumL, int(max_doc_len), Q, Lq, N, dim, _ptr(cand), _ld(cand), _ptr(cand_len), k, int(id_base),
+                                                  _ptr(out), _ld(out), _stream(Qtok)), "fz_maxsim_pairs_residual_f16")
+    return out
+
+
 def f64_to_f32(src: torch.Tensor) -> torch.Tensor:
     """Plane-preserving fp64 -> fp32 (what torch.tensor(..., dtype=float32) does to BM25's Python floats, hybrid.py:255)."""
     _dev(src, torch.float64, "f64_to_f32")

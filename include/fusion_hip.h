@@ -552,6 +552,43 @@ int fz_centroid_scores_filter_f32(const int64_t* coff, const int32_t* cdoc, cons
                                   int Lq, int nprobe, int N, int K, int doc_lo, int doc_hi, int64_t id_base, const float* tau,
                                   float* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow, void* stream);
 
+/* ---- K2 at corpus scale, storage: residual-compressed token rows (csrc/rerank_residual.hip; ABI 20, additive) ---------------------------
+ * 'Residual-compressed token rows'.  A token row t is its centroid id codes[t] (int32, the codes of the candidate stage: the nearest of
+ * the K rows of C [K][128] float16) and, per dimension, the nbits-wide number of the bucket its residual falls in, nbits in {2, 4},
+ * B = 2^nbits buckets: 4 + 16 nbits bytes per token against 256.
+ *   buckets     cutoffs [B - 1] float32, non-decreasing; weights [B] float16.  bucket(r) = the number of cutoffs c with r > c: a residual
+ *               equal to a cutoff falls in the LOWER bucket, a NaN residual in bucket 0 (for finite r: torch.bucketize(r, cutoffs)).
+ *   compress    r = float32(tok[t][j]) - float32(C[code[t]][j]), one IEEE subtraction; b = bucket(r).
+ *   decompress  D[t][j] = the IEEE float16 sum, round to nearest even, denormals kept, of C[code[t]][j] and weights[b].  No
+ *               renormalisation: D is a fixed function of the stored bytes.
+ *   storage     packed [sumL][16 nbits] uint8, FRAGMENT-MAJOR (part of the ABI): storage position s in 0 .. 127 holds dimension
+ *                   32 ((s >> 3) & 3) + 8 (s >> 5) + (s & 7);
+ *               positions fill ascending bytes and, inside a byte, ascending bit fields (little-endian).  Lane (row l & 15, group
+ *               g = l >> 4) of the v_mfma_f32_16x16x32_f16 A operand so finds all four k-steps of a token -- dimensions 32 ks + 8 g + j
+ *               = positions 32 g + 8 ks + j -- in ONE aligned piece of the row: 8 bytes at offset 8 g (nbits = 2), 16 bytes at offset
+ *               16 g (nbits = 4).
+ *   score       fz_maxsim_pairs_residual_f16 gives, for every slot, exactly what fz_maxsim_pairs_f16 gives on D, bit for bit on any
+ *               input: the same MFMA mapping, fmaxf from -inf and summation tree, the same -inf / 0 / clamped-length / last-row rules.
+ * A stored code outside [0, K) is clamped into it by every kernel here (no address leaves the table whatever the bytes are); callers
+ * validate the code range once, when an index is built.  All three are streaming / gather kernels without workspace.
+ * fz_residual_compress_f16: packs rows 0 .. n-1 of tok [n][128] float16 with their codes [n] -> packed [n][16 nbits].
+ * fz_residual_decompress_f16: rows [row_lo, row_hi) of a shard of sumL rows -> out [row_hi - row_lo][128] float16 (packed and codes are
+ * the shard's arrays, indexed by the shard's row; out starts at row_lo): exports part of a shard, and is what the tests compare against.
+ * fz_maxsim_pairs_residual_f16: Doff, sumL, max_doc_len, Q, Lq, N, dim, cand, ldc, cand_len, k, id_base, scores and lds as in
+ * fz_maxsim_pairs_f16, with (packed, codes, C, weights, K, nbits) in the place of Dtok.
+ * Argument checks in fz_maxsim_pairs_f16's order: negative sizes, K < 1, a bad row range, ldc < k, lds < k or a null pointer where a
+ * non-empty tensor is needed -> FZ_ERR_ARG; dim != 128, nbits outside {2, 4}, Lq outside {32, 64, 128}, tok / packed / C / Qtok / out
+ * not 16-byte aligned, max_doc_len > 16384 -> FZ_ERR_UNSUPPORTED; nothing to do (n == 0, an empty row range, Q == 0 or k == 0) -> FZ_OK
+ * with nothing launched. */
+int fz_residual_compress_f16(const void* tok, const int32_t* codes, const void* C, const float* cutoffs, int64_t n, int K, int dim, int nbits,
+                             void* packed, void* stream);
+int fz_residual_decompress_f16(const void* packed, const int32_t* codes, const void* C, const void* weights, int64_t sumL, int64_t row_lo,
+                               int64_t row_hi, int K, int dim, int nbits, void* out, void* stream);
+int fz_maxsim_pairs_residual_f16(const void* Qtok, const void* packed, const int32_t* codes, const void* C, const void* weights, int K,
+                                 int nbits, const int64_t* Doff, int64_t sumL, int max_doc_len, int Q, int Lq, int N, int dim,
+                                 const int64_t* cand, int ldc, const int32_t* cand_len, int k, int64_t id_base, float* scores, int lds,
+                                 void* stream);
+
 /* ---- encoder side: the per-sequence parts of SentenceTransformer.encode (hybrid.py:97-102) on PACKED token rows -- */
 /* Self-attention of a BERT/CamemBERT layer for ragged sequences without padding: for every sequence and head,
  * out = softmax(q k^T * scale) v in fp32 (MFMA products, online softmax over 16-key tiles), scale > 0.  qkv [T][ld] = fused
