@@ -120,6 +120,10 @@ _PROTOS = {
     "fz_tfidf_scores_range_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "fz_bm25_filter_pv_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "fz_tfidf_filter_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "fz_bm25_doc_scores_pv_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "fz_tfidf_doc_scores_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "fz_bm25_count_pv_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _i, _vp, _vp]),
+    "fz_tfidf_count_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _i, _vp, _vp]),
     "fz_centroid_slice_docs": (_i, []),
     "fz_centroid_slice_offsets": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "fz_centroid_scores_range_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),

@@ -1,6 +1,8 @@
 // bm25_walk.h -- what the lexical posting walk of bm25.hip (the whole corpus) and its restatement in bm25_stream.hip (a range of documents)
 // must agree on: the modes, the table grain, the terms per batch and the workgroup shapes.  The walk itself is not shared: as one device
 // function called from both kernels it cost bm25_kernel registers and an occupancy step (profiles/r14_slices_refactor.json).
+// bm25_count.hip (the range walk with the counting epilogue) restates it a third time: moving lexical_range_kernel's walk into a
+// __forceinline__ function for the two files took its TF-IDF instantiations from 32 / 33 to 58 VGPRs (plane / filter; cross-compiled).
 #pragma once
 #include "slices.h"
 

@@ -1,7 +1,8 @@
 // slices.h -- what the "one workgroup = (query, slice of documents)" kernels over an inverted index have in common (bm25.hip,
-// bm25_stream.hip, sparse.hip, centroid.hip): the posting search, the per-index slice-offset table, the document range and its slice
-// bounds, and the two epilogues -- the score plane of the range, or the streaming top-k's threshold filter in its place.  A scorer
-// supplies its arguments, its walk (the per-posting reduction into the slice's LDS accumulators) and its slice size.
+// bm25_stream.hip, bm25_count.hip, sparse.hip, centroid.hip): the posting search, the per-index slice-offset table, the document range and
+// its slice bounds, and the epilogues -- the score plane of the range, the streaming top-k's threshold filter in its place, or (float64)
+// the count of the documents ranked before each of a few listed ones.  A scorer supplies its arguments, its walk (the per-posting
+// reduction into the slice's LDS accumulators) and its slice size.
 #pragma once
 #include "common.h"
 
@@ -101,6 +102,75 @@ __device__ __forceinline__ void filter_candidates(const T* acc, int n, int d0, i
         }
     }
     if (__any(over) && lane == 0) atomicExch(f.overflow, 1);                  // one per wave that dropped something
+}
+
+// What the counting epilogue compares against and adds to: per query G listed ("gold") documents, as (float64 score, global id) -- an id
+// < 0 skips the gold -- and counts [Q][G] int32, ADDED to (the caller zeroes it).  id_base: the id of index document 0.
+struct CountSink { const double* gold_scores; const int64_t* gold_ids; int32_t* counts; int G; int64_t id_base; };
+
+constexpr int COUNT_GROUP = 8;   // golds compared per pass over the accumulators, at most (registers: a key and a position each)
+
+// one register group of count_beaters: the ng <= GW golds gs / gi / out point at
+template <int GW>
+__device__ __forceinline__ void count_group(const double* acc, int n, int d0, const double* __restrict__ gs, const int64_t* __restrict__ gi,
+                                            int32_t* __restrict__ out, int ng, int64_t id_base) {
+    uint64_t gk[GW]; int gj[GW], cnt[GW];
+    bool inside = false;                                                  // a gold's id falls among this slice's: workgroup-uniform
+#pragma unroll
+    for (int u = 0; u < GW; ++u) {
+        gk[u] = 0ull; gj[u] = 0; cnt[u] = 0;                              // skipped / padding: key 0, which nothing is below
+        if (u < ng) {
+            const int64_t gid = gi[u];
+            if (gid >= 0) {
+                const int64_t at = gid - id_base - d0;                    // the gold's place in this slice, if it is one of its documents
+                gk[u] = desc_key_f64(gs[u]);
+                gj[u] = at < 0 ? 0 : (at > n ? n : (int)at);
+                inside |= gj[u] > 0 && gj[u] < n;
+            }
+        }
+    }
+    if (!inside) {
+        // every document's id is on one side of every gold's (the usual slice): "before" is key < gk, or key <= gk = key < gk + 1 where the
+        // ids are all lower (no key is 2^64 - 1: the largest, -inf's, is 0xfff0...0) -- one 64-bit compare per (document, gold)
+#pragma unroll
+        for (int u = 0; u < GW; ++u) gk[u] += gj[u] > 0 ? 1ull : 0ull;
+        for (int j = threadIdx.x; j < n; j += blockDim.x) {
+            const uint64_t k = desc_key_f64(acc[j]);
+#pragma unroll
+            for (int u = 0; u < GW; ++u) cnt[u] += k < gk[u] ? 1 : 0;
+        }
+    } else {
+        for (int j = threadIdx.x; j < n; j += blockDim.x) {
+            const uint64_t k = desc_key_f64(acc[j]);
+#pragma unroll
+            for (int u = 0; u < GW; ++u) cnt[u] += (k < gk[u] || (k == gk[u] && j < gj[u])) ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < GW; ++u) {
+        const int total = wave_reduce_sum(cnt[u]);
+        if ((threadIdx.x & 63) == 0 && total != 0) atomicAdd(out + u, total);   // (total != 0 only where u < ng)
+    }
+}
+
+// counting epilogue (float64 scores): counts[q][g] += the number of documents d0 + j, j < n, that the stable descending float64 ranking
+// (sort_rows_desc: desc_key_f64 ascending, ties to the ascending id) puts BEFORE gold g = (gs, gid): desc_key_f64(acc[j]) <
+// desc_key_f64(gs), or equal keys and id_base + d0 + j < gid.  The id test is j < clamp(gid - id_base - d0, 0, n): 32-bit inside the
+// slice, and right for a gold of another slice, range or shard (every j, or none); a gold never counts itself.  Golds in register groups
+// of at most COUNT_GROUP (1, 2, 4 or 8 wide: a query with one gold pays for one): acc is read once per group, the gold scores and ids are
+// uniform (scalar loads).  Per gold a lane-sum over the wave, then one atomicAdd per (wave, gold) with a non-zero count -- integer adds:
+// any grid, range split or run gives the same counts.  No LDS and no barrier of the epilogue's own.  Whole waves must reach this call.
+__device__ __forceinline__ void count_beaters(const double* acc, int n, int d0, int q, const CountSink& c) {
+    const double* gs = c.gold_scores + (size_t)q * c.G;
+    const int64_t* gi = c.gold_ids + (size_t)q * c.G;
+    int32_t* out = c.counts + (size_t)q * c.G;
+    for (int g0 = 0; g0 < c.G; g0 += COUNT_GROUP) {
+        const int ng = c.G - g0 < COUNT_GROUP ? c.G - g0 : COUNT_GROUP;
+        if (ng > 4) count_group<8>(acc, n, d0, gs + g0, gi + g0, out + g0, ng, c.id_base);
+        else if (ng > 2) count_group<4>(acc, n, d0, gs + g0, gi + g0, out + g0, ng, c.id_base);
+        else if (ng > 1) count_group<2>(acc, n, d0, gs + g0, gi + g0, out + g0, ng, c.id_base);
+        else count_group<1>(acc, n, d0, gs + g0, gi + g0, out + g0, ng, c.id_base);
+    }
 }
 
 }  // namespace fz

@@ -224,6 +224,26 @@ class ShardedLexicalIndex:
         if mark: mark("allgather_merge")
         return RankedTopk.from_search(s.to(torch.float32), i, scores64=s)
 
+    def gold_ranks(self, queries: list[str], gold_ids) -> torch.Tensor:
+        """[Q, G] int64: the rank of global id gold_ids[q, g] in query q's ranking of the WHOLE corpus (what the grid search needs of it),
+        the same on every rank; an id < 0 gives -1.  Every shard scores the golds it holds (-inf for the others: all_reduce(MAX) leaves each
+        gold's score), counts its own documents ranked before each gold (the model's count_before), and the counts add: all_reduce(SUM).
+        With the merged statistics a document scores the same in any shard, so the sums are the whole index's ranks for any number of
+        shards.  The ids must be documents of the corpus."""
+        import torch.distributed as dist
+        m = self.model
+        gi = torch.as_tensor(gold_ids).to(device=m.device, dtype=torch.int64)
+        local = gi - self.id_base
+        mine = (gi >= 0) & (local >= 0) & (local < m.corpus_size)
+        many = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
+        sc = m.doc_scores(queries, torch.where(mine, local, -1))
+        if many:
+            dist.all_reduce(sc, op=dist.ReduceOp.MAX, group=self.group)
+        counts = m.count_before(queries, sc, gi)
+        if many:
+            dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
+        return torch.where(gi >= 0, counts, -1)
+
 
 class ShardedCentroidIndex(_ShardedIndex):
     """The candidate stage of one rank's ColBERT shard: an ops.CentroidIndex (per centroid the shard's documents that carry it, documents

@@ -1494,6 +1494,54 @@ def lexical_filter(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: in
               "fz_tfidf_filter_f64")
 
 
+def _query_blocks(Q: int, block: int):
+    return ((lo, min(Q, lo + block)) for lo in range(0, Q, block))
+
+
+def lexical_doc_scores(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int, docs: torch.Tensor, block: int = 1024) -> torch.Tensor:
+    """[Q, G] float64: the score the lexical walks give document docs[q, g] (int32 position in the index) for query q, with the bits of the
+    full plane's entry (fz_bm25_doc_scores_pv_f64 / fz_tfidf_doc_scores_f64: a binary search per query term, the walk's chain of adds).
+    A position < 0 (or >= N) gives -inf: not a document of this index.  Queries in blocks of `block`."""
+    what = "lexical_doc_scores"
+    _lexical_args(what, mode, toff, pdoc, vals, idf, qoff, qterms, Q, N, 0, None, None)
+    _need(_dev(docs, torch.int32, f"{what}(docs)").is_contiguous() and docs.dim() == 2 and docs.shape[0] == Q and docs.shape[1] >= 1,
+          f"{what}: docs must be a contiguous [Q, G >= 1] int32 tensor")
+    G, lib = docs.shape[1], _lib.lib()
+    out = torch.empty((Q, G), dtype=torch.float64, device=toff.device)
+    for lo, hi in _query_blocks(Q, block):
+        if mode == "pv":
+            check(lib.fz_bm25_doc_scores_pv_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(qoff[lo:]), _ptr(qterms), hi - lo, N, _ptr(docs[lo:]), G,
+                                                _ptr(out[lo:]), _stream(toff)), "fz_bm25_doc_scores_pv_f64")
+        else:
+            check(lib.fz_tfidf_doc_scores_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(idf), _ptr(qoff[lo:]), _ptr(qterms), hi - lo, N, _ptr(docs[lo:]),
+                                              G, _ptr(out[lo:]), _stream(toff)), "fz_tfidf_doc_scores_f64")
+    return out
+
+
+def lexical_count(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int, doc_lo: int, doc_hi, id_base: int, gold_scores, gold_ids,
+                  counts: torch.Tensor, slice_off: torch.Tensor | None = None, block: int = 1024) -> None:
+    """The range walk with the counting epilogue (fz_bm25_count_pv_f64 / fz_tfidf_count_f64): counts [Q, G] int32 += per (query, gold) the
+    number of documents d of [doc_lo, doc_hi) that the stable float64 ranking puts before the gold (gold_scores [Q, G] float64, gold_ids
+    [Q, G] int64 global ids, < 0: skipped): a better score, or the same and id_base + d < the gold's id.  Counts over disjoint ranges (and
+    shards) add up to the rank.  vals: pval ('pv') or ptf ('tfidf', with idf).  Queries in blocks of `block` (grid y)."""
+    what = "lexical_count"
+    doc_lo, doc_hi = _lexical_args(what, mode, toff, pdoc, vals, idf, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
+    _dev(gold_scores, torch.float64, f"{what}(gold_scores)"); _dev(gold_ids, torch.int64, f"{what}(gold_ids)"); _dev(counts, torch.int32, f"{what}(counts)")
+    G = gold_scores.shape[1] if gold_scores.dim() == 2 else 0
+    _need(G >= 1 and all(t.is_contiguous() and tuple(t.shape) == (Q, G) for t in (gold_scores, gold_ids, counts)),
+          f"{what}: gold_scores, gold_ids and counts must be contiguous [Q, G >= 1] tensors")
+    lib = _lib.lib()
+    for lo, hi in _query_blocks(Q, block):
+        if mode == "pv":
+            check(lib.fz_bm25_count_pv_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(slice_off), _ptr(qoff[lo:]), _ptr(qterms), hi - lo, N, doc_lo, doc_hi,
+                                           int(id_base), _ptr(gold_scores[lo:]), _ptr(gold_ids[lo:]), G, _ptr(counts[lo:]), _stream(toff)),
+                  "fz_bm25_count_pv_f64")
+        else:
+            check(lib.fz_tfidf_count_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(idf), _ptr(slice_off), _ptr(qoff[lo:]), _ptr(qterms), hi - lo, N, doc_lo,
+                                         doc_hi, int(id_base), _ptr(gold_scores[lo:]), _ptr(gold_ids[lo:]), G, _ptr(counts[lo:]), _stream(toff)),
+                  "fz_tfidf_count_f64")
+
+
 def _lexical_source(model, qoff, qterms, id_base: int) -> _Source:
     """The lexical posting walk whose epilogue is the filter (TopkStream64): document d of the model's index = id id_base + d.  model: a
     retrievers.bm25 TFIDF / BM25 / AtireBM25 whose lexical_mode() is 'pv' or 'tfidf' (lexical_tables(): the walk's per-posting values and idf)."""

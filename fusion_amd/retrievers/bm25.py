@@ -9,7 +9,8 @@ Python loops (tests/golden/bm25.json, bm25_family.json -- outputs of the referen
 
 The grid search (`BM25.tune`) is to BM25 what `Aggregator.tune` is to the fusion weights: the index and the queries' postings stay
 resident, each of the 187 (k1, b) pairs is one norm pass + one scoring launch + one row sort, and only the ranks of the gold documents
-come back -- every metric of bm25.py:223,230 is a function of them.
+come back -- every metric of bm25.py:223,230 is a function of them.  Past one sort row there is no plane and no sort either: a gold
+document's rank is the count of the documents ranked before it, taken on the posting walk (csrc/bm25_count.hip, `gold_ranks`).
 
 Reference defects in the driver, not reproduced (documented in DESIGN.md):
   * bm25.py:235 `scores.pop('recall')` raises KeyError with the Metrics of src/utils/metrics.py (its results are flat), :236
@@ -309,6 +310,73 @@ class TFIDF:
             self.last_overflow += redone
         return sc64, ids
 
+    # -- ranks of listed documents as counts on the posting walk (csrc/bm25_count.hip): no plane, no list, no sort --
+    def _walk_tables(self, what: str):
+        mode = self.lexical_mode()
+        if mode is None:
+            raise ValueError(f"{what}: this model's scoring has no range walk (no postings, or BM25.USE_POSTING_VALUES = False)")
+        return (mode,) + tuple(self.lexical_tables())
+
+    def _gold_plane(self, what: str, t, Q: int, dtype) -> torch.Tensor:
+        t = torch.as_tensor(t).to(device=self.device, dtype=dtype)
+        if t.dim() != 2 or t.shape[0] != Q or t.shape[1] < 1:
+            raise ValueError(f"{what}: expected a [Q = {Q}, G >= 1] array, got {tuple(t.shape)}")
+        return t.contiguous()
+
+    def doc_scores(self, queries: list[str], positions) -> torch.Tensor:
+        """[Q, G] float64: scores()[q, positions[q, g]] bit for bit, without the plane (one binary search per query term and listed
+        document).  A position of -1 -- not a document of this index -- gives -inf."""
+        Q = len(queries)
+        pos = self._gold_plane("doc_scores(positions)", positions, Q, torch.int64)
+        if Q == 0:
+            return torch.empty(tuple(pos.shape), dtype=torch.float64, device=self.device)
+        if not (isinstance(positions, torch.Tensor) and positions.is_cuda):      # (a device tensor is not read back: the kernel gives -inf)
+            host = np.asarray(torch.as_tensor(positions))
+            if host.size and (host.max() >= self.corpus_size or host.min() < -1):
+                raise ValueError(f"doc_scores: positions must be -1 or in [0, {self.corpus_size})")
+        mode, vals, idf = self._walk_tables("doc_scores")
+        qoff, flat = self._query_csr(queries)
+        return ops.lexical_doc_scores(mode, self.toff, self.pdoc, vals, idf, qoff, flat, Q, self.corpus_size, pos.to(torch.int32),
+                                      block=self.STREAM_QUERIES)
+
+    def count_before(self, queries: list[str], gold_scores, gold_ids, counts: torch.Tensor | None = None) -> torch.Tensor:
+        """[Q, G] int64: for every (query, gold) the number of THIS index's documents that the stable descending float64 ranking puts
+        before the gold -- gold_scores [Q, G] float64, gold_ids [Q, G] int64 GLOBAL ids (this index's documents are id_base ..
+        id_base + N - 1; the gold may be another shard's; an id < 0 is skipped: its count stays).  A document precedes a gold when its score
+        ranks before the gold's, or equals it and its id is lower.  counts: added to and returned (shards, or several indexes, sum into
+        one tensor); default zeros.  One count launch per CHUNK documents (int32 on the device), summed in int64."""
+        Q = len(queries)
+        gs = self._gold_plane("count_before(gold_scores)", gold_scores, Q, torch.float64)
+        gi = self._gold_plane("count_before(gold_ids)", gold_ids, Q, torch.int64)
+        if gs.shape != gi.shape:
+            raise ValueError("count_before: gold_scores and gold_ids differ in shape")
+        if counts is None:
+            counts = torch.zeros(tuple(gs.shape), dtype=torch.int64, device=self.device)
+        elif counts.dtype != torch.int64 or counts.shape != gs.shape or counts.device != gs.device:
+            raise ValueError("count_before: counts must be an int64 tensor of the golds' shape on the model's device")
+        N = self.corpus_size
+        if Q == 0 or N == 0:
+            return counts
+        mode, vals, idf = self._walk_tables("count_before")
+        qoff, flat = self._query_csr(queries)
+        chunk = ops.stream_chunk(self.CHUNK, ops.lexical_slice_docs(mode))
+        part = torch.empty(tuple(gs.shape), dtype=torch.int32, device=self.device)
+        for lo in range(0, N, chunk):
+            part.zero_()
+            ops.lexical_count(mode, self.toff, self.pdoc, vals, idf, qoff, flat, Q, N, lo, min(N, lo + chunk), self.id_base, gs, gi, part,
+                              slice_off=self.slice_off, block=self.STREAM_QUERIES)
+            counts += part
+        return counts
+
+    def gold_ranks(self, queries: list[str], positions) -> torch.Tensor:
+        """[Q, G] int64: the rank of document positions[q, g] in query q's full ranking (search_device(queries).rank gathered at the
+        positions), for a corpus of any size: the document's score, then the count of the documents ranked before it.  -1 -> -1."""
+        Q = len(queries)
+        pos = self._gold_plane("gold_ranks(positions)", positions, Q, torch.int64)
+        sc = self.doc_scores(queries, pos)
+        ids = torch.where(pos >= 0, pos + self.id_base, -1)
+        return torch.where(pos >= 0, self.count_before(queries, sc, ids), -1)
+
     def _query_step(self, k: int, budget_bytes: int) -> int:
         """Queries per chunk whose planes fit budget_bytes (at least one)."""
         N, W = self.corpus_size, ops.sort_max_n(torch.float64)
@@ -378,6 +446,7 @@ class BM25(TFIDF):
     (can be <= 0), avgdl = statistics.mean(doc_len)."""
 
     USE_POSTING_VALUES = True   # False: the per-posting expression (fz_bm25_scores_f64_f32): A/B runs and tests of the two forms
+    last_tune_path = None       # of the last tune: 'count' | 'plane'
 
     def __init__(self, corpus: list[str], k1: float, b: float, device="cuda", slice_table_max_bytes: int | None = None,
                  stats: LexicalStats | None = None, id_base: int = 0):
@@ -425,7 +494,8 @@ class BM25(TFIDF):
 
     # -- the grid search of bm25.py:221-237 on the device --------------------------------------------------------------
     def tune(self, queries: list[str], labels: list[list], ids=None, k1_range=None, b_range=None,
-             recall_at_k=(10, 100, 200, 500, 1000), top_k: int = 1000, budget_bytes: int = DEVICE_BUDGET_BYTES) -> list[dict]:
+             recall_at_k=(10, 100, 200, 500, 1000), top_k: int = 1000, budget_bytes: int = DEVICE_BUDGET_BYTES,
+             counting: bool | None = None) -> list[dict]:
         """For every (k1, b) of itertools.product(k1_range, b_range) (bm25.py:226-228): what
         `update_params(k1, b); search_all(queries, top_k); Metrics(recall_at_k).compute_all_metrics(labels, ids of the lists)` reports
         (bm25.py:231-234) -- recall@k for the given cut-offs and r-precision -- as one dict per pair: {'k1', 'b', 'recall@10', ...}.
@@ -433,7 +503,12 @@ class BM25(TFIDF):
         rank >= top_k was cut from the list: never retrieved) come back.  ids: corpus position -> dataset id (idx2id, bm25.py:214).
         The queries are taken in chunks whose planes fit budget_bytes, as in ranked_positions; a corpus longer than one sort row is cut to
         its first top_k entries (_top_positions), not ranked in full: a gold document's rank is its place in that head, or none.
-        The model's own k1 / b are restored afterwards."""
+
+        counting: True -- no plane either, wherever the model has a range walk: a gold document's rank is the COUNT of the documents ranked
+        before it (gold_ranks: its score by binary search, then the posting walk with the counting epilogue, csrc/bm25_count.hip), the same
+        ranks and therefore the same dicts.  False -- the plane route above.  None: count when N exceeds one float64 sort row, i.e. exactly
+        where the plane route cuts instead of ranking.  USE_POSTING_VALUES = False (no range walk) keeps the plane route.  last_tune_path
+        records 'count' or 'plane'.  The model's own k1 / b are restored afterwards."""
         from ..utils.metrics import metrics_from_gold_ranks
         k1_range = np.arange(0., 8.5, 0.5) if k1_range is None else k1_range      # bm25.py:226
         b_range = np.arange(0., 1.1, 0.1) if b_range is None else b_range        # bm25.py:227
@@ -455,8 +530,16 @@ class BM25(TFIDF):
         step = self._query_step(k, budget_bytes)
         keep = (self.k1, self.b)
         got = torch.full((len(combos), Q, G), k, dtype=torch.int64, device=self.device)   # k: not among the first top_k
+        if counting is None:
+            counting = N > W
+        counting = bool(counting) and self.lexical_mode() is not None and Q > 0 and k > 0
+        self.last_tune_path = "count" if counting else "plane"
+        gp_pos = torch.from_numpy(gp).to(self.device) if counting else None              # -1: not in the corpus
         for w, (k1, b) in enumerate(combos):
             self.update_params(k1, b)
+            if counting:
+                got[w] = self.gold_ranks(queries, gp_pos)                  # full ranks: one at or past k was cut from the list (below)
+                continue
             for lo in range(0, Q if k else 0, step):
                 chunk = queries[lo:lo + step]
                 g = gp_dev[lo:lo + len(chunk)]

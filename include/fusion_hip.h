@@ -525,6 +525,30 @@ int fz_tfidf_filter_f64(const int64_t* toff, const int32_t* pdoc, const int32_t*
                         const double* tau, double* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow,
                         void* stream);
 
+/* ---- A1's grid search at corpus scale: the ranks of listed documents as counts on the posting walk (csrc/bm25_count.hip; ABI 20, additive) ----
+ * Every metric of the k1 x b sweep (bm25.py:221-237) is a function of the gold documents' ranks, and a rank is a count:
+ * rank(g) = #{ d : d is ranked before g } in the stable descending float64 ranking (ties to the ascending id) -- no plane, list or sort.
+ * fz_*_doc_scores_*: docs [Q][G] int32 positions in this index -> out [Q][G] float64, the score the walks above give that document for that
+ * query, bit for bit (the same chain of adds, found by binary search in each query term's postings); a position < 0 or >= N gives -inf
+ * (so shards combine with one MAX).  Checks, in this order: Q < 0, N < 0 or G < 1 -> FZ_ERR_ARG; Q == 0 -> FZ_OK; then null pointers. */
+int fz_bm25_doc_scores_pv_f64(const int64_t* toff, const int32_t* pdoc, const double* pval, const int64_t* qoff, const int32_t* qterms, int Q,
+                              int N, const int32_t* docs, int G, double* out, void* stream);
+int fz_tfidf_doc_scores_f64(const int64_t* toff, const int32_t* pdoc, const int32_t* ptf, const double* idf, const int64_t* qoff,
+                            const int32_t* qterms, int Q, int N, const int32_t* docs, int G, double* out, void* stream);
+/* fz_*_count_*: the range walks above (same range rules, same slice_off) with a counting epilogue.  gold_scores [Q][G] float64 and gold_ids
+ * [Q][G] int64 (global ids; < 0: skip this gold) name G documents per query; counts [Q][G] int32 is ADDED to (the caller zeroes it):
+ * counts[q][g] += the number of documents d of [doc_lo, doc_hi), with id i = id_base + d and score s, such that s ranks before the gold's
+ * score (the float64 sort's key order: descending, -0.0 == +0.0, NaN first), or equals it with i < gold_ids[q][g].  The gold may lie
+ * anywhere -- in the range, elsewhere in the index, in another shard; it never counts itself.  Integer adds only: counts over disjoint
+ * ranges, chunks and shards sum to the rank, identically in every run.  Checks, in this order: Q < 0, a bad range or G < 1 -> FZ_ERR_ARG;
+ * Q == 0 or an empty range -> FZ_OK, nothing launched; then null pointers (every array but slice_off) -> FZ_ERR_ARG. */
+int fz_bm25_count_pv_f64(const int64_t* toff, const int32_t* pdoc, const double* pval, const int64_t* slice_off, const int64_t* qoff,
+                         const int32_t* qterms, int Q, int N, int doc_lo, int doc_hi, int64_t id_base, const double* gold_scores,
+                         const int64_t* gold_ids, int G, int32_t* counts, void* stream);
+int fz_tfidf_count_f64(const int64_t* toff, const int32_t* pdoc, const int32_t* ptf, const double* idf, const int64_t* slice_off,
+                       const int64_t* qoff, const int32_t* qterms, int Q, int N, int doc_lo, int doc_hi, int64_t id_base,
+                       const double* gold_scores, const int64_t* gold_ids, int G, int32_t* counts, void* stream);
+
 /* ---- K2 at corpus scale, first stage: candidate scores from token centroids (csrc/centroid.hip; ABI 20, additive) ------------------------
  * Ranker.multi_vector_search (hybrid.py:108-137) is a first-stage search: colbert-ai generates candidates from token centroids and scores
  * them exactly (fz_maxsim_pairs_f16 is the exact part).  Every document token carries the id of its nearest of K centroids; the index
