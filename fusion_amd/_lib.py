@@ -52,6 +52,8 @@ _PROTOS = {
     "fz_residual_compress_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
     "fz_residual_decompress_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp]),
     "fz_maxsim_pairs_residual_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
+    "fz_dot_pairs_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
+    "fz_sparse_dot_pairs_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
     "fz_sort_max_n": (_i, []),
     "fz_sort_max_n_f64": (_i, []),
     "fz_sort_workspace_bytes": (_sz, [_i, _i, _i]),

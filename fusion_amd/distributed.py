@@ -62,6 +62,52 @@ def allgather_topk(local_scores: torch.Tensor, local_ids: torch.Tensor, group=No
     return merge_fn(gs, gi)
 
 
+def _reduce_max(plane: torch.Tensor, group=None) -> torch.Tensor:
+    """Shards' pair planes -> everyone's: a slot a shard does not own holds -inf, so ONE all_reduce(MAX) leaves every slot its owner's score."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        plane = plane.contiguous()      # the collective takes the [Q, W] block, not the padded plane
+        dist.all_reduce(plane, op=dist.ReduceOp.MAX, group=group)
+    return plane
+
+
+def rank_order(ids: torch.Tensor, scores: torch.Tensor, row_len: torch.Tensor | None = None) -> torch.Tensor:
+    """[Q, k0] int64: the columns of every row in (score desc, id asc) order -- one id sort gives the incoming sequence, the stable
+    descending row sort (ops.sort_rows_desc; float32 or float64 scores) does the rest.  row_len [Q] int32: only the first row_len[q]
+    columns of row q take part; the rest of its order is -1."""
+    key = ids
+    if row_len is not None:      # columns past a row's length go last in the sequence, where the sort does not look
+        past = torch.arange(ids.shape[1], device=ids.device)[None, :] >= row_len[:, None]
+        key = ids.masked_fill(past, torch.iinfo(torch.int64).max)
+    by_id = torch.argsort(key, dim=1, stable=True).to(torch.int32)
+    order, _, _ = ops.sort_rows_desc(scores, init_order=by_id, row_len=row_len, want_keys=False)
+    return order.long()
+
+
+def rank_pairs(ids: torch.Tensor, scores: torch.Tensor, k: int | None = None):
+    """Candidate ids [Q, k0] int64 and their (reduced) pair scores [Q, k0], float32 or float64 -> planes.RankedTopk of the candidates in
+    (score desc, global id asc) order, the order of every corpus-scale search here, cut to the first k.  A slot no shard owned (-inf) goes
+    last as (-inf, -1); lens counts the others.  float64 scores are ranked as float64 and kept as scores64 (scores = their float32 roundings)."""
+    from .planes import RankedTopk
+    Q, k0 = ids.shape
+    k = k0 if k is None else max(0, min(int(k), k0))
+    wide = scores.dtype == torch.float64
+    if Q == 0 or k0 == 0:
+        s32 = torch.empty((Q, k), dtype=torch.float32, device=ids.device)
+        return RankedTopk(ids=ids[:, :k].clone(), scores=s32, lens=torch.zeros(Q, dtype=torch.int32, device=ids.device),
+                          scores64=s32.double() if wide else None)
+    order = rank_order(ids, scores)[:, :k]
+    ss = torch.gather(scores, 1, order)                      # the scores' own bits (the sort's key plane canonicalises -0.0 and NaN)
+    owned = ss != float("-inf")
+    out_ids = torch.where(owned, torch.gather(ids, 1, order), torch.full_like(order, -1))
+    return RankedTopk(ids=out_ids, scores=ss.to(torch.float32), lens=owned.sum(1, dtype=torch.int32), scores64=ss if wide else None)
+
+
+def _candidates(candidates):
+    from .planes import RankedTopk
+    return (candidates.ids, candidates.lens) if isinstance(candidates, RankedTopk) else (candidates, None)
+
+
 class _ShardedIndex:
     """One rank's shard of a corpus + the chunked score -> top-k search over it; a subclass supplies its constants and the scoring source of its
     shard for a set of queries (_source: what ops.TopkStream is fed from).  The first head_docs(k) documents are scored into a plane and get an
@@ -165,6 +211,20 @@ class ShardedDenseIndex(_ShardedIndex):
     def search(self, Qn: torch.Tensor, k: int = 1000, mark=None):
         return self._search((Qn,), k, mark)
 
+    def local_pair_scores(self, Qn: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
+        """[Q, W] float32: the GEMM's score of query q and candidate cand_ids[q, r], bit for bit, without the plane (ops.dot_pairs)."""
+        return ops.dot_pairs(Qn, self.Dn, cand_ids, cand_len, id_base=self.id_base)
+
+    def pair_scores(self, Qn: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
+        """local_pair_scores for the whole corpus: a slot this shard does not own holds -inf, one all_reduce(MAX) over the group."""
+        return _reduce_max(self.local_pair_scores(Qn, cand_ids, cand_len), self.group)
+
+    def rerank(self, Qn: torch.Tensor, candidates, k: int | None = None):
+        """candidates (a planes.RankedTopk: its ids and lens; or a [Q, k0] int64 id tensor, negative ids = padding) -> RankedTopk of the
+        candidates by their exact scores, in (score desc, global id asc) order, cut to the first k (rank_pairs)."""
+        ids, cand_len = _candidates(candidates)
+        return rank_pairs(ids, self.pair_scores(Qn, ids, cand_len), k)
+
 
 class ShardedSparseIndex(_ShardedIndex):
     """One rank's shard of a SPLADE corpus as an inverted index (ops.SparseIndex, documents 0 .. N-1 = global ids id_base ..) + the
@@ -191,6 +251,22 @@ class ShardedSparseIndex(_ShardedIndex):
 
     def search(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, k: int = 1000, mark=None):
         return self._search((qoff, qterms, qw), k, mark)
+
+    def local_pair_scores(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, cand_ids: torch.Tensor,
+                          cand_len: torch.Tensor | None = None) -> torch.Tensor:
+        """[Q, W] float32: the posting walk's score of query q and candidate cand_ids[q, r], bit for bit, without the plane
+        (ops.sparse_dot_pairs)."""
+        return ops.sparse_dot_pairs(self.index, qoff, qterms, qw, cand_ids, cand_len, id_base=self.id_base)
+
+    def pair_scores(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, cand_ids: torch.Tensor,
+                    cand_len: torch.Tensor | None = None) -> torch.Tensor:
+        """local_pair_scores for the whole corpus: one all_reduce(MAX) over the group."""
+        return _reduce_max(self.local_pair_scores(qoff, qterms, qw, cand_ids, cand_len), self.group)
+
+    def rerank(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, candidates, k: int | None = None):
+        """As ShardedDenseIndex.rerank, for the queries' term lists."""
+        ids, cand_len = _candidates(candidates)
+        return rank_pairs(ids, self.pair_scores(qoff, qterms, qw, ids, cand_len), k)
 
 
 class ShardedLexicalIndex:
@@ -223,6 +299,30 @@ class ShardedLexicalIndex:
         s, i = allgather_topk(s, i, group=self.group, merge_fn=ops.topk_merge64)
         if mark: mark("allgather_merge")
         return RankedTopk.from_search(s.to(torch.float32), i, scores64=s)
+
+    def local_pair_scores(self, queries: list[str], cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
+        """[Q, W] float64: the model's score of query q and candidate cand_ids[q, r] (model.doc_scores on the positions id - id_base: the
+        bits of the full plane's entry); -inf for a slot this shard does not own."""
+        m = self.model
+        ci = torch.as_tensor(cand_ids).to(device=m.device, dtype=torch.int64)
+        if ci.dim() != 2 or ci.shape[0] != len(queries):
+            raise ValueError(f"ShardedLexicalIndex.pair_scores: cand_ids must be [Q = {len(queries)}, W], got {tuple(ci.shape)}")
+        if ci.numel() == 0:
+            return torch.empty(tuple(ci.shape), dtype=torch.float64, device=m.device)
+        local = ci - self.id_base
+        mine = (ci >= 0) & (local >= 0) & (local < m.corpus_size)
+        if cand_len is not None:
+            mine &= torch.arange(ci.shape[1], device=m.device)[None, :] < cand_len.to(m.device)[:, None]
+        return m.doc_scores(queries, torch.where(mine, local, -1))
+
+    def pair_scores(self, queries: list[str], cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
+        """local_pair_scores for the whole corpus (float64): one all_reduce(MAX) over the group, as gold_ranks combines its golds' scores."""
+        return _reduce_max(self.local_pair_scores(queries, cand_ids, cand_len), self.group)
+
+    def rerank(self, queries: list[str], candidates, k: int | None = None):
+        """As ShardedDenseIndex.rerank; ranked by the float64 scores, which the result keeps as scores64."""
+        ids, cand_len = _candidates(candidates)
+        return rank_pairs(ids, self.pair_scores(queries, ids, cand_len), k)
 
     def gold_ranks(self, queries: list[str], gold_ids) -> torch.Tensor:
         """[Q, G] int64: the rank of global id gold_ids[q, g] in query q's ranking of the WHOLE corpus (what the grid search needs of it),
@@ -437,6 +537,10 @@ class ShardedTokenIndex:
             return ops.maxsim_pairs_residual(Qtok, self.packed, self.codes, self.centroids, self.weights, self.Doff, cand_ids, cand_len,
                                              id_base=self.id_base, max_doc_len=self.max_doc_len)
         return ops.maxsim_pairs(Qtok, self.Dtok, self.Doff, cand_ids, cand_len, id_base=self.id_base, max_doc_len=self.max_doc_len)
+
+    def pair_scores(self, Qtok: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
+        """[Q, W] float32: local_scores for the whole corpus -- the shards' planes under one all_reduce(MAX), as inside rerank."""
+        return _reduce_max(self.local_scores(Qtok, cand_ids, cand_len), self.group)
 
     def rerank(self, Qtok: torch.Tensor, candidates, k: int | None = None):
         """candidates: a planes.RankedTopk (its ids and lens are used) or a [Q, k0] int64 id tensor (negative ids = padding) -> RankedTopk of

@@ -216,6 +216,43 @@ def cos_scores(Qe: torch.Tensor, De: torch.Tensor) -> torch.Tensor:
     return dot_scores(normalize_rows(Qe), normalize_rows(De))
 
 
+def _pairs_args(what: str, Q: int, dev, cand: torch.Tensor, cand_len, out):
+    """The candidate side of the pair scorers: cand [Q, W] int64 (rows may be strided), cand_len [Q] int32 or None, out [Q, W] float32 or
+    None (allocated).  -> (cand_len, out, W)."""
+    _dev(cand, torch.int64, f"{what}(cand)")
+    _need(cand.dim() == 2 and cand.shape[0] == Q, f"{what}: cand must be [Q = {Q}, W], got {tuple(cand.shape)}")
+    W = cand.shape[1]
+    if cand_len is not None:
+        _dev(cand_len, torch.int32, f"{what}(cand_len)")
+        _need(tuple(cand_len.shape) == (Q,), f"{what}(cand_len): expected shape {(Q,)}, got {tuple(cand_len.shape)}")
+    if out is None:
+        out = alloc_plane(Q, W, torch.float32, dev)
+    else:
+        _dev(out, torch.float32, f"{what}(out)")
+        _need(tuple(out.shape) == (Q, W), f"{what}(out): expected shape {(Q, W)}, got {tuple(out.shape)}")
+    return cand_len, out, W
+
+
+def dot_pairs(Qn: torch.Tensor, Dn: torch.Tensor, cand: torch.Tensor, cand_len: torch.Tensor | None = None, *, id_base: int = 0,
+              out: torch.Tensor | None = None) -> torch.Tensor:
+    """Dot products of every query with its own candidates (fz_dot_pairs_f32): out[q, r] = dot_scores(Qn, Dn)[q, cand[q, r] - id_base],
+    bit for bit, with no [Q, N] plane.  Qn [Q, d], Dn [N, d] float32; cand [Q, W] int64 global ids (rows may be strided), cand_len [Q]
+    int32 or None (= W everywhere).  -inf where r >= cand_len[q], the id is negative or the document is not one of this shard's N
+    (id_base .. id_base + N - 1).  `out` [Q, W] float32 may be a view of a wider plane: only its W columns are written.  No host
+    synchronisation."""
+    _dev(Qn, torch.float32, "dot_pairs(Qn)")
+    _dev(Dn, torch.float32, "dot_pairs(Dn)")
+    _need(Qn.dim() == 2 and Dn.dim() == 2, "dot_pairs: Qn [Q, d] and Dn [N, d] expected")
+    Qn, Dn = pad_dim(Qn), pad_dim(Dn)
+    if Qn.shape[1] != Dn.shape[1]:
+        raise ValueError(f"embedding dims differ: {Qn.shape[1]} vs {Dn.shape[1]}")
+    Q, N, d = Qn.shape[0], Dn.shape[0], Qn.shape[1]
+    cand_len, out, W = _pairs_args("dot_pairs", Q, Qn.device, cand, cand_len, out)
+    check(_lib.lib().fz_dot_pairs_f32(_ptr(Qn), Qn.stride(0) if Q > 1 else d, _ptr(Dn), Dn.stride(0) if N > 1 else d, Q, N, d, _ptr(cand),
+                                      _ld(cand), _ptr(cand_len), W, int(id_base), _ptr(out), _ld(out), _stream(Qn)), "fz_dot_pairs_f32")
+    return out
+
+
 # ---------------------------------------------------------------------------------------
 # K2 MaxSim
 # ---------------------------------------------------------------------------------------
@@ -1762,6 +1799,22 @@ def sparse_dot(index: SparseIndex, qoff: torch.Tensor, qterms: torch.Tensor, qw:
         _need(tuple(out.shape) == (Q, doc_hi - doc_lo), f"sparse_dot(out): expected shape {(Q, doc_hi - doc_lo)}, got {tuple(out.shape)}")
     check(_lib.lib().fz_sparse_dot_range_f32(_ptr(index.toff), _ptr(index.pdoc), _ptr(index.pw), _ptr(index.slice_off), _ptr(qoff), _ptr(qterms),
                                              _ptr(qw), Q, index.N, doc_lo, doc_hi, _ptr(out), _ld(out), _stream(qoff)), "fz_sparse_dot_range_f32")
+    return out
+
+
+def sparse_dot_pairs(index: SparseIndex, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, cand: torch.Tensor,
+                     cand_len: torch.Tensor | None = None, *, id_base: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Sparse scores of every query against its own candidates (fz_sparse_dot_pairs_f32): out[q, r] = sparse_dot(index, qoff, qterms,
+    qw)[q, cand[q, r] - id_base], bit for bit, with no [Q, N] plane (a binary search per query term and candidate).  The queries as
+    sparse_rows gives them (terms ascending); cand, cand_len, id_base, out and the -inf rules as in dot_pairs; a document of the index
+    that shares no term with the query scores +0.0."""
+    if not isinstance(index, SparseIndex):
+        raise TypeError(f"sparse_dot_pairs(index): expected an ops.SparseIndex, got {type(index).__name__}")
+    Q = _sparse_queries(qoff, qterms, qw, "sparse_dot_pairs")
+    cand_len, out, W = _pairs_args("sparse_dot_pairs", Q, qoff.device, cand, cand_len, out)
+    check(_lib.lib().fz_sparse_dot_pairs_f32(_ptr(index.toff), _ptr(index.pdoc), _ptr(index.pw), _ptr(qoff), _ptr(qterms), _ptr(qw), Q, index.N,
+                                             _ptr(cand), _ld(cand), _ptr(cand_len), W, int(id_base), _ptr(out), _ld(out), _stream(qoff)),
+          "fz_sparse_dot_pairs_f32")
     return out
 
 

@@ -553,6 +553,67 @@ class Aggregator:
             T.append(cls._normalised_planes([rs], normalization, distr, st)[0])
         return T
 
+    # -- list completion: every system scores the union of the candidates before the lists are fused --------------
+    @classmethod
+    def complete_topk(cls, systems: dict[str, RankedTopk], scorers: dict, depth: int | None = None) -> dict[str, RankedTopk]:
+        """Complete top-k lists before fusion.  fuse_topk / tune_topk give a document that system s did not list nothing from s -- an
+        artefact of the cut (the reference's behaviour on truncated lists, and still the default), not of the systems.  Here every system
+        that has a scorer scores the per-query UNION of all the lists' ids, and its list becomes that union ranked by its own scores.
+
+        scorers[name](ids [Q, W] int64, lens [Q] int32) -> [Q, W] float32 or float64 scores of the query batch against those ids: a
+        closure over an index's pair_scores (distributed.Sharded*Index) and the batch's queries.  A system without a scorer keeps its list.
+          1. U, ulen: the union of the lists' ids per query in the fused dict's first-insertion order (an ids-only ops.lists_columns join:
+             the lists of one query may hold ops.lists_max_entries() entries in all, ValueError beyond);
+          2. P = scorers[n](U, ulen); a float64 result is kept as scores64, its float32 rounding as scores;
+          3. system n's completed list is U ranked by P in (score desc, id asc) order -- the order of the corpus-scale searches, so an
+             exact search's own list comes first, with its own score bits -- with lens = ulen; depth cuts it to its first `depth` entries.
+        Scores are finite by contract; an id that no shard owns comes back as -inf and ranks last.
+        The result goes into fuse_topk / tune_topk / evaluate_topk as it is, and their width limit applies to it: a completed list is as
+        wide as the union, up to the sum of the k_s, so S completed lists join only while S * width <= ops.lists_max_entries() = 8,192.
+        `depth` keeps them inside: S = 2 at depth 4,096, S = 3 at depth 2,730, S = 4 at depth 2,048."""
+        names = list(systems.keys())
+        ops._max_systems(len(names), "Aggregator.complete_topk")
+        if not names:
+            raise ValueError("Aggregator.complete_topk: no system")
+        for n in names:
+            if not isinstance(systems[n], RankedTopk):
+                raise TypeError(f"Aggregator.complete_topk: system {n!r} must be a RankedTopk, got {type(systems[n]).__name__}")
+        for n, f in scorers.items():
+            if n not in systems:
+                raise KeyError(f"Aggregator.complete_topk: a scorer for {n!r}, which is not one of the systems {names}")
+            if not callable(f):
+                raise TypeError(f"Aggregator.complete_topk: the scorer of {n!r} is not callable")
+        if depth is not None and int(depth) < 1:
+            raise ValueError(f"Aggregator.complete_topk: depth = {depth} must be at least 1")
+        from ..distributed import rank_order
+        S = [systems[n] for n in names]
+        Q = cls._same_queries(s.Q for s in S)
+        U, _, _, ulen, _ = ops.lists_columns([s.ids for s in S], [s.lens for s in S], None)
+        W = U.shape[1]
+        keep = W if depth is None else min(int(depth), W)
+        out = {}
+        for n, s in zip(names, S):
+            if n not in scorers:
+                out[n] = s
+                continue
+            P = scorers[n](U, ulen)
+            if not isinstance(P, torch.Tensor) or P.dtype not in (torch.float32, torch.float64):
+                raise TypeError(f"Aggregator.complete_topk: the scorer of {n!r} must return a float32 or float64 tensor")
+            if tuple(P.shape) != (Q, W):
+                raise ValueError(f"Aggregator.complete_topk: the scorer of {n!r} returned {tuple(P.shape)} for ids {(Q, W)}")
+            lens = torch.clamp(ulen, max=keep)
+            if Q == 0 or W == 0:
+                out[n] = RankedTopk(ids=U[:, :keep], scores=P[:, :keep].to(torch.float32), lens=lens,
+                                    scores64=P[:, :keep] if P.dtype == torch.float64 else None)
+                continue
+            order = rank_order(U, P, ulen)[:, :keep]
+            listed = order >= 0
+            at = order.clamp(min=0)
+            sc = torch.gather(P, 1, at).masked_fill_(~listed, float("-inf"))      # the scorer's own bits
+            ids = torch.gather(U, 1, at).masked_fill_(~listed, -1)
+            out[n] = RankedTopk(ids=ids, scores=sc.to(torch.float32), lens=lens, scores64=sc if P.dtype == torch.float64 else None)
+        return out
+
     # -- N1: the whole weight grid in one pass (hybrid.py:404-426) ----------------------------------
     @classmethod
     def tune(cls, ranked_lists: dict, normalization: str, weight_combinations: list[dict[str, float]], labels: list[list],

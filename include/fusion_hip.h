@@ -613,6 +613,30 @@ int fz_maxsim_pairs_residual_f16(const void* Qtok, const void* packed, const int
                                  const int64_t* cand, int ldc, const int32_t* cand_len, int k, int64_t id_base, float* scores, int lds,
                                  void* stream);
 
+/* ---- K1 / A3 at corpus scale: single-vector scores of candidate lists (csrc/pairs.hip; ABI 20, additive) -----------------------------------
+ * What fz_maxsim_pairs_f16 is to ColBERT, for DPR and SPLADE: every query against ITS OWN candidate list, no [Q][N] plane, so that the
+ * top-k lists of several systems can be completed -- every system scores the union of the candidates -- before they are fused.
+ * cand [Q][ldc] int64 global ids, cand_len [Q] int32 (NULL: W for every row), id_base = global id of this shard's document 0 (any
+ * int64), out [Q][ldo] float32: the slot rules of fz_maxsim_pairs_f16.  out[q][r] = -inf when r >= cand_len[q], when the id is negative
+ * or when its position falls outside [0, N); columns W .. ldo-1 are left untouched; duplicate ids are scored independently.  No
+ * workspace, no atomics, no host synchronisation.
+ * fz_dot_pairs_f32: out[q][r] = <Qn[q], Dn[cand[q][r] - id_base]> with the BITS of fz_dot_scores_f32's scores[q][cand[q][r] - id_base]:
+ * the tile stream's chain of fused multiply-adds from +0.0 in its k order (k-tiles of 32, their count rounded up to even, zeros past d;
+ * inside a group of 8: 0, 4, 1, 5, 2, 6, 3, 7), on v_mfma_f32_4x4x1_16b_f32.  Qn [Q][ldq], Dn [N][ldd] float32, 16-byte aligned rows.
+ * Checks, in this order: a negative size, d <= 0, ldq < d, ldd < d, ldc < W, ldo < W or a null pointer where a non-empty tensor is
+ * needed -> FZ_ERR_ARG; d % 4, ldq % 4, ldd % 4, d > 16384 or Qn / Dn not 16-byte aligned -> FZ_ERR_UNSUPPORTED; Q == 0 or W == 0 ->
+ * FZ_OK with nothing launched.
+ * fz_sparse_dot_pairs_f32: out[q][r] = fz_sparse_dot_f32's scores[q][cand[q][r] - id_base], bit for bit: acc = acc + qw * pw from +0.0
+ * over the query's terms in ascending order (one rounding per product and per add), a term whose postings do not hold the document
+ * skipped (binary search); a document of the shard that shares no term with the query scores +0.0.  toff / pdoc / pw and qoff / qterms /
+ * qw as in fz_sparse_dot_f32 (no slice table).  Checks: a negative size, ldc < W, ldo < W or a null pointer (qoff, cand, out; toff when
+ * N > 0) where a non-empty tensor is needed -> FZ_ERR_ARG; Q == 0 or W == 0 -> FZ_OK with nothing launched. */
+int fz_dot_pairs_f32(const float* Qn, int ldq, const float* Dn, int ldd, int Q, int N, int d, const int64_t* cand, int ldc,
+                     const int32_t* cand_len, int W, int64_t id_base, float* out, int ldo, void* stream);
+int fz_sparse_dot_pairs_f32(const int64_t* toff, const int32_t* pdoc, const float* pw, const int64_t* qoff, const int32_t* qterms,
+                            const float* qw, int Q, int N, const int64_t* cand, int ldc, const int32_t* cand_len, int W, int64_t id_base,
+                            float* out, int ldo, void* stream);
+
 /* ---- encoder side: the per-sequence parts of SentenceTransformer.encode (hybrid.py:97-102) on PACKED token rows -- */
 /* Self-attention of a BERT/CamemBERT layer for ragged sequences without padding: for every sequence and head,
  * out = softmax(q k^T * scale) v in fp32 (MFMA products, online softmax over 16-key tiles), scale > 0.  qkv [T][ld] = fused
