@@ -26,6 +26,7 @@
 // lexical_doc_scores_kernel (bm25_count.hip) in float32 with the weight.
 //
 // Where it stands: DESIGN.md section 'Pair scores and list completion'.
+#include "pairs.h"
 #include "slices.h"
 
 namespace fz {
@@ -48,16 +49,6 @@ struct DotPairsArgs {
     int nblocks;                          // ceil(W / DP_SLOTS)
     int KT;                               // k-tiles: ceil(d / 64) * 2
 };
-
-// slot r of query q -> its row in this shard, or -1
-__device__ __forceinline__ int pair_position(const int64_t* cand, int ldc, const int32_t* cand_len, int64_t id_base, int N, int W, int q, int r) {
-    int klen = W;
-    if (cand_len) { klen = cand_len[q]; klen = klen < 0 ? 0 : klen < W ? klen : W; }
-    if (r >= klen) return -1;
-    const int64_t id = cand[(size_t)q * ldc + r];
-    const uint64_t pos = (uint64_t)id - (uint64_t)id_base;
-    return (id >= 0 && id >= id_base && pos < (uint64_t)N) ? (int)pos : -1;
-}
 
 __global__ __launch_bounds__(DP_THREADS) void dot_pairs_kernel(DotPairsArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];   // [DP_SLOTS][DP_LDT] the k-tile | [KT * DP_BK] the query

@@ -252,10 +252,15 @@ class ShardedSparseIndex(_ShardedIndex):
     def search(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, k: int = 1000, mark=None):
         return self._search((qoff, qterms, qw), k, mark)
 
+    def build_forward(self):
+        """The shard's forward index (ops.SparseIndex.build_forward): local_pair_scores, pair_scores and rerank then follow
+        ops.sparse_dot_pairs' route rule."""
+        return self.index.build_forward()
+
     def local_pair_scores(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, cand_ids: torch.Tensor,
                           cand_len: torch.Tensor | None = None) -> torch.Tensor:
         """[Q, W] float32: the posting walk's score of query q and candidate cand_ids[q, r], bit for bit, without the plane
-        (ops.sparse_dot_pairs)."""
+        (ops.sparse_dot_pairs, by the route it picks)."""
         return ops.sparse_dot_pairs(self.index, qoff, qterms, qw, cand_ids, cand_len, id_base=self.id_base)
 
     def pair_scores(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, cand_ids: torch.Tensor,

@@ -1555,6 +1555,32 @@ def lexical_doc_scores(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N
     return out
 
 
+def lexical_doc_scores_fwd(mode: str, toff, pdoc, vals, idf, forward: "ForwardIndex", qoff, qterms, Q: int, N: int, docs: torch.Tensor,
+                           block: int = 1024) -> torch.Tensor:
+    """lexical_doc_scores through the index's forward index (fz_bm25_doc_scores_fwd_pv_f64 / fz_tfidf_doc_scores_fwd_f64): the same [Q, G]
+    float64 scores bit for bit; the binary search per query term runs in the listed document's row of terms, and forward.fpos leads to
+    the posting's value in `vals`.  Queries in blocks of `block`, as lexical_doc_scores takes them."""
+    what = "lexical_doc_scores_fwd"
+    if not isinstance(forward, ForwardIndex):
+        raise TypeError(f"{what}(forward): expected an ops.ForwardIndex, got {type(forward).__name__}")
+    _lexical_args(what, mode, toff, pdoc, vals, idf, qoff, qterms, Q, N, 0, None, None)
+    _need(forward.N == N and forward.nnz == pdoc.numel(), f"{what}: the forward index must be the one built from these postings")
+    _need(_dev(docs, torch.int32, f"{what}(docs)").is_contiguous() and docs.dim() == 2 and docs.shape[0] == Q and docs.shape[1] >= 1,
+          f"{what}: docs must be a contiguous [Q, G >= 1] int32 tensor")
+    G, lib, f = docs.shape[1], _lib.lib(), forward
+    out = torch.empty((Q, G), dtype=torch.float64, device=toff.device)
+    for lo, hi in _query_blocks(Q, block):
+        if mode == "pv":
+            check(lib.fz_bm25_doc_scores_fwd_pv_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(f.foff), _ptr(f.fterm), _ptr(f.fpos), _ptr(qoff[lo:]),
+                                                    _ptr(qterms), hi - lo, N, _ptr(docs[lo:]), G, _ptr(out[lo:]), _stream(toff)),
+                  "fz_bm25_doc_scores_fwd_pv_f64")
+        else:
+            check(lib.fz_tfidf_doc_scores_fwd_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(idf), _ptr(f.foff), _ptr(f.fterm), _ptr(f.fpos),
+                                                  _ptr(qoff[lo:]), _ptr(qterms), hi - lo, N, _ptr(docs[lo:]), G, _ptr(out[lo:]), _stream(toff)),
+                  "fz_tfidf_doc_scores_fwd_f64")
+    return out
+
+
 def lexical_count(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int, doc_lo: int, doc_hi, id_base: int, gold_scores, gold_ids,
                   counts: torch.Tensor, slice_off: torch.Tensor | None = None, block: int = 1024) -> None:
     """The range walk with the counting epilogue (fz_bm25_count_pv_f64 / fz_tfidf_count_f64): counts [Q, G] int32 += per (query, gold) the
@@ -1679,9 +1705,104 @@ def topk_merge64(in_scores: torch.Tensor, in_ids: torch.Tensor):
 # ---------------------------------------------------------------------------------------
 # A3, sparse form: SPLADE cosine scoring over an inverted index
 # ---------------------------------------------------------------------------------------
+PAIR_ROUTES = (None, "inverted", "forward")
+
+
+def _pair_route(what: str, route, forward, why_not: str | None, prefer_forward: bool) -> bool:
+    """The route rule of the pair scorers that have a forward index -> True for the forward route.  'forward' without a forward index (or
+    with one the kernel does not take: why_not) raises; None takes the forward route only where `prefer_forward` says the measurement
+    earned it ('Forward index') and nothing stands against it."""
+    if route not in PAIR_ROUTES:
+        raise ValueError(f"{what}(route): expected None, 'inverted' or 'forward', got {route!r}")
+    if route == "forward":
+        _need(forward is not None, f"{what}(route='forward'): the index has no forward index (build_forward())")
+        _need(why_not is None, f"{what}(route='forward'): {why_not}")
+        return True
+    return route is None and prefer_forward and forward is not None and why_not is None
+
+
+class ForwardIndex:
+    """The document-major view of an inverted index: foff [N + 1] int64 row offsets, fterm [nnz] int32 the terms of document d in
+    [foff[d], foff[d+1]) (ascending), fpos [nnz] int32 the place of each posting in the inverted arrays -- any per-posting table (pw, ptf,
+    BM25's pval for the current (k1, b)) is reached through it."""
+
+    def __init__(self, foff, fterm, fpos, N: int, V: int):
+        self.foff, self.fterm, self.fpos, self.N, self.V = foff, fterm, fpos, int(N), int(V)
+
+    @property
+    def nnz(self) -> int:
+        return int(self.fterm.numel())
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.foff, self.fterm, self.fpos))
+
+
+def forward_index(toff: torch.Tensor, pdoc: torch.Tensor, N: int) -> ForwardIndex:
+    """The forward index of the postings (toff [V + 1] int64, pdoc [nnz] int32, documents ascending inside a term): ONE stable sort of the
+    postings by document -- they lie in ascending term order, so terms stay ascending inside a document; a posting's term comes from
+    repeat_interleave over toff.  Documents without postings get empty rows."""
+    if isinstance(pdoc, torch.Tensor) and pdoc.numel() >= 2 ** 31:      # (on the count alone, before the tensor is looked at)
+        raise ValueError(f"forward_index: {pdoc.numel()} postings, but a posting's place is kept as an int32")
+    _need(_dev(toff, torch.int64, "forward_index(toff)").is_contiguous() and toff.dim() == 1 and toff.numel() >= 1,
+          "forward_index: toff must be a contiguous [V + 1] tensor")
+    _need(_dev(pdoc, torch.int32, "forward_index(pdoc)").is_contiguous() and pdoc.dim() == 1, "forward_index: pdoc must be a contiguous [nnz] tensor")
+    N, V, nnz = int(N), toff.numel() - 1, pdoc.numel()
+    _need(N >= 0, "forward_index: N must not be negative")
+    order = torch.sort(pdoc, stable=True).indices
+    term = torch.repeat_interleave(torch.arange(V, dtype=torch.int32, device=pdoc.device), toff[1:] - toff[:-1])
+    _need(term.numel() == nnz, "forward_index: toff does not describe pdoc's postings")
+    counts = torch.bincount(pdoc, minlength=N)
+    _need(counts.numel() == N, f"forward_index: pdoc holds a document beyond N = {N}")
+    foff = torch.zeros(N + 1, dtype=torch.int64, device=pdoc.device)
+    foff[1:] = torch.cumsum(counts, 0)
+    return ForwardIndex(foff, term[order].contiguous(), order.int(), N, V)
+
+
+class SparseForward:
+    """A SparseIndex's forward index in the form fz_sparse_fwd_pairs_f32 reads: foff [N + 1] int64 and rows [nnz, 2] int32, row-contiguous
+    8-byte postings {term, the bits of the float32 weight} (fpos is not kept: 8 bytes per posting in all)."""
+
+    def __init__(self, foff, rows, N: int, V: int):
+        self.foff, self.rows, self.N, self.V = foff, rows, int(N), int(V)
+
+    @property
+    def nbytes(self) -> int:
+        return self.foff.numel() * 8 + self.rows.numel() * 4
+
+    def terms(self) -> torch.Tensor:
+        return self.rows[:, 0]
+
+    def weights(self) -> torch.Tensor:
+        return self.rows[:, 1].view(torch.float32)
+
+
+def sparse_fwd_max_vocab() -> int:
+    """The largest vocabulary whose query bitmap fz_sparse_fwd_pairs_f32 holds in LDS."""
+    return int(_lib.lib().fz_sparse_fwd_max_vocab())
+
+
+# route=None of sparse_dot_pairs takes the forward route where an index has one.  The forward index doubles the index's memory, so the
+# condition was at most half the inverted route's time at Q = 1024, W = 3,000 on the 1.1 M-passage shard: 0.93 ms against 11.16 ms in
+# one run (profiles/r21_forward_pairs.json; DESIGN.md, 'Forward index')
+SPARSE_PAIRS_PREFER_FORWARD = True
+
+
 class SparseIndex:
     """L2-normalised corpus vectors as postings: toff [V + 1] int64, pdoc [nnz] int32 (ascending inside a term), pw [nnz] float32,
-    slice_off [V, NS + 1] int64 (fz_sparse_slice_offsets).  N documents over a vocabulary of V terms."""
+    slice_off [V, NS + 1] int64 (fz_sparse_slice_offsets).  N documents over a vocabulary of V terms.  forward: None, or the
+    SparseForward build_forward() made."""
+
+    forward = None
+
+    def build_forward(self) -> SparseForward:
+        """Build and keep the document-major rows sparse_dot_pairs' forward route reads (8 bytes per posting: the index's size again)."""
+        f = forward_index(self.toff, self.pdoc, self.N)
+        rows = torch.empty((f.nnz, 2), dtype=torch.int32, device=self.pw.device)
+        rows[:, 0] = f.fterm
+        rows[:, 1] = self.pw[f.fpos.long()].view(torch.int32)
+        self.forward = SparseForward(f.foff, rows, self.N, self.V)
+        return self.forward
 
     def __init__(self, toff, pdoc, pw, N: int, V: int, slice_off=None):
         self.toff, self.pdoc, self.pw, self.N, self.V = toff, pdoc, pw, int(N), int(V)
@@ -1803,15 +1924,31 @@ def sparse_dot(index: SparseIndex, qoff: torch.Tensor, qterms: torch.Tensor, qw:
 
 
 def sparse_dot_pairs(index: SparseIndex, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, cand: torch.Tensor,
-                     cand_len: torch.Tensor | None = None, *, id_base: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+                     cand_len: torch.Tensor | None = None, *, id_base: int = 0, out: torch.Tensor | None = None, route: str | None = None) -> torch.Tensor:
     """Sparse scores of every query against its own candidates (fz_sparse_dot_pairs_f32): out[q, r] = sparse_dot(index, qoff, qterms,
     qw)[q, cand[q, r] - id_base], bit for bit, with no [Q, N] plane (a binary search per query term and candidate).  The queries as
     sparse_rows gives them (terms ascending); cand, cand_len, id_base, out and the -inf rules as in dot_pairs; a document of the index
-    that shares no term with the query scores +0.0."""
+    that shares no term with the query scores +0.0.
+
+    route: 'inverted' -- the binary searches in the posting lists; 'forward' -- one walk along the candidate's row of index.forward
+    (fz_sparse_fwd_pairs_f32; the same bits), a ValueError without a forward index or with V beyond sparse_fwd_max_vocab(); None --
+    the forward route where the index has a forward index the kernel takes (SPARSE_PAIRS_PREFER_FORWARD: it measured 12 times faster),
+    the inverted route otherwise: an index without a forward index is scored as before."""
+    if route not in PAIR_ROUTES:
+        raise ValueError(f"sparse_dot_pairs(route): expected None, 'inverted' or 'forward', got {route!r}")
     if not isinstance(index, SparseIndex):
         raise TypeError(f"sparse_dot_pairs(index): expected an ops.SparseIndex, got {type(index).__name__}")
+    fwd, why_not = index.forward, None
+    if fwd is not None and index.V > sparse_fwd_max_vocab():
+        why_not = f"V = {index.V} is beyond the kernel's bitmap ({sparse_fwd_max_vocab()} terms)"
+    forward = _pair_route("sparse_dot_pairs", route, fwd, why_not, SPARSE_PAIRS_PREFER_FORWARD)
     Q = _sparse_queries(qoff, qterms, qw, "sparse_dot_pairs")
     cand_len, out, W = _pairs_args("sparse_dot_pairs", Q, qoff.device, cand, cand_len, out)
+    if forward:
+        check(_lib.lib().fz_sparse_fwd_pairs_f32(_ptr(fwd.foff), _ptr(fwd.rows), index.V, _ptr(qoff), _ptr(qterms), _ptr(qw), Q, index.N, _ptr(cand),
+                                                 _ld(cand), _ptr(cand_len), W, int(id_base), _ptr(out), _ld(out), _stream(qoff)),
+              "fz_sparse_fwd_pairs_f32")
+        return out
     check(_lib.lib().fz_sparse_dot_pairs_f32(_ptr(index.toff), _ptr(index.pdoc), _ptr(index.pw), _ptr(qoff), _ptr(qterms), _ptr(qw), Q, index.N,
                                              _ptr(cand), _ld(cand), _ptr(cand_len), W, int(id_base), _ptr(out), _ld(out), _stream(qoff)),
           "fz_sparse_dot_pairs_f32")

@@ -323,9 +323,23 @@ class TFIDF:
             raise ValueError(f"{what}: expected a [Q = {Q}, G >= 1] array, got {tuple(t.shape)}")
         return t.contiguous()
 
-    def doc_scores(self, queries: list[str], positions) -> torch.Tensor:
+    forward = None               # the ops.ForwardIndex build_forward() made, or None
+    # doc_scores(route=None) follows the faster route at the measured shape (Q = 1024, G = 3,000, 200,000 documents): the inverted one, 1.58 ms
+    # against the forward route's 3.20 ms (profiles/r21_forward_pairs.json; DESIGN.md, 'Forward index') -- the forward route is opt-in here
+    PREFER_FORWARD = False
+
+    def build_forward(self):
+        """Build and keep the document-major view of the postings (ops.forward_index, fpos kept: 16 bytes per document + 8 per posting)
+        that doc_scores' forward route searches.  The per-posting values are read through fpos, so update_params needs nothing redone."""
+        self.forward = ops.forward_index(self.toff, self.pdoc, self.corpus_size)
+        return self.forward
+
+    def doc_scores(self, queries: list[str], positions, route: str | None = None) -> torch.Tensor:
         """[Q, G] float64: scores()[q, positions[q, g]] bit for bit, without the plane (one binary search per query term and listed
-        document).  A position of -1 -- not a document of this index -- gives -inf."""
+        document).  A position of -1 -- not a document of this index -- gives -inf.  route: 'inverted' searches the term's posting list,
+        'forward' the document's row of the forward index (a ValueError without one); None: ops.sparse_dot_pairs' rule, with
+        PREFER_FORWARD."""
+        forward = ops._pair_route("doc_scores", route, self.forward, None, self.PREFER_FORWARD)
         Q = len(queries)
         pos = self._gold_plane("doc_scores(positions)", positions, Q, torch.int64)
         if Q == 0:
@@ -336,6 +350,9 @@ class TFIDF:
                 raise ValueError(f"doc_scores: positions must be -1 or in [0, {self.corpus_size})")
         mode, vals, idf = self._walk_tables("doc_scores")
         qoff, flat = self._query_csr(queries)
+        if forward:
+            return ops.lexical_doc_scores_fwd(mode, self.toff, self.pdoc, vals, idf, self.forward, qoff, flat, Q, self.corpus_size,
+                                              pos.to(torch.int32), block=self.STREAM_QUERIES)
         return ops.lexical_doc_scores(mode, self.toff, self.pdoc, vals, idf, qoff, flat, Q, self.corpus_size, pos.to(torch.int32),
                                       block=self.STREAM_QUERIES)
 

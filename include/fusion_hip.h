@@ -637,6 +637,34 @@ int fz_sparse_dot_pairs_f32(const int64_t* toff, const int32_t* pdoc, const floa
                             const float* qw, int Q, int N, const int64_t* cand, int ldc, const int32_t* cand_len, int W, int64_t id_base,
                             float* out, int ldo, void* stream);
 
+/* ---- pair scores from a FORWARD (document-major) index (csrc/forward.hip; ABI 20, additive) ------------------------------------------------
+ * A pair's score is a question about one document, and the forward index holds a document's postings as one contiguous row: foff [N + 1]
+ * int64 row offsets, terms ascending inside a row (a stable sort of the inverted postings by document: ops.forward_index).
+ * fz_sparse_fwd_pairs_f32: fz_sparse_dot_pairs_f32 with (foff, rows, V) in the place of (toff, pdoc, pw): rows [nnz] of 8-byte
+ * {int32 term, float32 weight} postings (8-byte aligned), V the vocabulary size.  out[q][r] equals fz_sparse_dot_pairs_f32's BITS in every
+ * slot -- the row walk meets the terms query and document share in the same ascending order, acc = acc + qw * w from +0.0 -- with the same
+ * -inf rules; columns W .. ldo-1 are left untouched.  The query's term set is a bitmap over V in LDS, with the count of set bits before
+ * each word next to it (a term's place in the query's list is the number of set bits below it: qterms strictly ascending and inside
+ * [0, V), as fz_sparse_dot_f32 takes them): V > fz_sparse_fwd_max_vocab() (at least 65,536) is not built; a query may hold any number
+ * of terms.  No workspace, no atomics on global memory, no host synchronisation.  Checks, in this order: a negative size, ldc < W, ldo < W or a null pointer (qoff, cand, out; foff when N > 0) where a
+ * non-empty tensor is needed -> FZ_ERR_ARG; V beyond the cap or rows not 8-byte aligned -> FZ_ERR_UNSUPPORTED; Q == 0 or W == 0 -> FZ_OK
+ * with nothing launched.
+ * fz_tfidf_doc_scores_fwd_f64 / fz_bm25_doc_scores_fwd_pv_f64: fz_tfidf_doc_scores_f64 / fz_bm25_doc_scores_pv_f64 with the forward index
+ * next to the inverted tables: fterm [nnz] int32 the rows' terms, fpos [nnz] int32 each posting's place e in the inverted arrays (ptf[e],
+ * pval[e]).  The same chain -- query order, terms not de-duplicated, -1 adds nothing, acc = acc + term from 0.0 -- and so the same bits;
+ * the binary search per query term runs in the document's row, not in the term's posting list.  toff and pdoc are accepted and not
+ * read.  Checks: Q < 0, N < 0, G < 1 or (Q > 0) a null pointer among the tables read -> FZ_ERR_ARG; Q == 0 -> FZ_OK. */
+int fz_sparse_fwd_max_vocab(void);
+int fz_sparse_fwd_pairs_f32(const int64_t* foff, const void* rows, int V, const int64_t* qoff, const int32_t* qterms, const float* qw, int Q,
+                            int N, const int64_t* cand, int ldc, const int32_t* cand_len, int W, int64_t id_base, float* out, int ldo,
+                            void* stream);
+int fz_tfidf_doc_scores_fwd_f64(const int64_t* toff, const int32_t* pdoc, const int32_t* ptf, const double* idf, const int64_t* foff,
+                                const int32_t* fterm, const int32_t* fpos, const int64_t* qoff, const int32_t* qterms, int Q, int N,
+                                const int32_t* docs, int G, double* out, void* stream);
+int fz_bm25_doc_scores_fwd_pv_f64(const int64_t* toff, const int32_t* pdoc, const double* pval, const int64_t* foff, const int32_t* fterm,
+                                  const int32_t* fpos, const int64_t* qoff, const int32_t* qterms, int Q, int N, const int32_t* docs, int G,
+                                  double* out, void* stream);
+
 /* ---- encoder side: the per-sequence parts of SentenceTransformer.encode (hybrid.py:97-102) on PACKED token rows -- */
 /* Self-attention of a BERT/CamemBERT layer for ragged sequences without padding: for every sequence and head,
  * out = softmax(q k^T * scale) v in fp32 (MFMA products, online softmax over 16-key tiles), scale > 0.  qkv [T][ld] = fused
