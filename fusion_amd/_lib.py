@@ -134,6 +134,9 @@ _PROTOS = {
     "fz_centroid_slice_offsets": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "fz_centroid_scores_range_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "fz_centroid_scores_filter_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "fz_pair_max_sep": (_i, []),
+    "fz_pair_plan": (_i, [_vp, _i, _vp, _i, _i, _i64, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "fz_pair_fill": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "fz_attn_varlen_f32": (_i, [_vp, _i, _vp, _i, _i, _i, C.c_float, _vp, _i, _vp]),
     "fz_add_layernorm_f32": (_i, [_vp, _i, _vp, _i, _vp, _vp, C.c_float, _i, _i, _vp, _i, _vp]),
     "fz_gelu_f32": (_i, [_vp, _vp, _sz, _vp]),

@@ -104,8 +104,8 @@ def rank_pairs(ids: torch.Tensor, scores: torch.Tensor, k: int | None = None):
 
 
 def _candidates(candidates):
-    from .planes import RankedTopk
-    return (candidates.ids, candidates.lens) if isinstance(candidates, RankedTopk) else (candidates, None)
+    from .planes import FusedTopk, RankedTopk
+    return (candidates.ids, candidates.lens) if isinstance(candidates, (RankedTopk, FusedTopk)) else (candidates, None)
 
 
 class _ShardedIndex:
@@ -566,6 +566,78 @@ class ShardedTokenIndex:
         order, _, _ = ops.sort_rows_desc(scores, want_keys=False)
         k0 = ids.shape[1]
         k = k0 if k is None else min(int(k), k0)
+        order = order[:, :k].long()
+        sorted_scores = torch.gather(scores, 1, order)      # the scores' own bits (the sort's key plane canonicalises -0.0 and NaN)
+        owned = sorted_scores != float("-inf")
+        out_ids = torch.where(owned, torch.gather(ids, 1, order), torch.full_like(order, -1))
+        return RankedTopk(ids=out_ids, scores=sorted_scores, lens=owned.sum(1, dtype=torch.int32))
+
+
+class ShardedTextIndex:
+    """One rank's shard of the corpus as TOKEN IDS, for the cross-encoder rerank of top-k lists (hybrid.py:139-163): tok [sumL] int32,
+    Doff [N + 1] int64, documents 0 .. N-1 = global ids id_base ..; the pattern of ShardedTokenIndex.  A document holds the first
+    min(len, max_length - (2 + nsep)) plain tokens of its text, no specials -- the most any pair can keep of it, since pair truncation
+    only ever removes from the tail -- and full_len [N] int32 (or None: nothing was cut) remembers len: the tokenizer's longest_first
+    rule gives the odd token of an odd budget to the STRICTLY longer sequence, which the stored prefix alone cannot tell once it is cut.
+    encoders.CrossEncoder.score_candidates assembles the (query, document) rows of the packed forward from these ids on the device
+    (fz_pair_plan / fz_pair_fill): no string is built, no document re-tokenised, no padded id matrix uploaded.  A slot this shard does not
+    own gets -inf, so the shards' [Q, W] planes combine by ONE all_reduce(MAX) and every rank forwards only the pairs whose documents it
+    holds: the forward is split across the ranks by the sharding alone."""
+
+    def __init__(self, tok: torch.Tensor, Doff: torch.Tensor, id_base: int, group=None, full_len: torch.Tensor | None = None):
+        ops._pair_store("ShardedTextIndex", tok, Doff, full_len)
+        self.tok, self.Doff, self.id_base, self.group, self.full_len = tok, Doff, int(id_base), group, full_len
+
+    @classmethod
+    def from_texts(cls, model, documents: list[str], id_base: int = 0, group=None, device=None):
+        """Tokenise this shard's documents ONCE with the cross-encoder's tokenizer (tokenizer.encode_plain), cut at what `model` can keep."""
+        import numpy as np
+        if device is None:
+            device = model._device
+        if torch.device(device).type != "cuda":
+            raise TypeError(f"ShardedTextIndex.from_texts: the index lives on the GPU (fusion_amd has no CPU path), got device {device}")
+        keep = model.max_length - (2 + model.tokenizer.pair_spec()["nsep"])
+        ids, full = model.tokenizer.encode_plain(documents, keep)
+        held = np.minimum(full.numpy().astype(np.int64), max(keep, 0))
+        Doff = np.zeros(len(documents) + 1, dtype=np.int64)
+        np.cumsum(held, out=Doff[1:])
+        tok = ids.numpy()[np.arange(ids.shape[1])[None, :] < held[:, None]]
+        cut = bool((full.numpy() > held).any())
+        return cls(torch.from_numpy(np.ascontiguousarray(tok, dtype=np.int32)).to(device), torch.from_numpy(Doff).to(device), id_base, group=group,
+                   full_len=full.to(device) if cut else None)
+
+    @property
+    def N(self) -> int:
+        return self.Doff.numel() - 1
+
+    def local_scores(self, model, qtok: torch.Tensor, qlen: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
+        """[Q, W] float32: model.score_candidates over this shard; -inf for a slot it does not own."""
+        return model.score_candidates(self, qtok, qlen, cand_ids, cand_len)
+
+    def pair_scores(self, model, qtok: torch.Tensor, qlen: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
+        """[Q, W] float32: local_scores for the whole corpus -- the shards' planes under one all_reduce(MAX).  As an Aggregator.complete_topk
+        scorer: lambda ids, lens: index.pair_scores(model, qtok, qlen, ids, lens)."""
+        return _reduce_max(self.local_scores(model, qtok, qlen, cand_ids, cand_len), self.group)
+
+    def rerank(self, model, qtok: torch.Tensor, qlen: torch.Tensor, candidates, k: int | None = None, depth: int | None = None):
+        """candidates: a planes.RankedTopk / FusedTopk (its ids and lens are used) or a [Q, k0] int64 id tensor (negative ids = padding) ->
+        RankedTopk of the candidates in descending cross-encoder score, cut to the first k (default: all), built as ShardedTokenIndex.rerank
+        builds its own: one stable descending row sort, ties keep candidate order, a slot no shard owns ends as (-inf, -1), lens counts the
+        rest.  depth: only the first `depth` slots of every list are scored (and returned)."""
+        from .planes import RankedTopk
+        ids, cand_len = _candidates(candidates)
+        ops._dev(ids, torch.int64, "ShardedTextIndex.rerank(candidates)")
+        if depth is not None:
+            if int(depth) < 1:
+                raise ValueError(f"ShardedTextIndex.rerank: depth = {depth} must be at least 1")
+            ids = ids[:, : int(depth)]
+        if ids.numel() == 0:
+            return RankedTopk(ids=ids.clone(), scores=torch.empty(ids.shape, dtype=torch.float32, device=ids.device),
+                              lens=torch.zeros(ids.shape[0], dtype=torch.int32, device=ids.device))
+        scores = self.pair_scores(model, qtok, qlen, ids, cand_len)
+        order, _, _ = ops.sort_rows_desc(scores, want_keys=False)
+        k0 = ids.shape[1]
+        k = k0 if k is None else max(0, min(int(k), k0))
         order = order[:, :k].long()
         sorted_scores = torch.gather(scores, 1, order)      # the scores' own bits (the sort's key plane canonicalises -0.0 and NaN)
         owned = sorted_scores != float("-inf")

@@ -52,6 +52,26 @@ class HashTokenizer:
             mask[i, : len(r)] = 1
         return ids, mask
 
+    def encode_plain(self, texts: list[str], max_tokens: int):
+        """The texts' own tokens, no specials: (ids [n, min(max_tokens, longest)] int32, padded with pad_token_id; lengths [n] int32, the
+        token counts BEFORE the cut at max_tokens -- min(lengths, max_tokens) tokens of a row are its text's)."""
+        return _plain_rows([[self._tok(w) for w in t.split()] for t in texts], max_tokens, self.pad_token_id)
+
+    def pair_spec(self) -> dict:
+        """How CrossEncoder._pair_ids lays out a (query, document) pair with this tokenizer: one row, the separator an ordinary token."""
+        return dict(mode="tail", nsep=1, bos=self.bos_id, sep=self._tok("</s>"), eos=self.eos_id)
+
+
+def _plain_rows(rows: list[list[int]], max_tokens: int, pad_id: int):
+    """Token lists -> (ids [n, min(max_tokens, longest)] int32 padded with pad_id, the lists' full lengths [n] int32)."""
+    full = np.array([len(r) for r in rows], dtype=np.int32)
+    width = int(min(max(int(max_tokens), 0), full.max())) if len(rows) else 0
+    ids = np.full((len(rows), width), pad_id, dtype=np.int32)
+    for i, r in enumerate(rows):
+        k = min(len(r), width)
+        ids[i, :k] = r[:k]
+    return torch.from_numpy(ids), torch.from_numpy(full)
+
 
 def _backbone(cfg: dict, mlm: bool = False):
     from transformers import CamembertConfig, CamembertForMaskedLM, CamembertModel
@@ -310,7 +330,19 @@ class PackedBertForward(FusedBertForward):
         cols = np.arange(T, dtype=np.int64) - np.repeat(cu[:-1].astype(np.int64), lengths)
         host = np.concatenate([np.repeat(np.arange(n, dtype=np.int64) * Lmax, lengths) + cols, cols + (self.pad_idx + 1)])
         meta = torch.from_numpy(host).to(dev, non_blocking=True)                       # one upload: gather indices + position ids
-        ids = input_ids.reshape(-1)[meta[:T]]
+        return self.hidden_packed(input_ids.reshape(-1)[meta[:T]], meta[T:], strips_d, cu_d, T, mark), cu_d
+
+    @torch.no_grad()
+    def hidden_packed(self, ids: torch.Tensor, pos_ids: torch.Tensor, strips_d: torch.Tensor, cu_d: torch.Tensor, T: int, mark=None) -> torch.Tensor:
+        """The forward from packed vectors that are already on the device: ids / pos_ids [T] int64 (token and position id of every row, T > 0),
+        strips_d [n_strips, 4] and cu_d [n + 1] int32 (ops.attn_strips of the sequences' lengths; the kernels walk the strips, cu_d is what
+        the callers pool or gather by) -> the last hidden states [T, hidden] fp32.  `hidden` derives the four from a padded id matrix on
+        the host; CrossEncoder.score_candidates has fz_pair_fill write the first two."""
+        from . import ops
+        dev = ids.device
+        H = self.heads
+        if self.word.shape[1] != H * 64:
+            raise ValueError(f"PackedBertForward: head_dim {self.word.shape[1] // H} is not 64 (use FusedBertForward)")
         # while GEMM tuning is on, the row count is padded to a multiple of ROW_GRANULE (zero rows: every op between the GEMMs is
         # row-wise, so they never touch a real row) -- tuned solutions are keyed by the exact shape
         Tp = -(-T // self.ROW_GRANULE) * self.ROW_GRANULE if torch.cuda.tunable.is_enabled() else T
@@ -321,14 +353,14 @@ class PackedBertForward(FusedBertForward):
             x = torch.empty((Tp, self.word.shape[1]), dtype=torch.float32, device=dev)
             x[T:].zero_()
         # embedding gather + position + type + LayerNorm in one pass over the packed rows
-        x = ops.embed_layernorm(self.word, self.pos, self.type0, ids, meta[T:], *self.emb_ln, out=x)
+        x = ops.embed_layernorm(self.word, self.pos, self.type0, ids, pos_ids, *self.emb_ln, out=x)
         ctx = torch.empty_like(x)                 # attention writes the real rows of this buffer in every layer; the pad rows stay zero
         if Tp != T:
             ctx[T:].zero_()
         mark = mark or (lambda name: None)
         mark("encode_embed")
         if self.amp_dtype == torch.float16 and self.word.shape[1] % 8 == 0 and self.layers[0]["w1"].shape[0] % 8 == 0:
-            return self._layers_f16(x, ctx, strips_d, H, mark, T)[:T], cu_d
+            return self._layers_f16(x, ctx, strips_d, H, mark, T)[:T]
         for ly in self.layers:
             qkv = self._linear(x, ly["wqkv"], ly["bqkv"]); mark("encode_gemm")
             ops.attn_varlen(qkv, strips_d, H, out=ctx); mark("encode_attn")
@@ -338,7 +370,7 @@ class PackedBertForward(FusedBertForward):
             h = ops.gelu_(h); mark("encode_gelu")                   # in place, non-temporal loads
             y = self._linear(h, ly["w2"], ly["b2"]); mark("encode_gemm")
             x = ops.add_layernorm(y, x, *ly["ln2"]); mark("encode_ln")
-        return x[:T], cu_d
+        return x[:T]
 
     @torch.no_grad()
     def __call__(self, input_ids: torch.Tensor, lengths, n_buckets: int = 0, mark=None) -> torch.Tensor:
@@ -791,6 +823,20 @@ def from_pretrained(model_name_or_path: str, kind: str, device="cuda"):
         def encode_pairs(self, first, second, max_length):   # "<s> query </s></s> document </s>", truncation as CrossEncoder.smart_batching_collate
             e = hf_tok(first, second, padding=True, truncation="longest_first", max_length=max_length, return_tensors="pt")
             return e["input_ids"], e["attention_mask"]
+
+        def encode_plain(self, texts, max_tokens):           # as HashTokenizer.encode_plain: no specials, lengths before the cut
+            rows = hf_tok(list(texts), add_special_tokens=False, truncation=False)["input_ids"] if len(texts) else []
+            return _plain_rows(rows, max_tokens, hf_tok.pad_token_id)
+
+        def pair_spec(self):
+            """encode_pairs' layout: "<s> q </s></s> d </s>" (as many separators as the pair template adds), longest_first truncation as
+            the fast (`tokenizers`) implementation applies it -- the slow Python tokenizers cut one token at a time, a different rule."""
+            if not getattr(hf_tok, "is_fast", False):
+                raise ValueError("pair rows from ids need a fast tokenizer: the slow tokenizers' longest_first truncation is a different rule")
+            if hf_tok.truncation_side != "right" or hf_tok.cls_token_id is None or hf_tok.sep_token_id is None:
+                raise ValueError("pair rows from ids: the tokenizer must truncate on the right and have cls / sep tokens")
+            return dict(mode="longest_first", nsep=hf_tok.num_special_tokens_to_add(pair=True) - 2, bos=hf_tok.cls_token_id,
+                        sep=hf_tok.sep_token_id, eos=hf_tok.sep_token_id)
     if kind == "dpr":
         return DenseEncoder(AutoModel.from_pretrained(model_name_or_path, local_files_only=True), _Tok(), device)
     if kind == "splade":
@@ -834,14 +880,24 @@ def from_pretrained(model_name_or_path: str, kind: str, device="cuda"):
 
 class CrossEncoder(_Base):
     """monoBERT reranker (hybrid.py:139-163, CrossEncoderCustom): CamemBERT sequence classifier over "<s> query </s></s> doc </s>",
-    one logit per pair, fp32.  `predict(pairs)` is what Ranker.cross_encoder_search calls."""
+    one logit per pair, fp32.  `predict(pairs)` is what Ranker.cross_encoder_search calls; `score_candidates` scores top-k lists of global
+    ids against a token store of the corpus (distributed.ShardedTextIndex), the pairs assembled on the device.
+    amp=True (opt-in) runs the packed forward with float16 Linears, the path the ColBERT encoder ships (PackedBertForward._layers_f16);
+    the reference runs monoBERT in float32, which stays the default."""
 
-    def __init__(self, classifier, tokenizer, device, max_length: int = 512, activation: str = "identity"):
+    def __init__(self, classifier, tokenizer, device, max_length: int = 512, activation: str = "identity", amp: bool = False):
         super().__init__(tokenizer, device)
+        self.amp = bool(amp) and self._device.type == "cuda"
         self.model = classifier.to(self._device).eval()
         self._clamp_lengths(classifier.config)
         self.max_length = min(max_length, self.max_doc_length)
         self.activation = activation     # CrossEncoder.predict applies the default activation: Sigmoid for one label (ST 2.2.2)
+
+    def _packed_forward(self, backbone):
+        fwd = super()._packed_forward(backbone)
+        if fwd is not None:
+            fwd.amp_dtype = torch.float16 if self.amp else None
+        return fwd
 
     def _pair_ids(self, pairs, max_len):
         """(query, document) pairs -> ids, mask.  A real tokenizer encodes the PAIR ("<s> q </s></s> d </s>", longest-first
@@ -874,6 +930,60 @@ class CrossEncoder(_Base):
                 raise ValueError(f"cross-encoder with {logits.shape[1]} labels: the rerank stage expects one relevance logit (hybrid.py:159)")
             score = logits[:, 0].float()                     # one label: score[0] (CrossEncoder.predict)
             out[torch.tensor(idx, device=self._device)] = torch.sigmoid(score) if self.activation == "sigmoid" else score
+        return out
+
+    @torch.no_grad()
+    def score_candidates(self, index, qtok, qlen, cand_ids, cand_len=None) -> torch.Tensor:
+        """[Q, W] float32: the relevance score of query q and document cand_ids[q, r] for every slot whose document `index` (one shard of the
+        corpus as token ids: tok, Doff, full_len, id_base -- distributed.ShardedTextIndex) holds; -inf for a slot it does not own (r >=
+        cand_len[q], a negative id, a document of another shard), to which the activation is never applied.  qtok [Q, Lq] int32 / qlen [Q]
+        int32: the queries' plain tokens and their lengths before any cut (tokenizer.encode_plain); cand_ids [Q, W] int64 global ids.
+        The pairs are what `_pair_ids` makes of the same texts -- "<s> q </s></s> d </s>" under the tokenizer's truncation rule
+        (tokenizer.pair_spec) -- but no string is built and no padded id matrix uploaded: fz_pair_plan decides every slot's kept lengths,
+        fz_pair_fill writes the packed ids and positions of each forward sub-batch straight from the token store.
+        ONE host synchronisation: the plan's row counts (Q * W int32) are copied to the host, because the row count of every sub-batch is a
+        tensor shape and the sub-batches (longest pairs first, cut at packed_tokens by the EXACT token counts) are chosen from them."""
+        from . import ops
+        cfg = self.model.config
+        if int(getattr(cfg, "type_vocab_size", 1)) > 1:
+            raise ValueError(f"score_candidates: a model with {cfg.type_vocab_size} token types needs type ids per row; the packed forward "
+                             "carries type 0 only")
+        if int(getattr(cfg, "num_labels", 1)) != 1:
+            raise ValueError(f"cross-encoder with {cfg.num_labels} labels: the rerank stage expects one relevance logit (hybrid.py:159)")
+        Q, Lq = ops._pair_queries("score_candidates", qtok, qlen)
+        ops._dev(cand_ids, torch.int64, "score_candidates(cand_ids)")
+        N = ops._pair_store("score_candidates", index.tok, index.Doff, index.full_len)
+        base = getattr(self.model, self.model.base_model_prefix)
+        fwd = self._packed_forward(base) if hasattr(self.model, "classifier") else None
+        if fwd is None:     # no quiet detour through the padded HF module
+            raise ValueError("score_candidates: the packed forward does not cover this model (64-wide heads, erf GELU, a `classifier` head, on a GPU)")
+        spec = self.tokenizer.pair_spec()
+        if cand_ids.dim() != 2 or cand_ids.shape[0] != Q:
+            raise ValueError(f"score_candidates: cand_ids must be [Q = {Q}, W], got {tuple(cand_ids.shape)}")
+        W = cand_ids.shape[1]
+        dev = cand_ids.device
+        out = torch.full((Q, W), float("-inf"), dtype=torch.float32, device=dev)
+        if Q == 0 or W == 0 or N == 0:
+            return out
+        kq, kd, L = ops.pair_plan(cand_ids, cand_len, index.Doff, index.full_len, index.id_base, qlen, Lq, self.max_length, spec["mode"], spec["nsep"])
+        rows = L.reshape(-1).cpu().numpy()                          # the one synchronisation of the call
+        owned = np.flatnonzero(rows)                                # an owned pair has at least its two specials
+        lengths = rows[owned].astype(np.int64)
+        flat = out.view(-1)
+        for idx in _id_batches(lengths, self.packed_tokens):
+            strips, cu = ops.attn_strips(lengths[idx])
+            T = int(cu[-1])
+            tables = torch.from_numpy(np.concatenate([strips.reshape(-1), cu, owned[idx].astype(np.int32)])).to(dev, non_blocking=True)
+            strips_d, cu_d, pairs_d = tables[: strips.size].view(-1, 4), tables[strips.size: strips.size + cu.size], tables[strips.size + cu.size:]
+            ids, pos = ops.pair_fill(pairs_d, cu_d, T, kq, kd, cand_ids, index.id_base, qtok, index.tok, index.Doff, spec["bos"], spec["sep"],
+                                     spec["eos"], fwd.pad_idx, spec["nsep"])
+            x = fwd.hidden_packed(ids, pos, strips_d, cu_d, T)
+            first = x.index_select(0, cu_d[:-1].long())              # the head reads the first token (<s>) of every pair: features[:, 0, :]
+            logits = self.model.classifier(first.unsqueeze(1)).reshape(len(idx), -1)
+            if logits.shape[1] != 1:
+                raise ValueError(f"cross-encoder with {logits.shape[1]} labels: the rerank stage expects one relevance logit (hybrid.py:159)")
+            score = logits[:, 0].float()
+            flat[pairs_d.long()] = torch.sigmoid(score) if self.activation == "sigmoid" else score
         return out
 
 

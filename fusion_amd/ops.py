@@ -2354,6 +2354,88 @@ def f64_to_f32(src: torch.Tensor) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------
 # encoder side: packed (padding-free) token rows
 # ---------------------------------------------------------------------------------------
+PAIR_MODES = {"longest_first": 0, "tail": 1}   # FZ_PAIR_LONGEST_FIRST / FZ_PAIR_TAIL (include/fusion_hip.h)
+
+
+def _pair_store(what: str, tok, Doff, full_len):
+    """The token store of the pair kernels: tok [sumL] int32, Doff [N + 1] int64, full_len [N] int32 or None.  -> N."""
+    _dev(tok, torch.int32, f"{what}(tok)")
+    _dev(Doff, torch.int64, f"{what}(Doff)")
+    _need(tok.dim() == 1 and tok.is_contiguous(), f"{what}: tok must be a contiguous [sumL] vector")
+    _need(Doff.dim() == 1 and Doff.numel() >= 1 and Doff.is_contiguous(), f"{what}: Doff must hold N + 1 offsets")
+    N = Doff.numel() - 1
+    if full_len is not None:
+        _dev(full_len, torch.int32, f"{what}(full_len)")
+        _need(tuple(full_len.shape) == (N,) and full_len.is_contiguous(), f"{what}(full_len): expected shape {(N,)}, got {tuple(full_len.shape)}")
+    return N
+
+
+def _pair_queries(what: str, qtok, qlen):
+    _dev(qtok, torch.int32, f"{what}(qtok)")
+    _dev(qlen, torch.int32, f"{what}(qlen)")
+    _need(qtok.dim() == 2, f"{what}: qtok must be [Q, Lq]")
+    Q, Lq = qtok.shape
+    _need(tuple(qlen.shape) == (Q,) and qlen.is_contiguous(), f"{what}(qlen): expected shape {(Q,)}, got {tuple(qlen.shape)}")
+    return Q, Lq
+
+
+def pair_plan(cand: torch.Tensor, cand_len: torch.Tensor | None, Doff: torch.Tensor, full_len: torch.Tensor | None, id_base: int,
+              qlen: torch.Tensor, Lq: int, max_length: int, mode: str, nsep: int):
+    """The plan of a cross-encoder forward over candidate lists (fz_pair_plan): for every slot of cand [Q, W] int64 (global ids, rows may be
+    strided; cand_len [Q] int32 or None) -> (kq, kd, L), three contiguous [Q, W] int32 planes: the query and document tokens the pair
+    keeps under the tokenizer's truncation rule `mode` ('longest_first' / 'tail', include/fusion_hip.h) and the pair's row count; all 0
+    where the slot is not this shard's (past cand_len, a negative id, a document outside id_base .. id_base + N - 1).  qlen [Q] int32:
+    the queries' plain lengths before any cut, Lq: the columns of the query id matrix.  No host synchronisation."""
+    if mode not in PAIR_MODES:
+        raise ValueError(f"pair_plan: mode must be one of {sorted(PAIR_MODES)}, got {mode!r}")
+    _dev(cand, torch.int64, "pair_plan(cand)")
+    _dev(Doff, torch.int64, "pair_plan(Doff)")
+    _dev(qlen, torch.int32, "pair_plan(qlen)")
+    _need(cand.dim() == 2 and cand.shape[0] == qlen.numel() and qlen.dim() == 1, f"pair_plan: cand must be [Q = {qlen.numel()}, W], got {tuple(cand.shape)}")
+    _need(Doff.dim() == 1 and Doff.numel() >= 1 and Doff.is_contiguous() and qlen.is_contiguous(), "pair_plan: Doff must hold N + 1 offsets")
+    Q, W = cand.shape
+    N = Doff.numel() - 1
+    if cand_len is not None:
+        _dev(cand_len, torch.int32, "pair_plan(cand_len)")
+        _need(tuple(cand_len.shape) == (Q,) and cand_len.is_contiguous(), f"pair_plan(cand_len): expected shape {(Q,)}, got {tuple(cand_len.shape)}")
+    if full_len is not None:
+        _dev(full_len, torch.int32, "pair_plan(full_len)")
+        _need(tuple(full_len.shape) == (N,) and full_len.is_contiguous(), f"pair_plan(full_len): expected shape {(N,)}, got {tuple(full_len.shape)}")
+    plan = torch.empty((3, Q, W), dtype=torch.int32, device=cand.device)
+    check(_lib.lib().fz_pair_plan(_ptr(cand), _ld(cand), _ptr(cand_len), Q, W, int(id_base), _ptr(Doff), _ptr(full_len), N, _ptr(qlen), int(Lq),
+                                  int(max_length), PAIR_MODES[mode], int(nsep), _ptr(plan[0]), _ptr(plan[1]), _ptr(plan[2]), _stream(cand)),
+          "fz_pair_plan")
+    return plan[0], plan[1], plan[2]
+
+
+def pair_fill(pairs: torch.Tensor, cu_rows: torch.Tensor, T: int, kq: torch.Tensor, kd: torch.Tensor, cand: torch.Tensor, id_base: int,
+              qtok: torch.Tensor, tok: torch.Tensor, Doff: torch.Tensor, bos: int, sep: int, eos: int, pad_idx: int, nsep: int):
+    """The packed rows of one forward sub-batch (fz_pair_fill): pairs [P] int32 flat slots q * W + r of cand [Q, W] in forward order,
+    cu_rows [P + 1] int32 (cu_rows[P] = T), kq / kd the planes of pair_plan, qtok [Q, Lq] int32, (tok, Doff) the token store ->
+    (ids [T], pos_ids [T]) int64, what embed_layernorm takes: bos, the kept query tokens, the separators, the kept document tokens, eos;
+    positions pad_idx + 1 + column.  Every stored token id must index inside the model's embedding table."""
+    _dev(pairs, torch.int32, "pair_fill(pairs)")
+    _dev(cu_rows, torch.int32, "pair_fill(cu_rows)")
+    _dev(cand, torch.int64, "pair_fill(cand)")
+    _dev(qtok, torch.int32, "pair_fill(qtok)")
+    N = _pair_store("pair_fill", tok, Doff, None)
+    P, T = pairs.numel(), int(T)
+    _need(pairs.dim() == 1 and cu_rows.dim() == 1 and cu_rows.numel() == P + 1 and pairs.is_contiguous() and cu_rows.is_contiguous(),
+          f"pair_fill: pairs [P] and cu_rows [P + 1] expected, got {tuple(pairs.shape)} and {tuple(cu_rows.shape)}")
+    _need(cand.dim() == 2 and qtok.dim() == 2 and qtok.shape[0] == cand.shape[0], "pair_fill: cand [Q, W] and qtok [Q, Lq] expected")
+    Q, W = cand.shape
+    for t_, w_ in ((kq, "kq"), (kd, "kd")):
+        _dev(t_, torch.int32, f"pair_fill({w_})")
+        _need(tuple(t_.shape) == (Q, W) and t_.is_contiguous(), f"pair_fill({w_}): expected a contiguous {(Q, W)} plane, got {tuple(t_.shape)}")
+    _need(T >= 0, "pair_fill: T must not be negative")
+    out = torch.empty((2, T), dtype=torch.int64, device=cand.device)
+    check(_lib.lib().fz_pair_fill(_ptr(pairs), _ptr(cu_rows), P, T, _ptr(kq), _ptr(kd), _ptr(cand), _ld(cand), Q, W, int(id_base),
+                                  _ptr(qtok) if qtok.numel() else None, qtok.stride(0) if Q > 1 else qtok.shape[1], qtok.shape[1],
+                                  _ptr(tok) if tok.numel() else None, _ptr(Doff), N, int(bos), int(sep), int(eos), int(pad_idx), int(nsep),
+                                  _ptr(out[0]) if T else None, _ptr(out[1]) if T else None, _stream(cand)), "fz_pair_fill")
+    return out[0], out[1]
+
+
 def attn_strips(lengths, cu_rows=None):
     """HOST helper: the strip table fz_attn_varlen_f32 walks -- one (first row, length, first query, 0) entry per 32 queries
     of every sequence, longest sequences first.  Returns (strips int32 [n_strips, 4] numpy, cu_rows int32 [B+1] numpy)."""

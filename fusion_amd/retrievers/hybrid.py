@@ -218,6 +218,17 @@ class Ranker:
             torch.cuda.empty_cache()
         return ranked_lists
 
+    @staticmethod
+    def cross_encoder_rerank(queries: list[str], index, candidates, *, model, return_topk: int = None, depth: int = None):
+        """The same rerank over top-k LISTS of global ids (planes.RankedTopk / FusedTopk, or a [Q, k0] int64 tensor): what
+        Aggregator.fuse_topk returns goes in as it is, a RankedTopk comes out.  `index`: this rank's distributed.ShardedTextIndex (the corpus
+        tokenised once); `model`: a fusion_amd.encoders.CrossEncoder.  The queries are tokenised once each (tokenizer.encode_plain); the
+        pairs are assembled on the device from ids, and each rank forwards only the pairs whose documents it owns.  depth: only the first
+        `depth` entries of every list are reranked."""
+        qtok, qlen = model.tokenizer.encode_plain(list(queries), model.max_length - 2)     # the most a pair row can keep of a query
+        dev = index.Doff.device
+        return index.rerank(model, qtok.to(dev), qlen.to(dev), candidates, k=return_topk, depth=depth)
+
 
 def _pack_by_dicts(ranked_lists: dict):
     """The reference's own data flow, entry by entry (any hashable id): corpus position = first-seen order of the ids."""

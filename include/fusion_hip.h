@@ -665,6 +665,43 @@ int fz_bm25_doc_scores_fwd_pv_f64(const int64_t* toff, const int32_t* pdoc, cons
                                   const int32_t* fpos, const int64_t* qoff, const int32_t* qterms, int Q, int N, const int32_t* docs, int G,
                                   double* out, void* stream);
 
+/* ---- cross-encoder pairs assembled from token ids (csrc/crosspack.hip; ABI 20, additive) ---------------------------------------------------
+ * The monoBERT rerank (hybrid.py:139-163) over top-k lists: the pair rows "<s> q </s></s> d </s>" of the packed forward are built on the
+ * device from the queries' token ids and a token store of the corpus, sharded by document: tok [sumL] int32, Doff [N + 1] int64 (document d
+ * of the shard = global id id_base + d holds the first Doff[d+1] - Doff[d] plain tokens of its text, no specials), doc_full_len [N] int32
+ * or NULL: the documents' plain lengths before the store cut them (NULL: nothing was cut).  cand / ldc / cand_len / id_base: the slot
+ * rules of fz_maxsim_pairs_f16 -- a slot is this shard's iff r < cand_len[q] and 0 <= cand[q][r] - id_base < N, the subtraction in 64 bits.
+ * The pair rule, with B = max_length - (2 + nsep) and lq = qlen[q] (the query's plain length before any cut), ld the document's:
+ *   FZ_PAIR_LONGEST_FIRST  the `tokenizers` library's longest_first: lq + ld <= B keeps both; else n1 = min(lq, ld), n2 = max(n1, B - n1),
+ *                          and if n1 + n2 > B still, n1 = B / 2, n2 = n1 + B % 2; the STRICTLY longer sequence keeps n2 (a tie: the
+ *                          document).  The row is bos, query, nsep separators, document, eos.
+ *   FZ_PAIR_TAIL           the row is bos + (query ++ nsep separators ++ document)[: max_length - 2] + eos: the separators are ordinary
+ *                          tokens and are cut before the document is.
+ * A kept count never exceeds what is stored (Lq columns of qtok, the document's stored tokens).
+ * fz_pair_plan: one thread per slot; kq / kd / L [Q][W] int32 (contiguous): the kept query and document tokens and the pair's row count
+ * L = 2 + kq + separators + kd; all three 0 for a slot that is not this shard's, for which nothing is read.  Checks, in this order: a
+ * negative size, ldc < W, an unknown mode, max_length < 2 + nsep or a null pointer (cand, qlen, kq, kd, L; Doff when N > 0) where a
+ * non-empty tensor is needed -> FZ_ERR_ARG; nsep > fz_pair_max_sep() (2) or Q * W >= 2^31 -> FZ_ERR_UNSUPPORTED; Q == 0 or W == 0 ->
+ * FZ_OK with nothing launched.
+ * fz_pair_fill: the packed rows of ONE forward sub-batch: pairs [P] int32 flat slots q * W + r in forward order, cu_rows [P + 1] int32
+ * with cu_rows[p+1] - cu_rows[p] = L of pair p and cu_rows[P] <= T, kq / kd the plan's planes, qtok [Q][ldq] int32 (Lq columns), the
+ * special ids -> ids [T] and pos_ids [T] int64, what fz_embed_layernorm_f32 takes: pos_ids = pad_idx + 1 + column.  One wave per pair.
+ * Token type ids are not written (type 0 everywhere).  A pair whose plan does not fit what is stored (slot outside the plane or the shard,
+ * kept counts beyond the row or the document) reads nothing and is written as pad_idx tokens at position pad_idx; the caller guarantees
+ * that the stored token ids index inside the embedding table.  Checks, in this order: a negative size or special id, ldc < W, ldq < Lq
+ * or (P > 0) a null pointer among pairs, cu_rows, kq, kd, cand, Doff, ids / pos_ids (T > 0), qtok (Lq > 0) -> FZ_ERR_ARG; nsep beyond
+ * fz_pair_max_sep() or Q * W >= 2^31 -> FZ_ERR_UNSUPPORTED; P == 0 -> FZ_OK with nothing launched.
+ * No workspace, no atomics, no host synchronisation. */
+#define FZ_PAIR_LONGEST_FIRST 0
+#define FZ_PAIR_TAIL 1
+int fz_pair_max_sep(void);
+int fz_pair_plan(const int64_t* cand, int ldc, const int32_t* cand_len, int Q, int W, int64_t id_base, const int64_t* Doff,
+                 const int32_t* doc_full_len, int N, const int32_t* qlen, int Lq, int max_length, int mode, int nsep, int32_t* kq, int32_t* kd,
+                 int32_t* L, void* stream);
+int fz_pair_fill(const int32_t* pairs, const int32_t* cu_rows, int P, int T, const int32_t* kq, const int32_t* kd, const int64_t* cand, int ldc,
+                 int Q, int W, int64_t id_base, const int32_t* qtok, int ldq, int Lq, const int32_t* tok, const int64_t* Doff, int N, int bos,
+                 int sep, int eos, int pad_idx, int nsep, int64_t* ids, int64_t* pos_ids, void* stream);
+
 /* ---- encoder side: the per-sequence parts of SentenceTransformer.encode (hybrid.py:97-102) on PACKED token rows -- */
 /* Self-attention of a BERT/CamemBERT layer for ragged sequences without padding: for every sequence and head,
  * out = softmax(q k^T * scale) v in fp32 (MFMA products, online softmax over 16-key tiles), scale > 0.  qkv [T][ld] = fused
