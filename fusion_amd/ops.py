@@ -2436,11 +2436,18 @@ def pair_fill(pairs: torch.Tensor, cu_rows: torch.Tensor, T: int, kq: torch.Tens
     return out[0], out[1]
 
 
+ATTN_MAX_SEQ = 16384
+
+
 def attn_strips(lengths, cu_rows=None):
     """HOST helper: the strip table fz_attn_varlen_f32 walks -- one (first row, length, first query, 0) entry per 32 queries
-    of every sequence, longest sequences first.  Returns (strips int32 [n_strips, 4] numpy, cu_rows int32 [B+1] numpy)."""
+    of every sequence, longest sequences first.  Returns (strips int32 [n_strips, 4] numpy, cu_rows int32 [B+1] numpy).
+    A sequence holds at most ATTN_MAX_SEQ rows: the kernels' in-sequence byte offsets are 32-bit (include/fusion_hip.h)."""
     import numpy as np
     lengths = np.asarray(lengths, dtype=np.int64)
+    _need(lengths.size == 0 or int(lengths.min()) >= 0, "attn_strips: a sequence length is negative")
+    _need(lengths.size == 0 or int(lengths.max()) <= ATTN_MAX_SEQ,
+          f"attn_strips: a sequence is longer than {ATTN_MAX_SEQ} rows, the most fz_attn_varlen_* addresses")
     if cu_rows is None:
         cu_rows = np.zeros(len(lengths) + 1, dtype=np.int64)
         np.cumsum(lengths, out=cu_rows[1:])
