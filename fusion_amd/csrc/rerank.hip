@@ -1,184 +1,43 @@
-// rerank.hip -- K2b: exact ColBERT MaxSim of every query against ITS OWN candidate list (the corpus-scale rerank stage).
+// rerank.hip -- K2b: exact ColBERT MaxSim of every query against ITS OWN candidate list over float16 token rows.
 //
-// scores[q][r] = s(q, cand[q][r] - id_base) with s as in maxsim.hip, bit for bit: the same v_mfma_f32_16x16x32_f16 mapping (A = 16
-// document tokens x 32 dims, B = 32 dims x 16 query tokens, k-steps 0..3 from a zero accumulator), the same fmaxf maximum from -inf
-// and the same sum (row16_sum per 16-token column block, then the pair tree (b0+b1)+(b2+b3) ...), so a system's all-pairs plane and
-// its candidate lists are interchangeable.
-//
-// The workload is a gather: every (query, candidate) pair reads its own document, one contiguous run of len x 256 B found through
-// Doff, and nothing is shared between pairs but the query (about 18 GB of token rows against 1.2 TFLOP at Q = 1024, k = 1000).
-// So the design keeps loads in flight and hangs the MFMAs off them:
-//   * a workgroup = 4 waves = one (query, slice of 128 candidate slots); workgroups are query-major, so a query's slices are
-//     dispatched next to each other;
-//   * every wave keeps the query's B fragments in registers (16 VGPRs per 16-token column block: 32 / 64 / 128 at Lq = 32 / 64 / 128)
-//     and walks its own candidates: slots slice + 4 i + w, i < 32.  Lane i resolves candidate i ONCE at the start of the wave
-//     (id -> position -> Doff pair -> clamped length: three dependent reads, paid once per wave, not once per candidate); the
-//     loop takes them back with v_readlane, so everything that steers it is in SGPRs;
-//   * document rows go straight from global memory into the A-operand registers, up to 4 row blocks (64 tokens, 16 KiB, 16
-//     global_load_dwordx4 per lane) issued back to back before the first MFMA; other waves of the SIMD cover the latency (no LDS, no
-//     barrier: waves of a workgroup never wait for each other);
-//   * a row index past the document's last token is CLAMPED to that token: the row block re-reads a real row, the maximum is
-//     unchanged and nothing needs a mask; nothing past Doff[pos + 1], past max_doc_len or past row sumL - 1 is ever read.  Row
-//     blocks wholly past the end are skipped (wave-uniform).
-// Slots: r >= cand_len[q], id < 0 or position outside [0, N) -> -inf (a shard scores what it owns); an empty document -> 0.
-//
-// Where it stands: DESIGN.md section 'Candidate-list MaxSim' and profiles/r10_maxsim_pairs.json.
-#include <hip/hip_fp16.h>
-
-#include <type_traits>
-
-#include "common.h"
+// The kernel is the slot walk of maxsim_pairs.h (its header says what is computed and why it has this shape); this file states only
+// how a row block of float16 rows reaches the A-operand registers: straight from global memory, 64 contiguous bytes of 16 rows per
+// global_load_dwordx4 of a wave, 4 row blocks in flight.
+#include "maxsim_pairs.h"
 
 namespace fz {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int MP_RB = 4;   // 16-token row blocks loaded before the MFMAs start
 
-constexpr int MP_DIM = 128;
-constexpr int MP_WAVES = 4;                  // waves per workgroup
-constexpr int MP_CPW = 32;                   // candidate slots per wave (<= 64: one lane resolves one slot)
-constexpr int MP_SLICE = MP_WAVES * MP_CPW;  // candidate slots per workgroup
-constexpr int MP_RB = 4;                     // 16-token row blocks loaded before the MFMAs start
-constexpr int MP_MAX_DOC_LEN = 16384;        // as fz_maxsim_f16
+struct PlainRows {
+    const _Float16* Dtok;     // [sumL][128]
+
+    __device__ __forceinline__ void prologue(int, int) const {}
+    // lane l reads row (l & 15) of a row block, dims 32 ks + 8 (l >> 4) .. + 7
+    __device__ __forceinline__ const _Float16* doc(int64_t t0, int, int lane) const { return Dtok + (size_t)t0 * MP_DIM + 8 * (lane >> 4); }
+    template <int NB>
+    __device__ __forceinline__ void load(const _Float16* doc, int c0, int last, int lane, f16x8 (&af)[NB][4]) const {
+#pragma unroll
+        for (int rb = 0; rb < NB; ++rb) {
+            int row = c0 + 16 * rb + (lane & 15);
+            row = row < last ? row : last;   // the last partial row block re-reads the last token: the maximum is unchanged
+            const _Float16* p = doc + (size_t)row * MP_DIM;
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) af[rb][ks] = *reinterpret_cast<const f16x8*>(p + 32 * ks);
+        }
+    }
+};
 
 struct PairsArgs {
-    const _Float16* Qtok;     // [Q][Lq][128]
-    const _Float16* Dtok;     // [sumL][128]
-    const int64_t* Doff;      // [N+1]
-    const int64_t* cand;      // [Q][ldc]
-    const int32_t* cand_len;  // [Q] or null
-    float* scores;            // [Q][lds]
-    int64_t sumL, id_base;
-    int ldc, lds, Q, N, k, max_doc_len;
-    int nslices;              // ceil(k / MP_SLICE)
+    PairSlots s;
+    PlainRows rows;
 };
 
 // NCB = Lq / 16 column blocks of 16 query tokens.
 template <int NCB>
 __global__ __launch_bounds__(MP_WAVES * 64) __attribute__((amdgpu_waves_per_eu(NCB == 2 ? 4 : 2)))
 void maxsim_pairs_kernel(PairsArgs a) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int q = blockIdx.x / a.nslices;
-    const int r_first = (blockIdx.x % a.nslices) * MP_SLICE + w;   // this wave's slots: r_first + MP_WAVES * i
-    if (r_first >= a.k) return;                                    // a wave with no candidate in this slice
-    const int left = (a.k - r_first + MP_WAVES - 1) / MP_WAVES;
-    const int nmine = left < MP_CPW ? left : MP_CPW;
-
-    // ---- lane i resolves slot r_first + MP_WAVES * i: first token row and length (-1: absent, 0: empty document) ----
-    int64_t my_t0 = 0;
-    int my_len = -1;
-    {
-        int klen = a.k;
-        if (a.cand_len) { klen = a.cand_len[q]; klen = klen < 0 ? 0 : klen < a.k ? klen : a.k; }
-        const int r = r_first + MP_WAVES * lane;
-        if (lane < nmine && r < klen) {
-            const int64_t id = a.cand[(size_t)q * a.ldc + r];
-            const uint64_t pos = (uint64_t)id - (uint64_t)a.id_base;
-            if (id >= 0 && id >= a.id_base && pos < (uint64_t)a.N) {
-                const int64_t t0 = a.Doff[pos];
-                int64_t len = a.Doff[pos + 1] - t0;
-                if (len > a.max_doc_len) len = a.max_doc_len;
-                if (len > a.sumL - t0) len = a.sumL - t0;   // offsets that disagree with sumL: never read past the last row
-                if (t0 < 0 || len < 0) len = 0;
-                my_t0 = t0;
-                my_len = (int)len;
-            }
-        }
-    }
-
-    // ---- B fragments of the query, resident for the whole wave:
-    //      lane l holds B[k = 8 (l >> 4) + j][col = l & 15] = Qtok[q][16 b + (l & 15)][32 ks + 8 (l >> 4) + j] ----
-    f16x8 bq[NCB][4];
-    {
-        const _Float16* src = a.Qtok + ((size_t)q * NCB * 16 + (lane & 15)) * MP_DIM + 8 * (lane >> 4);
-#pragma unroll
-        for (int b = 0; b < NCB; ++b)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) bq[b][ks] = *reinterpret_cast<const f16x8*>(src + (size_t)b * 16 * MP_DIM + 32 * ks);
-    }
-
-    float* const out = a.scores + (size_t)q * a.lds + r_first;
-    for (int i = 0; i < nmine; ++i) {
-        const int len = __builtin_amdgcn_readlane(my_len, i);
-        float* const dst = out + MP_WAVES * i;
-        if (len <= 0) {   // absent slot / empty document (sum of an empty max := 0, as in maxsim.hip)
-            if (lane == 0) *dst = len < 0 ? -INFINITY : 0.f;
-            continue;
-        }
-        const int64_t t0 = ((int64_t)__builtin_amdgcn_readlane((int)(my_t0 >> 32), i) << 32) |
-                           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_t0, i);
-        // lane l reads row (l & 15) of a row block, dims 32 ks + 8 (l >> 4) .. + 7
-        const _Float16* const doc = a.Dtok + (size_t)t0 * MP_DIM + 8 * (lane >> 4);
-        const int last = len - 1;
-
-        float run[NCB];
-#pragma unroll
-        for (int b = 0; b < NCB; ++b) run[b] = -INFINITY;
-
-        for (int c0 = 0; c0 < len; c0 += 16 * MP_RB) {
-            const int nb = (len - c0 + 15) >> 4;   // row blocks left (wave-uniform); >= 1
-            // NB row blocks: every load is issued before the first MFMA; then NB x NCB four-step chains, the row blocks' chains interleaved
-            auto body = [&](auto NBc) __attribute__((always_inline)) {
-                constexpr int NB = decltype(NBc)::value;
-                f16x8 af[NB][4];
-#pragma unroll
-                for (int rb = 0; rb < NB; ++rb) {
-                    int row = c0 + 16 * rb + (lane & 15);
-                    row = row < last ? row : last;   // the last partial row block re-reads the last token: the maximum is unchanged
-                    const _Float16* p = doc + (size_t)row * MP_DIM;
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) af[rb][ks] = *reinterpret_cast<const f16x8*>(p + 32 * ks);
-                }
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb) {
-                    f32x4 acc[NB];
-#pragma unroll
-                    for (int rb = 0; rb < NB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[rb][0], bq[cb][0], (f32x4)0.f, 0, 0, 0);
-#pragma unroll
-                    for (int ks = 1; ks < 4; ++ks)
-#pragma unroll
-                        for (int rb = 0; rb < NB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[rb][ks], bq[cb][ks], acc[rb], 0, 0, 0);
-                    float m = run[cb];
-#pragma unroll
-                    for (int rb = 0; rb < NB; ++rb)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) m = fmaxf(m, acc[rb][r]);
-                    run[cb] = m;
-                }
-            };
-            if (nb >= 4) body(std::integral_constant<int, 4>{});
-            else if (nb == 3) body(std::integral_constant<int, 3>{});
-            else if (nb == 2) body(std::integral_constant<int, 2>{});
-            else body(std::integral_constant<int, 1>{});
-        }
-
-        // ---- the maximum over the four 16-lane rows, then the sum over the query tokens, in maxsim.hip's order: P / S transpose
-        //      the column blocks' partial maxima onto the rows, row16_sum adds 16 tokens, two swap steps add the blocks in pairs ----
-        auto P = [&](float A, float B) __attribute__((always_inline)) -> float { swap32(A, B); return fmaxf(A, B); };
-        auto S = [&](float X, float Y) __attribute__((always_inline)) -> float { swap16(X, Y); return fmaxf(X, Y); };
-        auto blk = [&](int b) __attribute__((always_inline)) -> float { return b < NCB ? run[b < NCB ? b : 0] : -INFINITY; };
-        float s0 = row16_sum(S(P(blk(0), blk(2)), P(blk(1), blk(3))));   // rows: column blocks 0, 1, 2, 3
-        float o0 = s0;
-        swap16(s0, o0);
-        s0 += o0;                                                        // rows (0, 1): b0 + b1 | rows (2, 3): b2 + b3
-        if constexpr (NCB >= 4) {
-            o0 = s0;
-            swap32(s0, o0);
-            s0 += o0;                                                    // (b0 + b1) + (b2 + b3)
-        }
-        if constexpr (NCB == 8) {
-            float s1 = row16_sum(S(P(blk(4), blk(6)), P(blk(5), blk(7))));
-            float o1 = s1;
-            swap16(s1, o1);
-            s1 += o1;
-            o1 = s1;
-            swap32(s1, o1);
-            s1 += o1;
-            s0 += s1;                                                    // ((b0 + b1) + (b2 + b3)) + ((b4 + b5) + (b6 + b7))
-        }
-        if (lane == 0) *dst = s0;
-    }
+    maxsim_pairs_walk<NCB, MP_RB>(a.s, a.rows);
 }
 
 }  // namespace fz
@@ -188,28 +47,16 @@ using namespace fz;
 extern "C" int fz_maxsim_pairs_f16(const void* Qtok, const void* Dtok, const int64_t* Doff, int64_t sumL, int max_doc_len, int Q, int Lq,
                                    int N, int dim, const int64_t* cand, int ldc, const int32_t* cand_len, int k, int64_t id_base,
                                    float* scores, int lds, void* stream) {
-    if (Q < 0 || N < 0 || k < 0 || Lq <= 0 || ldc < k || lds < k) return FZ_ERR_ARG;
-    if ((Q != 0 && k != 0) && (!Qtok || !cand || !scores)) return FZ_ERR_ARG;   // empty tensors carry null pointers
-    if ((Q != 0 && k != 0 && N != 0) && !Doff) return FZ_ERR_ARG;
-    if (!Dtok && sumL != 0) return FZ_ERR_ARG;   // an empty token matrix (every document empty) has no pointer to give
-    if (dim != MP_DIM) return FZ_ERR_UNSUPPORTED;
-    if (Lq != 32 && Lq != 64 && Lq != 128) return FZ_ERR_UNSUPPORTED;
-    if (((uintptr_t)Qtok % 16) || ((uintptr_t)Dtok % 16)) return FZ_ERR_UNSUPPORTED;
-    if (Q == 0 || k == 0) return FZ_OK;
-    if (sumL < 0 || max_doc_len <= 0) return FZ_ERR_ARG;
-    if (max_doc_len > MP_MAX_DOC_LEN) return FZ_ERR_UNSUPPORTED;
     PairsArgs a{};
-    a.Qtok = reinterpret_cast<const _Float16*>(Qtok);
-    a.Dtok = reinterpret_cast<const _Float16*>(Dtok);
-    a.Doff = Doff; a.cand = cand; a.cand_len = cand_len; a.scores = scores;
-    a.sumL = sumL; a.id_base = id_base; a.ldc = ldc; a.lds = lds; a.Q = Q; a.N = N; a.k = k; a.max_doc_len = max_doc_len;
-    a.nslices = (k + MP_SLICE - 1) / MP_SLICE;
-    const long nblk = (long)Q * a.nslices;
-    if (nblk > 0x7fffffffL) return FZ_ERR_UNSUPPORTED;
+    const int rc = pair_slots_args(a.s, !Dtok && sumL != 0,   // an empty token matrix (every document empty) has no pointer to give
+                                   (uintptr_t)Dtok % 16, Qtok, Doff, sumL, max_doc_len, Q, Lq, N, dim, cand, ldc, cand_len, k, id_base, scores, lds);
+    if (rc != FZ_OK || Q == 0 || k == 0) return rc;
+    a.rows.Dtok = reinterpret_cast<const _Float16*>(Dtok);
+    const unsigned nblk = (unsigned)Q * a.s.nslices;
     hipStream_t st = as_stream(stream);
-    if (Lq == 32) maxsim_pairs_kernel<2><<<(unsigned)nblk, MP_WAVES * 64, 0, st>>>(a);
-    else if (Lq == 64) maxsim_pairs_kernel<4><<<(unsigned)nblk, MP_WAVES * 64, 0, st>>>(a);
-    else maxsim_pairs_kernel<8><<<(unsigned)nblk, MP_WAVES * 64, 0, st>>>(a);
+    if (Lq == 32) maxsim_pairs_kernel<2><<<nblk, MP_WAVES * 64, 0, st>>>(a);
+    else if (Lq == 64) maxsim_pairs_kernel<4><<<nblk, MP_WAVES * 64, 0, st>>>(a);
+    else maxsim_pairs_kernel<8><<<nblk, MP_WAVES * 64, 0, st>>>(a);
     FZ_LAUNCH_CHECK();
     return FZ_OK;
 }

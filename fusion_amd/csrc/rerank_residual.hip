@@ -12,35 +12,21 @@
 // dimensions 32 ks + 8 g + j (ks < 4, j < 8) = positions 32 g + 8 ks + j: ONE aligned piece of the row, 8 bytes at offset 8 g for
 // nbits = 2, 16 bytes at offset 16 g for nbits = 4.
 //
-// fz_maxsim_pairs_residual_f16 keeps the shape of rerank.hip (workgroup = query x 128 slots, B fragments resident, one lane resolves one
-// slot per wave, scalar control, no barrier).  Per row block a lane loads its row's code, then the four 16-byte centroid fragments the
-// code points at and its residual piece, and decompresses IN PLACE into the fragment registers: the piece's bytes index a table of packed
+// fz_maxsim_pairs_residual_f16 is the slot walk of maxsim_pairs.h, the one rerank.hip runs (workgroup = query x 128 slots, B fragments
+// resident, one lane resolves one slot per wave, scalar control, no barrier), with another way of filling the A fragments.  Per row
+// block a lane loads its row's code, then the four 16-byte centroid fragments the code points at and its residual piece, and decompresses IN PLACE into the fragment registers: the piece's bytes index a table of packed
 // half weights (nbits = 2: a byte = 4 positions = 4 halves, ds_read_b64; nbits = 4: a byte = 2 positions = 2 halves, ds_read_b32; 256
 // entries, one copy per wave, filled once by the wave that reads it) and v_pk_add_f16 adds them.  The code is clamped into [0, K - 1]
 // (v_med3_i32), so no address leaves the table whatever the stored bytes are.  The codes of all row blocks of a round are issued before
 // the first fragment load (the fragment is a dependent read).  Lq = 128 keeps 2 row blocks in flight instead of 4: the maximum does not
 // depend on the grouping of the row blocks.
-//
-// Slot resolution and the closing sum are restated from rerank.hip (the bm25_walk.h precedent would share them; rerank.hip's three
-// kernels are pinned by their resource report, so they stay untouched).
-#include <hip/hip_fp16.h>
-
-#include <type_traits>
-
-#include "common.h"
+#include "maxsim_pairs.h"
 
 namespace fz {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int RR_DIM = 128;
-constexpr int RR_WAVES = 4;                  // as rerank.hip: waves per workgroup,
-constexpr int RR_CPW = 32;                   // candidate slots per wave,
-constexpr int RR_SLICE = RR_WAVES * RR_CPW;  // candidate slots per workgroup
-constexpr int RR_MAX_DOC_LEN = 16384;
 constexpr int RR_THREADS = 256;              // the two streaming kernels
 
 // dimension of the first of the 8 storage positions of group G = s >> 3 (they hold 8 consecutive dimensions)
@@ -64,8 +50,8 @@ void residual_compress_kernel(const _Float16* __restrict__ tok, const int32_t* _
     if (idx >= n * WPR) return;
     const int64_t t = idx / WPR;
     const int word = (int)(idx % WPR);
-    const _Float16* const crow = C + (size_t)clamp_code(codes[t], K) * RR_DIM;
-    const _Float16* const trow = tok + (size_t)t * RR_DIM;
+    const _Float16* const crow = C + (size_t)clamp_code(codes[t], K) * MP_DIM;
+    const _Float16* const trow = tok + (size_t)t * MP_DIM;
     uint32_t bits = 0;
 #pragma unroll
     for (int gi = 0; gi < GPW; ++gi) {
@@ -97,7 +83,7 @@ void residual_decompress_kernel(const uint8_t* __restrict__ packed, const int32_
     const int64_t t = row_lo + idx / 16;
     const int G = (int)(idx % 16);
     const int d0 = group_dim(G);
-    const f16x8 c = *reinterpret_cast<const f16x8*>(C + (size_t)clamp_code(codes[t], K) * RR_DIM + d0);
+    const f16x8 c = *reinterpret_cast<const f16x8*>(C + (size_t)clamp_code(codes[t], K) * MP_DIM + d0);
     const uint8_t* const p = packed + (size_t)t * (16 * NBITS) + G * NBITS;
     uint32_t bits;
     if constexpr (NBITS == 2) bits = *reinterpret_cast<const uint16_t*>(p);
@@ -105,25 +91,10 @@ void residual_decompress_kernel(const uint8_t* __restrict__ packed, const int32_
     f16x8 d;
 #pragma unroll
     for (int j = 0; j < 8; ++j) d[j] = c[j] + sw[(bits >> (NBITS * j)) & ((1u << NBITS) - 1)];
-    *reinterpret_cast<f16x8*>(out + (size_t)(idx / 16) * RR_DIM + d0) = d;
+    *reinterpret_cast<f16x8*>(out + (size_t)(idx / 16) * MP_DIM + d0) = d;
 }
 
-// ---- the rerank over compressed rows ---------------------------------------------------------------------------------------------
-struct ResidualPairsArgs {
-    const _Float16* Qtok;     // [Q][Lq][128]
-    const uint8_t* packed;    // [sumL][16 nbits]
-    const int32_t* codes;     // [sumL]
-    const _Float16* C;        // [K][128]
-    const _Float16* weights;  // [2^nbits]
-    const int64_t* Doff;      // [N+1]
-    const int64_t* cand;      // [Q][ldc]
-    const int32_t* cand_len;  // [Q] or null
-    float* scores;            // [Q][lds]
-    int64_t sumL, id_base;
-    int ldc, lds, Q, N, K, k, max_doc_len;
-    int nslices;              // ceil(k / RR_SLICE)
-};
-
+// ---- the rerank over compressed rows: maxsim_pairs.h's walk, the rows decompressed on their way into the A operands -----------------
 template <int NBITS> struct Piece;
 template <> struct Piece<2> { typedef uint2 reg; typedef uint2 entry; };   // 8 bytes of a row; a byte's four half weights
 template <> struct Piece<4> { typedef uint4 reg; typedef uint32_t entry; };  // 16 bytes of a row; a byte's two half weights
@@ -149,175 +120,90 @@ __device__ __forceinline__ void add_weights(f16x8& c, const uint32_t* tab, const
     c = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-// NCB = Lq / 16 column blocks of 16 query tokens; RB row blocks in flight per round.
-template <int NCB, int NBITS>
-__global__ __launch_bounds__(RR_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
-void maxsim_residual_kernel(ResidualPairsArgs a) {
-    constexpr int RB = NCB == 8 ? 2 : 4;
-    constexpr int ROW_BYTES = 16 * NBITS, PIECE_BYTES = 4 * NBITS;
+struct ResidualStore {
+    const uint8_t* packed;    // [sumL][16 nbits]
+    const int32_t* codes;     // [sumL]
+    const _Float16* C;        // [K][128]
+    const _Float16* weights;  // [2^nbits]
+    int K;
+};
+
+template <int NBITS>
+struct ResidualRows : ResidualStore {
     typedef typename Piece<NBITS>::reg piece_t;
     typedef typename Piece<NBITS>::entry entry_t;
-    __shared__ entry_t wtab[RR_WAVES][256];
+    static constexpr int ROW_BYTES = 16 * NBITS, PIECE_BYTES = 4 * NBITS;
+    struct Doc {
+        const int32_t* code;   // the document's codes
+        const uint8_t* res;    // this lane's piece of the document's first row
+        const _Float16* cbase; // this lane's 8 dimensions of centroid 0
+        const entry_t* tab;    // this wave's weight table
+    };
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int q = blockIdx.x / a.nslices;
-    const int r_first = (blockIdx.x % a.nslices) * RR_SLICE + w;   // this wave's slots: r_first + RR_WAVES * i
-    if (r_first >= a.k) return;                                    // a wave with no candidate in this slice
-    const int left = (a.k - r_first + RR_WAVES - 1) / RR_WAVES;
-    const int nmine = left < RR_CPW ? left : RR_CPW;
+    entry_t (*wtab)[256];     // [MP_WAVES][256] in LDS
 
-    // ---- this wave's weight table: entry e = the packed half weights of the 8 / nbits positions byte e holds, ascending bit fields.
-    //      Written and read by the same wave only: DS operations of a wave complete in order, so no barrier is needed ----
-    entry_t* const tab = wtab[w];
+    // this wave's weight table: entry e = the packed half weights of the 8 / nbits positions byte e holds, ascending bit fields.
+    // Written and read by the same wave only: DS operations of a wave complete in order, so no barrier is needed
+    __device__ __forceinline__ void prologue(int w, int lane) const {
+        entry_t* const tab = wtab[w];
 #pragma unroll
-    for (int e = lane; e < 256; e += 64) {
-        if constexpr (NBITS == 2) {
-            tab[e] = make_uint2(pack_halves(a.weights[e & 3], a.weights[(e >> 2) & 3]), pack_halves(a.weights[(e >> 4) & 3], a.weights[e >> 6]));
-        } else {
-            tab[e] = pack_halves(a.weights[e & 15], a.weights[e >> 4]);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-    // ---- lane i resolves slot r_first + RR_WAVES * i: first token row and length (-1: absent, 0: empty document) ----
-    int64_t my_t0 = 0;
-    int my_len = -1;
-    {
-        int klen = a.k;
-        if (a.cand_len) { klen = a.cand_len[q]; klen = klen < 0 ? 0 : klen < a.k ? klen : a.k; }
-        const int r = r_first + RR_WAVES * lane;
-        if (lane < nmine && r < klen) {
-            const int64_t id = a.cand[(size_t)q * a.ldc + r];
-            const uint64_t pos = (uint64_t)id - (uint64_t)a.id_base;
-            if (id >= 0 && id >= a.id_base && pos < (uint64_t)a.N) {
-                const int64_t t0 = a.Doff[pos];
-                int64_t len = a.Doff[pos + 1] - t0;
-                if (len > a.max_doc_len) len = a.max_doc_len;
-                if (len > a.sumL - t0) len = a.sumL - t0;   // offsets that disagree with sumL: never read past the last row
-                if (t0 < 0 || len < 0) len = 0;
-                my_t0 = t0;
-                my_len = (int)len;
-            }
-        }
-    }
-
-    // ---- B fragments of the query, resident for the whole wave (as rerank.hip) ----
-    f16x8 bq[NCB][4];
-    {
-        const _Float16* src = a.Qtok + ((size_t)q * NCB * 16 + (lane & 15)) * RR_DIM + 8 * (lane >> 4);
-#pragma unroll
-        for (int b = 0; b < NCB; ++b)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) bq[b][ks] = *reinterpret_cast<const f16x8*>(src + (size_t)b * 16 * RR_DIM + 32 * ks);
-    }
-
-    const int g = lane >> 4;
-    const _Float16* const cbase = a.C + 8 * g;
-    float* const out = a.scores + (size_t)q * a.lds + r_first;
-    for (int i = 0; i < nmine; ++i) {
-        const int len = __builtin_amdgcn_readlane(my_len, i);
-        float* const dst = out + RR_WAVES * i;
-        if (len <= 0) {   // absent slot / empty document (sum of an empty max := 0)
-            if (lane == 0) *dst = len < 0 ? -INFINITY : 0.f;
-            continue;
-        }
-        const int64_t t0 = ((int64_t)__builtin_amdgcn_readlane((int)(my_t0 >> 32), i) << 32) |
-                           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_t0, i);
-        const int32_t* const dcode = a.codes + t0;
-        const uint8_t* const dres = a.packed + (size_t)t0 * ROW_BYTES + PIECE_BYTES * g;
-        const int last = len - 1;
-
-        float run[NCB];
-#pragma unroll
-        for (int b = 0; b < NCB; ++b) run[b] = -INFINITY;
-
-        for (int c0 = 0; c0 < len; c0 += 16 * RB) {
-            const int nb = (len - c0 + 15) >> 4;   // row blocks left (wave-uniform); >= 1
-            auto body = [&](auto NBc) __attribute__((always_inline)) {
-                constexpr int NB = decltype(NBc)::value;
-                int code[NB];
-                piece_t piece[NB];
-                f16x8 af[NB][4];
-#pragma unroll
-                for (int rb = 0; rb < NB; ++rb) {   // the codes of the whole round first: the fragment loads depend on them
-                    int row = c0 + 16 * rb + (lane & 15);
-                    row = row < last ? row : last;   // the last partial row block re-reads the last token: the maximum is unchanged
-                    code[rb] = dcode[row];
-                    piece[rb] = *reinterpret_cast<const piece_t*>(dres + (size_t)row * ROW_BYTES);
-                }
-#pragma unroll
-                for (int rb = 0; rb < NB; ++rb) {
-                    const _Float16* p = cbase + (size_t)clamp_code(code[rb], a.K) * RR_DIM;
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) af[rb][ks] = *reinterpret_cast<const f16x8*>(p + 32 * ks);
-                }
-#pragma unroll
-                for (int rb = 0; rb < NB; ++rb)
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) add_weights(af[rb][ks], tab, piece[rb], ks);   // decompressed in place
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb) {
-                    f32x4 acc[NB];
-#pragma unroll
-                    for (int rb = 0; rb < NB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[rb][0], bq[cb][0], (f32x4)0.f, 0, 0, 0);
-#pragma unroll
-                    for (int ks = 1; ks < 4; ++ks)
-#pragma unroll
-                        for (int rb = 0; rb < NB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[rb][ks], bq[cb][ks], acc[rb], 0, 0, 0);
-                    float m = run[cb];
-#pragma unroll
-                    for (int rb = 0; rb < NB; ++rb)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) m = fmaxf(m, acc[rb][r]);
-                    run[cb] = m;
-                }
-            };
-            if constexpr (RB == 4) {
-                if (nb >= 4) body(std::integral_constant<int, 4>{});
-                else if (nb == 3) body(std::integral_constant<int, 3>{});
-                else if (nb == 2) body(std::integral_constant<int, 2>{});
-                else body(std::integral_constant<int, 1>{});
+        for (int e = lane; e < 256; e += 64) {
+            if constexpr (NBITS == 2) {
+                tab[e] = make_uint2(pack_halves(weights[e & 3], weights[(e >> 2) & 3]), pack_halves(weights[(e >> 4) & 3], weights[e >> 6]));
             } else {
-                if (nb >= 2) body(std::integral_constant<int, 2>{});
-                else body(std::integral_constant<int, 1>{});
+                tab[e] = pack_halves(weights[e & 15], weights[e >> 4]);
             }
         }
-
-        // ---- the maximum over the four 16-lane rows, then the sum over the query tokens: rerank.hip's tree, restated ----
-        auto P = [&](float A, float B) __attribute__((always_inline)) -> float { swap32(A, B); return fmaxf(A, B); };
-        auto S = [&](float X, float Y) __attribute__((always_inline)) -> float { swap16(X, Y); return fmaxf(X, Y); };
-        auto blk = [&](int b) __attribute__((always_inline)) -> float { return b < NCB ? run[b < NCB ? b : 0] : -INFINITY; };
-        float s0 = row16_sum(S(P(blk(0), blk(2)), P(blk(1), blk(3))));   // rows: column blocks 0, 1, 2, 3
-        float o0 = s0;
-        swap16(s0, o0);
-        s0 += o0;                                                        // rows (0, 1): b0 + b1 | rows (2, 3): b2 + b3
-        if constexpr (NCB >= 4) {
-            o0 = s0;
-            swap32(s0, o0);
-            s0 += o0;                                                    // (b0 + b1) + (b2 + b3)
-        }
-        if constexpr (NCB == 8) {
-            float s1 = row16_sum(S(P(blk(4), blk(6)), P(blk(5), blk(7))));
-            float o1 = s1;
-            swap16(s1, o1);
-            s1 += o1;
-            o1 = s1;
-            swap32(s1, o1);
-            s1 += o1;
-            s0 += s1;                                                    // ((b0 + b1) + (b2 + b3)) + ((b4 + b5) + (b6 + b7))
-        }
-        if (lane == 0) *dst = s0;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
+    __device__ __forceinline__ Doc doc(int64_t t0, int w, int lane) const {
+        const int g = lane >> 4;
+        return Doc{codes + t0, packed + (size_t)t0 * ROW_BYTES + PIECE_BYTES * g, C + 8 * g, wtab[w]};
+    }
+    template <int NB>
+    __device__ __forceinline__ void load(const Doc& d, int c0, int last, int lane, f16x8 (&af)[NB][4]) const {
+        int code[NB];
+        piece_t piece[NB];
+#pragma unroll
+        for (int rb = 0; rb < NB; ++rb) {   // the codes of the whole round first: the fragment loads depend on them
+            int row = c0 + 16 * rb + (lane & 15);
+            row = row < last ? row : last;   // the last partial row block re-reads the last token: the maximum is unchanged
+            code[rb] = d.code[row];
+            piece[rb] = *reinterpret_cast<const piece_t*>(d.res + (size_t)row * ROW_BYTES);
+        }
+#pragma unroll
+        for (int rb = 0; rb < NB; ++rb) {
+            const _Float16* p = d.cbase + (size_t)clamp_code(code[rb], K) * MP_DIM;
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) af[rb][ks] = *reinterpret_cast<const f16x8*>(p + 32 * ks);
+        }
+#pragma unroll
+        for (int rb = 0; rb < NB; ++rb)
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) add_weights(af[rb][ks], d.tab, piece[rb], ks);   // decompressed in place
+    }
+};
+
+struct ResidualPairsArgs {
+    PairSlots s;
+    ResidualStore rows;
+};
+
+// NCB = Lq / 16 column blocks of 16 query tokens; Lq = 128 keeps 2 row blocks in flight instead of 4.
+template <int NCB, int NBITS>
+__global__ __launch_bounds__(MP_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
+void maxsim_residual_kernel(ResidualPairsArgs a) {
+    __shared__ typename Piece<NBITS>::entry wtab[MP_WAVES][256];
+    maxsim_pairs_walk<NCB, NCB == 8 ? 2 : 4>(a.s, ResidualRows<NBITS>{a.rows, wtab});
 }
 
 template <int NBITS>
 static void launch_pairs(int Lq, unsigned nblk, hipStream_t st, const ResidualPairsArgs& a) {
-    if (Lq == 32) maxsim_residual_kernel<2, NBITS><<<nblk, RR_WAVES * 64, 0, st>>>(a);
-    else if (Lq == 64) maxsim_residual_kernel<4, NBITS><<<nblk, RR_WAVES * 64, 0, st>>>(a);
-    else maxsim_residual_kernel<8, NBITS><<<nblk, RR_WAVES * 64, 0, st>>>(a);
+    if (Lq == 32) maxsim_residual_kernel<2, NBITS><<<nblk, MP_WAVES * 64, 0, st>>>(a);
+    else if (Lq == 64) maxsim_residual_kernel<4, NBITS><<<nblk, MP_WAVES * 64, 0, st>>>(a);
+    else maxsim_residual_kernel<8, NBITS><<<nblk, MP_WAVES * 64, 0, st>>>(a);
 }
 
 }  // namespace fz
@@ -328,7 +214,7 @@ extern "C" int fz_residual_compress_f16(const void* tok, const int32_t* codes, c
                                         int nbits, void* packed, void* stream) {
     if (n < 0 || K < 1) return FZ_ERR_ARG;
     if (n != 0 && (!tok || !codes || !C || !cutoffs || !packed)) return FZ_ERR_ARG;
-    if (dim != RR_DIM) return FZ_ERR_UNSUPPORTED;
+    if (dim != MP_DIM) return FZ_ERR_UNSUPPORTED;
     if (nbits != 2 && nbits != 4) return FZ_ERR_UNSUPPORTED;
     if (((uintptr_t)tok % 16) || ((uintptr_t)C % 16) || ((uintptr_t)packed % 16)) return FZ_ERR_UNSUPPORTED;
     if (n == 0) return FZ_OK;
@@ -347,7 +233,7 @@ extern "C" int fz_residual_decompress_f16(const void* packed, const int32_t* cod
                                           int64_t row_lo, int64_t row_hi, int K, int dim, int nbits, void* out, void* stream) {
     if (sumL < 0 || K < 1 || row_lo < 0 || row_hi < row_lo || row_hi > sumL) return FZ_ERR_ARG;
     if (row_hi != row_lo && (!packed || !codes || !C || !weights || !out)) return FZ_ERR_ARG;
-    if (dim != RR_DIM) return FZ_ERR_UNSUPPORTED;
+    if (dim != MP_DIM) return FZ_ERR_UNSUPPORTED;
     if (nbits != 2 && nbits != 4) return FZ_ERR_UNSUPPORTED;
     if (((uintptr_t)packed % 16) || ((uintptr_t)C % 16) || ((uintptr_t)out % 16)) return FZ_ERR_UNSUPPORTED;
     if (row_hi == row_lo) return FZ_OK;
@@ -369,31 +255,18 @@ extern "C" int fz_maxsim_pairs_residual_f16(const void* Qtok, const void* packed
                                             int K, int nbits, const int64_t* Doff, int64_t sumL, int max_doc_len, int Q, int Lq, int N,
                                             int dim, const int64_t* cand, int ldc, const int32_t* cand_len, int k, int64_t id_base,
                                             float* scores, int lds, void* stream) {
-    if (Q < 0 || N < 0 || k < 0 || Lq <= 0 || K < 1 || ldc < k || lds < k) return FZ_ERR_ARG;
-    if ((Q != 0 && k != 0) && (!Qtok || !cand || !scores || !C || !weights)) return FZ_ERR_ARG;   // empty tensors carry null pointers
-    if ((Q != 0 && k != 0 && N != 0) && !Doff) return FZ_ERR_ARG;
-    if ((!packed || !codes) && sumL != 0) return FZ_ERR_ARG;   // an empty shard (every document empty) has no rows to point at
-    if (dim != RR_DIM) return FZ_ERR_UNSUPPORTED;
-    if (nbits != 2 && nbits != 4) return FZ_ERR_UNSUPPORTED;
-    if (Lq != 32 && Lq != 64 && Lq != 128) return FZ_ERR_UNSUPPORTED;
-    if (((uintptr_t)Qtok % 16) || ((uintptr_t)packed % 16) || ((uintptr_t)C % 16)) return FZ_ERR_UNSUPPORTED;
-    if (Q == 0 || k == 0) return FZ_OK;
-    if (sumL < 0 || max_doc_len <= 0) return FZ_ERR_ARG;
-    if (max_doc_len > RR_MAX_DOC_LEN) return FZ_ERR_UNSUPPORTED;
     ResidualPairsArgs a{};
-    a.Qtok = reinterpret_cast<const _Float16*>(Qtok);
-    a.packed = reinterpret_cast<const uint8_t*>(packed);
-    a.codes = codes;
-    a.C = reinterpret_cast<const _Float16*>(C);
-    a.weights = reinterpret_cast<const _Float16*>(weights);
-    a.Doff = Doff; a.cand = cand; a.cand_len = cand_len; a.scores = scores;
-    a.sumL = sumL; a.id_base = id_base; a.ldc = ldc; a.lds = lds; a.Q = Q; a.N = N; a.K = K; a.k = k; a.max_doc_len = max_doc_len;
-    a.nslices = (k + RR_SLICE - 1) / RR_SLICE;
-    const long nblk = (long)Q * a.nslices;
-    if (nblk > 0x7fffffffL) return FZ_ERR_UNSUPPORTED;
+    const int rc = pair_slots_args(a.s,
+                                   K < 1 || ((Q != 0 && k != 0) && (!C || !weights)) ||
+                                       ((!packed || !codes) && sumL != 0),   // an empty shard (every document empty) has no rows to point at
+                                   (nbits != 2 && nbits != 4) || ((uintptr_t)packed % 16) || ((uintptr_t)C % 16), Qtok, Doff, sumL, max_doc_len, Q,
+                                   Lq, N, dim, cand, ldc, cand_len, k, id_base, scores, lds);
+    if (rc != FZ_OK || Q == 0 || k == 0) return rc;
+    a.rows = {reinterpret_cast<const uint8_t*>(packed), codes, reinterpret_cast<const _Float16*>(C), reinterpret_cast<const _Float16*>(weights), K};
+    const unsigned nblk = (unsigned)Q * a.s.nslices;
     hipStream_t st = as_stream(stream);
-    if (nbits == 2) launch_pairs<2>(Lq, (unsigned)nblk, st, a);
-    else launch_pairs<4>(Lq, (unsigned)nblk, st, a);
+    if (nbits == 2) launch_pairs<2>(Lq, nblk, st, a);
+    else launch_pairs<4>(Lq, nblk, st, a);
     FZ_LAUNCH_CHECK();
     return FZ_OK;
 }

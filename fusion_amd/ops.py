@@ -280,6 +280,21 @@ def maxsim(Qtok: torch.Tensor, Dtok: torch.Tensor, Doff: torch.Tensor, out: torc
     return out
 
 
+def _maxsim_pairs_args(what: str, Qtok: torch.Tensor, Doff: torch.Tensor, cand: torch.Tensor, cand_len, out, max_doc_len):
+    """What the two candidate-list MaxSim ops check whatever the token rows are stored as: Qtok [Q, Lq, dim] float16, Doff [N + 1] int64,
+    the candidate side (_pairs_args) and max_doc_len.  -> (Qtok, Doff, cand_len, out, (Q, Lq, dim, N, k))."""
+    _dev(Qtok, torch.float16, f"{what}(Qtok)")
+    _dev(Doff, torch.int64, f"{what}(Doff)")
+    _need(Qtok.dim() == 3, f"{what}: Qtok must be [Q, Lq, dim]")
+    Qtok, Doff = Qtok.contiguous(), Doff.contiguous()
+    Q, Lq, dim = Qtok.shape
+    N = Doff.numel() - 1
+    _need(Doff.dim() == 1 and N >= 0, f"{what}: Doff must hold N + 1 offsets")
+    cand_len, out, k = _pairs_args(what, Q, Qtok.device, cand, cand_len, out)
+    _need(int(max_doc_len) >= 1, f"{what}: max_doc_len must be at least 1")
+    return Qtok, Doff, cand_len, out, (Q, Lq, dim, N, k)
+
+
 def maxsim_pairs(Qtok: torch.Tensor, Dtok: torch.Tensor, Doff: torch.Tensor, cand: torch.Tensor, cand_len: torch.Tensor | None = None, *,
                  id_base: int = 0, max_doc_len: int = 512, out: torch.Tensor | None = None) -> torch.Tensor:
     """Exact MaxSim of every query against its own candidates (fz_maxsim_pairs_f16): out[q, r] = the score ops.maxsim gives query q and
@@ -287,27 +302,9 @@ def maxsim_pairs(Qtok: torch.Tensor, Dtok: torch.Tensor, Doff: torch.Tensor, can
     int32 or None (= k everywhere).  -inf where r >= cand_len[q], the id is negative or the document is not one of this shard's N
     (id_base .. id_base + N - 1); an empty document scores 0.  `out` [Q, k] float32 may be a view of a wider plane: only its k columns
     are written.  No host synchronisation."""
-    _dev(Qtok, torch.float16, "maxsim_pairs(Qtok)")
-    _dev(Dtok, torch.float16, "maxsim_pairs(Dtok)")
-    _dev(Doff, torch.int64, "maxsim_pairs(Doff)")
-    _dev(cand, torch.int64, "maxsim_pairs(cand)")
-    _need(Qtok.dim() == 3, "maxsim_pairs: Qtok must be [Q, Lq, dim]")
-    Qtok, Dtok, Doff = Qtok.contiguous(), Dtok.contiguous(), Doff.contiguous()
-    Q, Lq, dim = Qtok.shape
-    N = Doff.numel() - 1
+    Qtok, Doff, cand_len, out, (Q, Lq, dim, N, k) = _maxsim_pairs_args("maxsim_pairs", Qtok, Doff, cand, cand_len, out, max_doc_len)
+    Dtok = _dev(Dtok, torch.float16, "maxsim_pairs(Dtok)").contiguous()
     _need(Dtok.dim() == 2 and Dtok.shape[1] == dim, f"maxsim_pairs: Dtok must be [sumL, {dim}]")
-    _need(Doff.dim() == 1 and N >= 0, "maxsim_pairs: Doff must hold N + 1 offsets")
-    _need(cand.dim() == 2 and cand.shape[0] == Q, f"maxsim_pairs: cand must be [Q = {Q}, k], got {tuple(cand.shape)}")
-    k = cand.shape[1]
-    if cand_len is not None:
-        _dev(cand_len, torch.int32, "maxsim_pairs(cand_len)")
-        _need(tuple(cand_len.shape) == (Q,), f"maxsim_pairs(cand_len): expected shape {(Q,)}, got {tuple(cand_len.shape)}")
-    if out is None:
-        out = alloc_plane(Q, k, torch.float32, Qtok.device)
-    else:
-        _dev(out, torch.float32, "maxsim_pairs(out)")
-        _need(tuple(out.shape) == (Q, k), f"maxsim_pairs(out): expected shape {(Q, k)}, got {tuple(out.shape)}")
-    _need(int(max_doc_len) >= 1, "maxsim_pairs: max_doc_len must be at least 1")
     check(_lib.lib().fz_maxsim_pairs_f16(_ptr(Qtok), _ptr(Dtok), _ptr(Doff), int(Dtok.shape[0]), int(max_doc_len), Q, Lq, N, dim, _ptr(cand),
                                          _ld(cand), _ptr(cand_len), k, int(id_base), _ptr(out), _ld(out), _stream(Qtok)),
           "fz_maxsim_pairs_f16")
@@ -2311,29 +2308,11 @@ def maxsim_pairs_residual(Qtok: torch.Tensor, packed: torch.Tensor, codes: torch
     residual_decompress(packed, codes, C, weights), bit for bit, without that matrix ever existing.  packed [sumL, 16 * nbits] uint8,
     codes [sumL] int32, C [K, 128] float16, weights [2^nbits] float16; everything else as maxsim_pairs.  No host synchronisation."""
     what = "maxsim_pairs_residual"
-    _dev(Qtok, torch.float16, f"{what}(Qtok)")
+    Qtok, Doff, cand_len, out, (Q, Lq, dim, N, k) = _maxsim_pairs_args(what, Qtok, Doff, cand, cand_len, out, max_doc_len)
+    _need(dim == 128, f"{what}: Qtok must be [Q, Lq, 128]")
     nbits = _residual_packed(what, packed, weights)
     sumL = packed.shape[0]
     C, codes = _residual_table(what, C, codes, sumL)
-    _dev(Doff, torch.int64, f"{what}(Doff)")
-    _dev(cand, torch.int64, f"{what}(cand)")
-    _need(Qtok.dim() == 3, f"{what}: Qtok must be [Q, Lq, dim]")
-    Qtok, Doff = Qtok.contiguous(), Doff.contiguous()
-    Q, Lq, dim = Qtok.shape
-    N = Doff.numel() - 1
-    _need(dim == 128, f"{what}: Qtok must be [Q, Lq, 128]")
-    _need(Doff.dim() == 1 and N >= 0, f"{what}: Doff must hold N + 1 offsets")
-    _need(cand.dim() == 2 and cand.shape[0] == Q, f"{what}: cand must be [Q = {Q}, k], got {tuple(cand.shape)}")
-    k = cand.shape[1]
-    if cand_len is not None:
-        _dev(cand_len, torch.int32, f"{what}(cand_len)")
-        _need(tuple(cand_len.shape) == (Q,), f"{what}(cand_len): expected shape {(Q,)}, got {tuple(cand_len.shape)}")
-    if out is None:
-        out = alloc_plane(Q, k, torch.float32, Qtok.device)
-    else:
-        _dev(out, torch.float32, f"{what}(out)")
-        _need(tuple(out.shape) == (Q, k), f"{what}(out): expected shape {(Q, k)}, got {tuple(out.shape)}")
-    _need(int(max_doc_len) >= 1, f"{what}: max_doc_len must be at least 1")
     check(_lib.lib().fz_maxsim_pairs_residual_f16(_ptr(Qtok), _ptr(packed), _ptr(codes), _ptr(C), _ptr(weights), C.shape[0], nbits, _ptr(Doff),
                                                   sumL, int(max_doc_len), Q, Lq, N, dim, _ptr(cand), _ld(cand), _ptr(cand_len), k, int(id_base),
                                                   _ptr(out), _ld(out), _stream(Qtok)), "fz_maxsim_pairs_residual_f16")

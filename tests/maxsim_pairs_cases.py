@@ -5,8 +5,8 @@ The corpus: clean documents of every EDGE_LENS length and three empty ones at th
 ones, 37 poisoned rows before Doff[0], 41 after Doff[N], and a last clean document of 530 tokens that every max_doc_len of the sweep
 truncates, so its tail -- the last rows any document owns -- is poison as well.
 
-The case table restates the launch arithmetic of csrc/rerank.hip in plain Python (pairs_plan) and names, for every k and max_doc_len of
-the sweep, the wave-uniform branches of the kernel that value is there for (K_CLAIMS, M_CLAIMS; branches_of checks them); BRANCHES lists
+The case table restates the launch arithmetic of csrc/maxsim_pairs.h (with rerank.hip's 4 row blocks in flight) in plain Python
+(pairs_plan) and names, for every k and max_doc_len of the sweep, the wave-uniform branches of the kernel that value is there for (K_CLAIMS, M_CLAIMS; branches_of checks them); BRANCHES lists
 every branch the sweep as a whole must land on."""
 import functools
 
@@ -14,7 +14,7 @@ import numpy as np
 
 import maxsim_cases as M
 
-# csrc/rerank.hip
+# csrc/maxsim_pairs.h; MP_RB: csrc/rerank.hip
 MP_WAVES, MP_CPW, MP_RB = 4, 32, 4
 MP_SLICE = MP_WAVES * MP_CPW
 

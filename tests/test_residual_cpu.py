@@ -248,9 +248,21 @@ def test_the_residual_kernels_hold_everything_in_registers(tmp_path):
     assert not any("maxsim_pairs_kernel" in n for n in rep)      # the uncompressed kernel lives in rerank.hip alone
 
 
+def test_the_residual_kernels_keep_their_registers_and_occupancy(tmp_path):
+    """The six kernels' VGPRs and waves per SIMD as recorded (DESIGN.md 'One walk, two storages'; the nbits = 4 figures are the ones
+    profiles/r23_colbert_residual_shared_walk.json was measured with).  Their walk is csrc/maxsim_pairs.h, shared with rerank.hip: an
+    edit there that moves a schedule fails here first, and is then due a measurement, not a new number."""
+    rep = _report(tmp_path, "rerank_residual")
+    by = {tuple(int(x) for x in n.split("<")[1].split(">")[0].split(",")): r for n, r in rep.items() if "maxsim_residual_kernel" in n}
+    assert sorted(by) == [(ncb, nbits) for ncb in (2, 4, 8) for nbits in (2, 4)], sorted(by)
+    assert [by[n, 2]["vgprs"] for n in (2, 4, 8)] == [120, 162, 240] and [by[n, 2]["occupancy"] for n in (2, 4, 8)] == [4, 3, 2]
+    assert [by[n, 4]["vgprs"] for n in (2, 4, 8)] == [152, 168, 240] and [by[n, 4]["occupancy"] for n in (2, 4, 8)] == [3, 3, 2]
+
+
 def test_the_uncompressed_rerank_kernels_are_unchanged(tmp_path):
-    """rerank.hip is not touched by the compressed path: its report lists the three kernels it listed, with the registers and occupancy
-    they had before the compressed path existed (Lq = 32 / 64 / 128: 106 / 168 / 250 VGPRs, 4 / 3 / 2 waves per SIMD)."""
+    """The walk rerank.hip shares with the compressed path (csrc/maxsim_pairs.h) costs the plain kernels nothing: the report lists the
+    three kernels it listed, with the registers and occupancy they had when the walk was theirs alone (Lq = 32 / 64 / 128: 106 / 168 /
+    250 VGPRs, 4 / 3 / 2 waves per SIMD)."""
     rep = _report(tmp_path, "rerank")
     assert len(rep) == 3 and all("maxsim_pairs_kernel" in n for n in rep), sorted(rep)
     by_ncb = {int(n.split("<")[1].split(">")[0]): r for n, r in rep.items()}
