@@ -44,6 +44,7 @@ _PROTOS = {
     "fz_normalize_rows_f32": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "fz_dot_scores_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "fz_dot_scores_filter_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "fz_dot_scores_plan": (_i, [_i, _i, _i, _i, _i, _vp]),
     "fz_dot_topn_max": (_i, []),
     "fz_dot_topn_workspace_bytes": (_sz, [_i, _i, _i]),
     "fz_dot_topn_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

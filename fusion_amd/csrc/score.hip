@@ -683,29 +683,79 @@ extern "C" int fz_normalize_rows_f32(const float* X, int rows, int d, int ldx, f
     return FZ_OK;
 }
 
-static int launch_gemm(GemmArgs& g, int epi, hipStream_t st) {
+// The dispatch plan: everything launch_gemm derives from the shape, the epilogue and the CU count -- a pure host function, so that
+// fz_dot_scores_plan can show it on a machine without a GPU (tests/score_cases.py lands every branch below through it).
+struct GemmPlan {
+    int slab_rows, slab_row0;  // the straggler slab (0: none) ...
+    int rows;                  // ... and the rows left to the tiles
+    int QB, TN, full, halves, tail_ids, tail_row0, tail_rows;   // as in GemmArgs
+    int cover7, nP, nQ;        // the 7-row-block cover: taken, 128 x 192 tiles, 96 x 256 tiles
+    int grid;                  // workgroups launched
+    int ragged;                // d is not a whole number of k-tile pairs: the instantiation with the ragged-d masks
+    int slots;                 // resident workgroups (two per CU), a multiple of the 8 XCDs
+};
+
+static int gemm_plan(int Q, int N, int d, int epi, int cus, GemmPlan& p) {
+    p = GemmPlan{};
     // the last 1..4 rows over a multiple of 32 ride as ONE slab inside the 64-row tail tiles: Q % 128 in 65 .. 68 (195: the LLeQA test batch).
     // Measured (profiles/r05_gemm_slabs_ab.json): Q = 195 0.0907 -> 0.0867 ms (0.587 -> 0.614 of the fp32-MFMA peak), Q = 193 0.0888 -> 0.0852; two
     // slabs (Q = 197 .. 200) bring nothing over the 7-row-block cover (0.629 vs 0.636), three (Q = 201) lose: those batches keep the cover.
     static const bool slabs_on = [] { const char* e = getenv("FZ_GEMM_SLABS"); return !(e && e[0] == '0'); }();   // (A/B runs)
-    g.slab_rows = 0; g.slab_row0 = 0;
-    if (epi == EPI_STORE && slabs_on && g.Q % BM > 64 && g.Q % BM <= 68) {
-        g.slab_rows = g.Q % BM - 64;
-        g.slab_row0 = g.Q - g.slab_rows;
-        g.Q = g.slab_row0;                                 // the tiles see the rows before the stragglers only
+    p.rows = Q;
+    if (epi == EPI_STORE && slabs_on && Q % BM > 64 && Q % BM <= 68) {
+        p.slab_rows = Q % BM - 64;
+        p.slab_row0 = Q - p.slab_rows;
+        p.rows = p.slab_row0;                              // the tiles see the rows before the stragglers only
     }
+    p.ragged = d % (2 * BK) != 0;
     // rows -> whole 128-row query blocks + a last block in its own height class (32, 64 or 96 rows; more than 96: a padded whole block)
-    int nfull = g.Q / BM;
-    const int rem = g.Q % BM;
+    int nfull = p.rows / BM;
+    const int rem = p.rows % BM;
     int tail = 0;
     if (epi == EPI_SPLADE || rem > 96) nfull += rem > 0;
     else if (rem > 0) tail = (rem + 31) / 32 * 32;
-    g.QB = nfull;
-    g.TN = (g.N + 127) / 128;
-    const long TN8 = 8L * ((g.TN + 7) / 8);             // corpus-tile ids incl. the XCD padding, which decodes to nothing
+    p.QB = nfull;
+    p.TN = (N + 127) / 128;
+    const long TN8 = 8L * ((p.TN + 7) / 8);             // corpus-tile ids incl. the XCD padding, which decodes to nothing
     const long B = TN8 * nfull;                           // ids of whole tiles
-    g.tail_ids = tail ? (int)TN8 : 0; g.tail_row0 = nfull * BM; g.tail_rows = tail;
-    const long Bt = g.tail_ids;
+    p.tail_ids = tail ? (int)TN8 : 0; p.tail_row0 = nfull * BM; p.tail_rows = tail;
+    const long Bt = p.tail_ids;
+    if (epi == EPI_STORE && p.rows > 192 && p.rows <= 224) {   // the 7-row-block cover, when its tiles fit the chip in one round
+        const long nP = ((long)N + 191) / 192, nQ = ((long)N + 255) / 256;
+        if (nP + nQ <= cus) {
+            p.cover7 = 1; p.nP = (int)nP; p.nQ = (int)nQ;
+            p.grid = (int)(nP + nQ);
+            return FZ_OK;
+        }
+    }
+    const long slots = 2L * cus / 8 * 8;                 // resident workgroups (two per CU), a multiple of the 8 XCDs
+    if (slots <= 0 || B + Bt > 0x3fffffffL) return FZ_ERR_UNSUPPORTED;
+    p.slots = (int)std::min(slots, 0x3fffffffL);
+    long R = B % slots;                                  // the partial last round ...
+    if (R > slots / 2 || B < slots || Bt > 0) R = 0;     // ... is only worth halving when it is at most half full (and nothing follows it)
+    p.full = (int)(B - R);
+    p.halves = (int)(2 * R);
+    const long ids = B + Bt;
+    p.grid = (int)(ids < slots ? ids : slots);
+    return FZ_OK;
+}
+
+// (host only, no HIP call) the plan of a Q x N x d launch with epilogue epi (0 store, 1 filter, 2 SPLADE) on a device of `cus` compute units:
+// out[FZ_DOT_SCORES_PLAN_FIELDS = 16], in the order of GemmPlan
+extern "C" int fz_dot_scores_plan(int Q, int N, int d, int epi, int cus, int32_t* out) {
+    if (Q < 0 || N < 0 || d <= 0 || epi < EPI_STORE || epi > EPI_SPLADE || cus <= 0 || !out) return FZ_ERR_ARG;
+    if (d % 4) return FZ_ERR_UNSUPPORTED;
+    GemmPlan p{};
+    if (Q > 0 && N > 0) {                          // (an empty problem launches nothing: all zeros)
+        if (int rc = gemm_plan(Q, N, d, epi, cus, p)) return rc;
+    }
+    const int32_t f[16] = {p.slab_rows, p.slab_row0, p.rows, p.QB, p.TN, p.full, p.halves, p.tail_ids, p.tail_row0, p.tail_rows,
+                           p.cover7, p.nP, p.nQ, p.grid, p.ragged, p.slots};
+    std::copy(f, f + 16, out);
+    return FZ_OK;
+}
+
+static int launch_gemm(GemmArgs& g, int epi, hipStream_t st) {
     static int cus[64];
     int dev = 0;
     FZ_HIP_TRY(hipGetDevice(&dev));
@@ -713,41 +763,32 @@ static int launch_gemm(GemmArgs& g, int epi, hipStream_t st) {
     if (!cus[dev]) FZ_HIP_TRY(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
     // per-lane offsets are signed 32-bit byte offsets inside one operand tile (at most 256 rows)
     if (256.0 * g.lda * 4 >= 2147483648.0 || 256.0 * g.ldb * 4 >= 2147483648.0) return FZ_ERR_UNSUPPORTED;
-    if (epi == EPI_STORE && g.Q > 192 && g.Q <= 224) {   // the 7-row-block cover, when its tiles fit the chip in one round
-        const long nP = (g.N + 191) / 192, nQ = (g.N + 255) / 256;
-        if (nP + nQ <= cus[dev]) {
-            constexpr size_t lds_c7 = 2 * (96 + 256) * LDT * sizeof(float);
-            static unsigned long long c7_set[2] = {0ull, 0ull};
-            const bool rg = g.d % (2 * BK) != 0;
-            if (rg) {
-                if (int rc = raise_lds_limit((const void*)dot_scores_cover7_kernel<true>, lds_c7, c7_set[1])) return rc;
-                dot_scores_cover7_kernel<true><<<(unsigned)(nP + nQ), 256, lds_c7, st>>>(g, (int)nP);
-            } else {
-                if (int rc = raise_lds_limit((const void*)dot_scores_cover7_kernel<false>, lds_c7, c7_set[0])) return rc;
-                dot_scores_cover7_kernel<false><<<(unsigned)(nP + nQ), 256, lds_c7, st>>>(g, (int)nP);
-            }
-            FZ_LAUNCH_CHECK();
-            return FZ_OK;
+    GemmPlan p;
+    if (int rc = gemm_plan(g.Q, g.N, g.d, epi, cus[dev], p)) return rc;
+    g.slab_rows = p.slab_rows; g.slab_row0 = p.slab_row0; g.Q = p.rows;
+    g.QB = p.QB; g.TN = p.TN; g.full = p.full; g.halves = p.halves;
+    g.tail_ids = p.tail_ids; g.tail_row0 = p.tail_row0; g.tail_rows = p.tail_rows;
+    if (p.grid <= 0) return FZ_OK;
+    if (p.cover7) {
+        constexpr size_t lds_c7 = 2 * (96 + 256) * LDT * sizeof(float);
+        static unsigned long long c7_set[2] = {0ull, 0ull};
+        if (p.ragged) {
+            if (int rc = raise_lds_limit((const void*)dot_scores_cover7_kernel<true>, lds_c7, c7_set[1])) return rc;
+            dot_scores_cover7_kernel<true><<<(unsigned)p.grid, 256, lds_c7, st>>>(g, p.nP);
+        } else {
+            if (int rc = raise_lds_limit((const void*)dot_scores_cover7_kernel<false>, lds_c7, c7_set[0])) return rc;
+            dot_scores_cover7_kernel<false><<<(unsigned)p.grid, 256, lds_c7, st>>>(g, p.nP);
         }
+        FZ_LAUNCH_CHECK();
+        return FZ_OK;
     }
-    const long slots = 2L * cus[dev] / 8 * 8;            // resident workgroups (two per CU), a multiple of the 8 XCDs
-    if (slots <= 0 || B + Bt > 0x3fffffffL) return FZ_ERR_UNSUPPORTED;
-    long R = B % slots;                                  // the partial last round ...
-    if (R > slots / 2 || B < slots || Bt > 0) R = 0;     // ... is only worth halving when it is at most half full (and nothing follows it)
-    g.full = (int)(B - R);
-    g.halves = (int)(2 * R);
-    const long ids = B + Bt;
-    const long nblk = ids < slots ? ids : slots;
-    if (nblk <= 0) return FZ_OK;
     constexpr size_t lds_db = 2 * (BM + 128) * LDT * sizeof(float);
-    // per-lane offsets are signed 32-bit byte offsets inside one 128-row operand tile
-    if (128.0 * g.lda * 4 >= 2147483648.0 || 128.0 * g.ldb * 4 >= 2147483648.0) return FZ_ERR_UNSUPPORTED;
     static unsigned long long lds_set[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
-    const bool ragged = g.d % (2 * BK) != 0;
+    const bool ragged = p.ragged;
 #define FZ_GEMM_LAUNCH(RG, EP)                                                                                                   \
     {                                                                                                                            \
         if (int rc = raise_lds_limit((const void*)dot_scores_kernel<RG, EP>, lds_db, lds_set[3 * RG + EP])) return rc;           \
-        dot_scores_kernel<RG, EP><<<(unsigned)nblk, 256, lds_db, st>>>(g);                                                       \
+        dot_scores_kernel<RG, EP><<<(unsigned)p.grid, 256, lds_db, st>>>(g);                                                     \
     }
     if (ragged && epi == EPI_FILTER) FZ_GEMM_LAUNCH(true, EPI_FILTER)
     else if (ragged && epi == EPI_SPLADE) FZ_GEMM_LAUNCH(true, EPI_SPLADE)

@@ -74,6 +74,22 @@ int fz_dot_scores_f32(const float* Qn, int ldq, const float* Dn, int ldd, int Q,
 int fz_dot_scores_filter_f32(const float* Qn, int ldq, const float* Dn, int ldd, int Q, int N, int d, int64_t id_base,
                              const float* tau_padded, float* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap,
                              int32_t* overflow, void* stream);
+/* (ABI 20, additive) The dispatch plan of the three entries above and of fz_splade_head_max_f32: what their launcher derives from the shape,
+ * the epilogue (epi: 0 score plane, 1 filter, 2 SPLADE pooling with Q = T, N = V) and the device's compute-unit count `cus` -- the launcher
+ * itself runs this function.  Host only, no HIP call: it answers on a machine without a GPU (tests/score_cases.py proves its coverage of the
+ * launcher's branches through it).  out[FZ_DOT_SCORES_PLAN_FIELDS]:
+ *    0 slab_rows   rows riding as a 4-row slab in the 64-row tail tiles (Q % 128 in 65 .. 68, score plane only; FZ_GEMM_SLABS=0 turns it off)
+ *    1 slab_row0   first of them                     2 rows       rows left to the tiles
+ *    3 QB          whole 128-row query blocks (a last block of more than 96 rows -- SPLADE: of any height -- is padded to one)
+ *    4 TN          128-column corpus tiles           5 full       ids (incl. XCD padding ids) run as whole 128 x 128 tiles
+ *    6 halves      128 x 64 half tiles of the halved last round
+ *    7 tail_ids    ids of the last query block's tiles (0: none)      8 tail_row0  its first row      9 tail_rows  its height: 32, 64 or 96
+ *   10 cover7      1: the 7-row-block cover (193 .. 224 rows, score plane only, 11 nP + 12 nQ tiles <= cus)
+ *   13 grid        workgroups launched               14 ragged    d % 64 != 0      15 slots  resident workgroups, 2 * cus rounded down to 8
+ * All zeros for an empty problem (Q == 0 or N == 0).  Negative sizes, d <= 0, epi outside 0 .. 2, cus <= 0 or out == NULL -> FZ_ERR_ARG;
+ * d % 4 != 0, cus < 4 or more tile ids than 2^30 - 1 -> FZ_ERR_UNSUPPORTED, as the entries themselves answer. */
+#define FZ_DOT_SCORES_PLAN_FIELDS 16
+int fz_dot_scores_plan(int Q, int N, int d, int epi, int cus, int32_t* out);
 
 /* (ABI 20, additive) The same GEMM with a top-n selection as its epilogue: out_scores / out_ids [rows][n] = the n best columns of every row
  * of X . C^T by (score desc, id asc), (-inf, -1) padding when n > K -- bit for bit fz_topk_rows_f32(fz_dot_scores_f32(X, C), n), with no
