@@ -149,6 +149,8 @@ _PROTOS = {
     "fz_segment_mean_f32": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp]),
     "fz_segment_splade_max_f32": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp]),
     "fz_splade_head_max_f32": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "fz_splade_head_max_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "fz_splade_head_f16_tile": (_i, [_vp, _vp, _vp, _vp]),
     "fz_fill_i32": (_i, [_vp, _sz, C.c_int32, _vp]),
     "fz_f64_to_f32": (_i, [_vp, _vp, _sz, _vp]),
 }

@@ -264,6 +264,7 @@ class PackedBertForward(FusedBertForward):
     # residual + LayerNorm -- stays in float32 here (autocast keeps LayerNorm and softmax in float32 and lets GELU follow its float16
     # input: this forward is never less precise than that).  None = float32 Linears.
     amp_dtype = None
+    hidden16 = None         # float16 copy of the last hidden_packed's result when the float16 layers ran (the last LayerNorm's out16), else None
 
     def _low(self, t: torch.Tensor) -> torch.Tensor:
         """The weight / bias in amp_dtype, converted once."""
@@ -298,6 +299,7 @@ class PackedBertForward(FusedBertForward):
             ops.gelu_f16_(h16); mark("encode_gelu")
             y16 = F.linear(h16, lo(ly["w2"]), lo(ly["b2"])); mark("encode_gemm")
             x = ops.add_layernorm_x16(y16, x, *ly["ln2"], out16=x16); mark("encode_ln")
+        self.hidden16 = x16[:T]                    # the last LayerNorm's rounded copy: the float16 SPLADE head's operand, no conversion pass
         return x
 
     @staticmethod
@@ -326,6 +328,7 @@ class PackedBertForward(FusedBertForward):
         tables = torch.from_numpy(np.concatenate([strips.reshape(-1), cu])).to(dev, non_blocking=True)
         strips_d, cu_d = tables[: strips.size].view(-1, 4), tables[strips.size:]
         if T == 0:
+            self.hidden16 = None
             return torch.zeros((0, self.word.shape[1]), dtype=torch.float32, device=dev), cu_d
         cols = np.arange(T, dtype=np.int64) - np.repeat(cu[:-1].astype(np.int64), lengths)
         host = np.concatenate([np.repeat(np.arange(n, dtype=np.int64) * Lmax, lengths) + cols, cols + (self.pad_idx + 1)])
@@ -359,6 +362,7 @@ class PackedBertForward(FusedBertForward):
             ctx[T:].zero_()
         mark = mark or (lambda name: None)
         mark("encode_embed")
+        self.hidden16 = None
         if self.amp_dtype == torch.float16 and self.word.shape[1] % 8 == 0 and self.layers[0]["w1"].shape[0] % 8 == 0:
             return self._layers_f16(x, ctx, strips_d, H, mark, T)[:T]
         for ly in self.layers:
@@ -381,13 +385,23 @@ class PackedBertForward(FusedBertForward):
 
 
 class DenseEncoder(_Base):
-    """DPR bi-encoder: CamemBERT + mean pooling over the attention mask, fp32."""
+    """DPR bi-encoder: CamemBERT + mean pooling over the attention mask, fp32.
+    amp=True (opt-in, GPU only) runs the packed forward with float16 Linears and float16-MFMA attention over a float32 residual stream
+    (PackedBertForward._layers_f16, the path the ColBERT encoder ships); pooling stays fz_segment_mean_f32 over the float32 stream.  The
+    reference runs DPR in float32, which stays the default."""
 
-    def __init__(self, backbone, tokenizer, device):
+    def __init__(self, backbone, tokenizer, device, amp: bool = False):
         super().__init__(tokenizer, device)
+        self.amp = bool(amp) and self._device.type == "cuda"
         self.backbone = backbone.to(self._device).eval()
         self.dim = backbone.config.hidden_size
         self._clamp_lengths(backbone.config)
+
+    def _packed_forward(self, backbone):
+        fwd = super()._packed_forward(backbone)
+        if fwd is not None:
+            fwd.amp_dtype = torch.float16 if self.amp else None
+        return fwd
 
     @torch.no_grad()
     def encode_ids(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
@@ -407,7 +421,7 @@ class DenseEncoder(_Base):
         """Same embeddings again, padding-free (PackedBertForward: HIP attention / LayerNorm / pooling kernels)."""
         if getattr(self, "_packed", None) is None:
             self._packed = PackedBertForward(self.backbone)
-        return self._packed(input_ids, lengths, mark=mark)   # raises for head_dim != 64
+        return self._packed_forward(self.backbone)(input_ids, lengths, mark=mark)   # raises for head_dim != 64
 
     @torch.no_grad()
     def encode_ids_corpus(self, input_ids: torch.Tensor, lengths) -> torch.Tensor:
@@ -453,15 +467,26 @@ class DenseEncoder(_Base):
 
 
 class SpladeEncoder(_Base):
-    """SPLADE-max: amax over tokens of log1p(relu(MLM logits * mask))  (splade/splade.py:88-99)."""
+    """SPLADE-max: amax over tokens of log1p(relu(MLM logits * mask))  (splade/splade.py:88-99).
+    amp=True (opt-in, GPU only): the packed backbone runs PackedBertForward._layers_f16, and a fusable RoBERTa-style head (dense,
+    layer_norm, decoder) runs in float16 too -- float16 dense Linear, fz_gelu_f16, fz_add_layernorm_x16 and fz_splade_head_max_f16 over the
+    float16 copy of the last hidden rows, float32 accumulation throughout.  A head that is not fusable, or FUSED_HEAD = False, keeps the
+    float32 head on the float32 stream: only the backbone is mixed then.  The reference runs SPLADE in float32, which stays the default."""
     similarity = "cos_sim"   # BaseModel's default (splade/base.py): index() and search() L2-normalise both sides; "dot_score": raw weights
     INDEX_BLOCK = 4096       # documents per encode() call of index(): the dense rows of one block (0.5 GB at 32,005 terms) are all it holds
 
-    def __init__(self, mlm, tokenizer, device):
+    def __init__(self, mlm, tokenizer, device, amp: bool = False):
         super().__init__(tokenizer, device)
+        self.amp = bool(amp) and self._device.type == "cuda"
         self.mlm = mlm.to(self._device).eval()
         self.dim = mlm.config.vocab_size
         self._clamp_lengths(mlm.config)
+
+    def _packed_forward(self, backbone):
+        fwd = super()._packed_forward(backbone)
+        if fwd is not None:
+            fwd.amp_dtype = torch.float16 if self.amp else None
+        return fwd
 
     @torch.no_grad()
     def encode_ids(self, input_ids, attention_mask) -> torch.Tensor:
@@ -485,11 +510,12 @@ class SpladeEncoder(_Base):
     FUSED_HEAD = True       # False: decoder GEMM -> [T, vocab] logits -> fz_segment_splade_max_f32 (the reference's shape, splade.py:94)
 
     @torch.no_grad()
-    def _pool_packed(self, x: torch.Tensor, cu_d: torch.Tensor, mark=None) -> torch.Tensor:
+    def _pool_packed(self, x: torch.Tensor, cu_d: torch.Tensor, mark=None, x16: torch.Tensor | None = None) -> torch.Tensor:
         """MLM head + SPLADE-max pooling over packed hidden rows x [T, hidden] of the sequences cu_d [n+1] -> [n, vocab].
         With a RoBERTa-style head (dense -> GELU -> LayerNorm -> decoder) the vocabulary projection runs as fz_splade_head_max_f32: the
         pooling is the GEMM's epilogue and the [T, vocab] logits -- 4.2 GB per batch of 64 x 512 tokens in the reference, splade.py:94,
-        ~1 TB over the LLeQA corpus -- are never written."""
+        ~1 TB over the LLeQA corpus -- are never written.  x16 (the forward's float16 copy of x, PackedBertForward.hidden16) with amp: the
+        same head on float16 operands, fz_splade_head_max_f16 ("splade_head_pool_f16" for the `mark` hook)."""
         from . import ops
         head = self.mlm.lm_head
         fused = self.FUSED_HEAD and all(hasattr(head, n) for n in ("dense", "layer_norm", "decoder")) and x.shape[0] > 0
@@ -501,10 +527,19 @@ class SpladeEncoder(_Base):
                 out = part if out is None else torch.maximum(out, part)
             if mark: mark("splade_head_pool")
             return out
+        bias = head.decoder.bias if head.decoder.bias is not None else torch.zeros(head.decoder.weight.shape[0], device=x.device)
+        if self.amp and x16 is not None and x16.shape == x.shape and x16.shape[1] % 8 == 0 and head.dense.weight.shape[0] % 8 == 0:
+            lo = self._packed._low
+            h16 = torch.nn.functional.linear(x16, lo(head.dense.weight), lo(head.dense.bias))
+            ops.gelu_f16_(h16)
+            g16 = torch.empty_like(h16)
+            ops.add_layernorm_x16(h16, None, head.layer_norm.weight, head.layer_norm.bias, head.layer_norm.eps, out16=g16)
+            out = ops.splade_head_max_f16(g16, lo(head.decoder.weight), bias.float().contiguous(), cu_d)
+            if mark: mark("splade_head_pool_f16")
+            return out
         h = torch.nn.functional.linear(x, head.dense.weight, head.dense.bias)
         h = ops.gelu_(h) if h.numel() % 4 == 0 and h.is_contiguous() else torch.nn.functional.gelu(h)
         h = ops.add_layernorm(h, None, head.layer_norm.weight, head.layer_norm.bias, head.layer_norm.eps)
-        bias = head.decoder.bias if head.decoder.bias is not None else torch.zeros(head.decoder.weight.shape[0], device=x.device)
         out = ops.splade_head_max(h, head.decoder.weight, bias.contiguous(), cu_d)
         if mark: mark("splade_head_pool")
         return out
@@ -521,7 +556,7 @@ class SpladeEncoder(_Base):
         for idx in _id_batches(lengths, self.HEAD_TOKENS):
             sel = torch.from_numpy(idx).to(self._device)
             x, cu_d = fwd.hidden(input_ids.index_select(0, sel), lengths[idx], mark)
-            out[sel] = self._pool_packed(x, cu_d, mark)
+            out[sel] = self._pool_packed(x, cu_d, mark, fwd.hidden16)
         return out
 
     @torch.no_grad()
@@ -533,7 +568,7 @@ class SpladeEncoder(_Base):
             self.packed_tokens = min(self.packed_tokens, self.HEAD_TOKENS)
             for idx, ids, lens in _token_batches(self, sentences, max_len, batch_size):
                 x, cu_d = fwd.hidden(ids.to(self._device, non_blocking=True), lens)
-                out[torch.tensor(idx, device=self._device)] = self._pool_packed(x, cu_d)
+                out[torch.tensor(idx, device=self._device)] = self._pool_packed(x, cu_d, None, fwd.hidden16)
             return out
         for idx, ids, mask in self._batches(sentences, batch_size, max_len):
             out[torch.tensor(idx, device=self._device)] = self.encode_ids(ids, mask).float()
@@ -765,10 +800,11 @@ class ColbertEncoder(_Base):
         return tok.contiguous(), torch.from_numpy(off).to(self._device)
 
 
-def random_init(kind: str, device="cuda", size: str = "base", seed: int = 0, tokenizer: str = "hash"):
+def random_init(kind: str, device="cuda", size: str = "base", seed: int = 0, tokenizer: str = "hash", amp: bool | None = None):
     """CamemBERT-base-shaped (or tiny) encoder with random weights: `kind` in {'dpr','splade','colbert'}.
     tokenizer: 'hash' (whitespace words hashed into the vocabulary) or 'synth-fr' (base size only: the 32,005-piece BPE of
-    tokenization.SynthFrenchTokenizer -- real sub-word work on the host)."""
+    tokenization.SynthFrenchTokenizer -- real sub-word work on the host).
+    amp: None keeps each kind's own precision (DPR and SPLADE float32, ColBERT mixed); a bool overrides it."""
     cfg = dict(CAMEMBERT_BASE if size == "base" else TINY)
     g = torch.random.get_rng_state()
     torch.manual_seed(seed)
@@ -781,11 +817,11 @@ def random_init(kind: str, device="cuda", size: str = "base", seed: int = 0, tok
         else:
             tok = HashTokenizer(cfg["vocab_size"], cfg["pad_token_id"], cfg["bos_token_id"], cfg["eos_token_id"])
         if kind == "dpr":
-            return DenseEncoder(_backbone(cfg), tok, device)
+            return DenseEncoder(_backbone(cfg), tok, device, amp=bool(amp))
         if kind == "splade":
-            return SpladeEncoder(_backbone(cfg, mlm=True), tok, device)
+            return SpladeEncoder(_backbone(cfg, mlm=True), tok, device, amp=bool(amp))
         if kind == "colbert":
-            return ColbertEncoder(_backbone(cfg), tok, device)
+            return ColbertEncoder(_backbone(cfg), tok, device) if amp is None else ColbertEncoder(_backbone(cfg), tok, device, amp=bool(amp))
         raise ValueError(kind)
     finally:
         torch.random.set_rng_state(g)
@@ -804,10 +840,11 @@ def _checkpoint_tensor(model_name_or_path: str, name: str) -> torch.Tensor | Non
     return None
 
 
-def from_pretrained(model_name_or_path: str, kind: str, device="cuda"):
+def from_pretrained(model_name_or_path: str, kind: str, device="cuda", amp: bool | None = None):
     """Load a real checkpoint from a local directory / HF cache (no network on the build boxes).
     kind: 'dpr' (AutoModel + mean pooling), 'splade' (AutoModelForMaskedLM), 'colbert' (colbert-ai layout: base model +
-    `linear.weight` + artifact.metadata), 'monobert' (AutoModelForSequenceClassification, hybrid.py:139-163)."""
+    `linear.weight` + artifact.metadata), 'monobert' (AutoModelForSequenceClassification, hybrid.py:139-163).
+    amp: None keeps each kind's own precision (DPR, SPLADE and monoBERT float32, ColBERT as its metadata says); a bool overrides it."""
     import json
     import string
     from transformers import AutoModel, AutoModelForMaskedLM, AutoModelForSequenceClassification, AutoTokenizer
@@ -838,9 +875,9 @@ def from_pretrained(model_name_or_path: str, kind: str, device="cuda"):
             return dict(mode="longest_first", nsep=hf_tok.num_special_tokens_to_add(pair=True) - 2, bos=hf_tok.cls_token_id,
                         sep=hf_tok.sep_token_id, eos=hf_tok.sep_token_id)
     if kind == "dpr":
-        return DenseEncoder(AutoModel.from_pretrained(model_name_or_path, local_files_only=True), _Tok(), device)
+        return DenseEncoder(AutoModel.from_pretrained(model_name_or_path, local_files_only=True), _Tok(), device, amp=bool(amp))
     if kind == "splade":
-        return SpladeEncoder(AutoModelForMaskedLM.from_pretrained(model_name_or_path, local_files_only=True), _Tok(), device)
+        return SpladeEncoder(AutoModelForMaskedLM.from_pretrained(model_name_or_path, local_files_only=True), _Tok(), device, amp=bool(amp))
     if kind == "colbert":
         meta = {}
         mp = os.path.join(model_name_or_path, "artifact.metadata")       # colbert-ai's ColBERTConfig dump
@@ -859,7 +896,8 @@ def from_pretrained(model_name_or_path: str, kind: str, device="cuda"):
                              linear_weight=lin,
                              q_marker_id=hf_tok.convert_tokens_to_ids(meta.get("query_token_id", "[unused0]")),
                              d_marker_id=hf_tok.convert_tokens_to_ids(meta.get("doc_token_id", "[unused1]")),
-                             attend_to_mask_tokens=bool(meta.get("attend_to_mask_tokens", True)), amp=bool(meta.get("amp", True)))
+                             attend_to_mask_tokens=bool(meta.get("attend_to_mask_tokens", True)),
+                             amp=bool(meta.get("amp", True)) if amp is None else bool(amp))
         enc.max_query_length = min(enc.max_query_length, int(meta.get("query_maxlen", enc.max_query_length)))   # hybrid.py:129 passes 64 / 512
         enc.max_doc_length = min(enc.max_doc_length, int(meta.get("doc_maxlen", enc.max_doc_length)))
         return enc
@@ -874,7 +912,7 @@ def from_pretrained(model_name_or_path: str, kind: str, device="cuda"):
             act = "identity"
         else:
             raise ValueError(f"cross-encoder activation {act!r} is not supported")
-        return CrossEncoder(model, _Tok(), device, activation=act)
+        return CrossEncoder(model, _Tok(), device, activation=act, amp=bool(amp))
     raise ValueError(kind)
 
 

@@ -2594,6 +2594,28 @@ def splade_head_max(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, c
     return pool
 
 
+def splade_head_max_f16(x16: torch.Tensor, weight16: torch.Tensor, bias: torch.Tensor, cu_rows: torch.Tensor) -> torch.Tensor:
+    """splade_head_max for the mixed-precision encoders: x16 [T, d] and weight16 [V, d] float16, bias [V] float32, cu_rows [B+1] int32 ->
+    [B, V] fp32, products accumulated in float32 (fz_splade_head_max_f16: v_mfma_f32_32x32x16_f16 tiles with the same pooling epilogue).
+    d must be a multiple of 8 (ValueError: there is no padding copy); rows 16-byte aligned."""
+    _dev(x16, torch.float16, "splade_head_max_f16(x16)"); _dev(weight16, torch.float16, "splade_head_max_f16(weight16)")
+    _dev(bias, torch.float32, "splade_head_max_f16(bias)"); _dev(cu_rows, torch.int32, "splade_head_max_f16(cu_rows)")
+    _need(x16.dim() == 2 and weight16.dim() == 2, "splade_head_max_f16: x16 [T, d] and weight16 [V, d] expected")
+    T, d = x16.shape
+    V = weight16.shape[0]
+    B = cu_rows.numel() - 1
+    _need(weight16.shape[1] == d and bias.numel() == V and bias.is_contiguous(), f"splade_head_max_f16: weight16 [V, {d}] and bias [V] expected")
+    _need(cu_rows.is_contiguous() and B >= 0, "splade_head_max_f16: cu_rows must hold B + 1 contiguous offsets")
+    _need(d % 8 == 0, f"splade_head_max_f16: d = {d} is not a multiple of 8")
+    ldp = max(round_up(V, _PAD), _PAD)
+    pool = torch.zeros((max(B, 1), ldp), dtype=torch.float32, device=x16.device)[:B, :V]     # zero = log1p(relu(.)) of an empty sequence
+    if T == 0 or B == 0:
+        return pool
+    check(_lib.lib().fz_splade_head_max_f16(_ptr(x16), x16.stride(0) if T > 1 else d, _ptr(weight16), weight16.stride(0) if V > 1 else d, _ptr(bias),
+                                            _ptr(cu_rows), B, T, V, d, _ptr(pool), ldp, _stream(x16)), "fz_splade_head_max_f16")
+    return pool
+
+
 def segment_mean(x: torch.Tensor, cu_rows: torch.Tensor) -> torch.Tensor:
     """Mean over each sequence's rows: x [T, d] fp32, cu_rows [B+1] int32 -> [B, d]."""
     return _segment_reduce("fz_segment_mean_f32", x, cu_rows)

@@ -98,8 +98,11 @@ class Ranker:
 
     @staticmethod
     def single_vector_search(queries: list[str], corpus: dict[int, str], model_name_or_path: str, return_topk: int = None,
-                             *, encoder=None, as_device: bool = False, cache_dir: str | None = None):
+                             *, encoder=None, as_device: bool = False, cache_dir: str | None = None, amp: bool = False):
         """hybrid.py:77-106: encode docs + queries (batch 64), cosine similarity, full ranking.
+        `amp` (opt-in) builds the encoder in mixed precision (encoders.from_pretrained(.., amp=True): float16 Linears, attention and SPLADE
+        head over a float32 residual stream); an injected `encoder` keeps its own setting.  The corpus cache key carries the precision of
+        the encoder that runs: a float32 cache and a mixed one never answer for each other.
         `encoder` (optional) injects an already-built fusion_amd.encoders module (e.g. random_init for synthetic runs);
         `cache_dir` (optional) keeps the encoded corpus on disk, keyed by (checkpoint, corpus text) -- the sweep of
         scripts/run_hybrid.sh otherwise re-encodes the corpus in each of its 99 processes."""
@@ -107,8 +110,9 @@ class Ranker:
         documents = list(corpus.values())
         ids = np.array(list(corpus.keys()))
         kind = "splade" if "splade" in model_name_or_path.lower() else "dpr"
-        model = encoder if encoder is not None else encoders.from_pretrained(model_name_or_path, kind, device=_device())
-        key = encoders.corpus_cache_key(model_name_or_path, documents, kind) if cache_dir else ""
+        model = encoder if encoder is not None else encoders.from_pretrained(model_name_or_path, kind, device=_device(), amp=bool(amp))
+        precision = kind + "-amp16" if getattr(model, "amp", False) else kind      # (float32: the key of every cache written so far)
+        key = encoders.corpus_cache_key(model_name_or_path, documents, precision) if cache_dir else ""
         if kind == "splade":
             # SPLADE vectors are a few hundred non-zeros of 32,005: the corpus side is kept (and cached) as an inverted index of its
             # L2-normalised rows -- tens of MB instead of the dense 3.6 GB -- and scored by fz_sparse_dot_f32: the products of the dense
@@ -911,19 +915,22 @@ def main(args):
 
     cache = join(args.output_dir, "corpus_cache") if not getattr(args, "no_corpus_cache", False) else None
 
+    amp = bool(getattr(args, "encoder_amp", False))
+
     def enc(kind):
         if synth:   # random-init CamemBERT-shaped encoder (no checkpoints offline)
-            return encoders.random_init(kind, device=_device(), size=getattr(args, "synthetic_model", "tiny"))
+            return encoders.random_init(kind, device=_device(), size=getattr(args, "synthetic_model", "tiny"),
+                                        amp=True if amp and kind in ("dpr", "splade") else None)
         return None
     if args.run_bm25:
         print(f"{sep}\n# Ranking with BM25\n{sep}")
         results["bm25"] = Ranker.bm25_search(queries, corpus, do_preprocessing=False, k1=2.5, b=0.2, as_device=True)
     if args.run_dpr:
         print(f"{sep}\n# Ranking with DPR\n{sep}")
-        results["dpr"] = Ranker.single_vector_search(queries, corpus, MODEL_CKPTS["dpr"][args.models_domain], encoder=enc("dpr"), as_device=True, cache_dir=cache)
+        results["dpr"] = Ranker.single_vector_search(queries, corpus, MODEL_CKPTS["dpr"][args.models_domain], encoder=enc("dpr"), as_device=True, cache_dir=cache, amp=amp)
     if args.run_splade:
         print(f"{sep}\n# Ranking with SPLADE\n{sep}")
-        results["splade"] = Ranker.single_vector_search(queries, corpus, MODEL_CKPTS["splade"][args.models_domain], encoder=enc("splade"), as_device=True, cache_dir=cache)
+        results["splade"] = Ranker.single_vector_search(queries, corpus, MODEL_CKPTS["splade"][args.models_domain], encoder=enc("splade"), as_device=True, cache_dir=cache, amp=amp)
     if args.run_colbert:
         print(f"{sep}\n# Ranking with ColBERT\n{sep}")
         results["colbert"] = Ranker.multi_vector_search(queries, corpus, MODEL_CKPTS["colbert"][args.models_domain], encoder=enc("colbert"), as_device=True, cache_dir=cache)
@@ -1043,6 +1050,8 @@ def build_parser():
     parser.add_argument("--synthetic_model", type=str, default="tiny", choices=["tiny", "base"])
     parser.add_argument("--no_corpus_cache", action="store_true", default=False, help="do not keep encoded corpora under <output_dir>/corpus_cache")
     parser.add_argument("--rerank_topk", type=int, default=100, help="candidates per query handed to monoBERT")
+    parser.add_argument("--encoder_amp", action="store_true", default=False,
+                        help="run the DPR and SPLADE encoders in mixed precision (float16 Linears, attention and SPLADE head; float32 is the reference's arithmetic)")
     return parser
 
 

@@ -773,6 +773,16 @@ int fz_segment_splade_max_f32(const float* x, int ldx, const int32_t* cu_rows, i
  * d % 4 == 0, 16-byte aligned rows. */
 int fz_splade_head_max_f32(const float* X, int ldx, const float* W, int ldw, const float* bias, const int32_t* cu_rows, int nseq, int T, int V,
                            int d, float* pool, int ldp, void* stream);
+/* (ABI 20, additive) The same head for the mixed-precision encoders: X16 [T][ldx] and W16 [V][ldw] are float16, the products are accumulated in
+ * float32 on the matrix pipe (v_mfma_f32_32x32x16_f16: a product of two float16 values is exact in float32), bias and pool are float32, pool
+ * MUST be zero on entry, and no [T][V] plane is written.  The contract of fz_splade_head_max_f32 with one change: d, ldx and ldw must be
+ * multiples of 8 and both operand pointers 16-byte aligned (anything else: FZ_ERR_UNSUPPORTED); every argument is judged on the host, in that
+ * entry's order, before anything touches the device.  Hidden values are finite by contract: the float16 encoder path lives with the float16
+ * range already, and an infinity or NaN in X16 or W16 pools to an unspecified value. */
+int fz_splade_head_max_f16(const void* X16, int ldx, const void* W16, int ldw, const float* bias, const int32_t* cu_rows, int nseq, int T, int V,
+                           int d, float* pool, int ldp, void* stream);
+/* (host only, no HIP call) the tile constants of fz_splade_head_max_f16: output tile rows x cols, the k-tile and the MFMA k-step in halves */
+int fz_splade_head_f16_tile(int* rows, int* cols, int* ktile, int* kstep);
 
 /* ---- small utilities ------------------------------------------------------------------ */
 int fz_fill_i32(int32_t* p, size_t count, int32_t value, void* stream);
