@@ -280,6 +280,84 @@ def maxsim(Qtok: torch.Tensor, Dtok: torch.Tensor, Doff: torch.Tensor, out: torc
     return out
 
 
+E4M3_SCALE_EXP = (-8, 15)   # fz_quantize_e4m3_f16's range of scale_exp
+
+
+def _e4m3_exp(e, what: str) -> int:
+    _need(isinstance(e, (int, np.integer)) and not isinstance(e, bool) and E4M3_SCALE_EXP[0] <= int(e) <= E4M3_SCALE_EXP[1],
+          f"{what}: scale exponent {e!r} outside the integers {E4M3_SCALE_EXP[0]} .. {E4M3_SCALE_EXP[1]}")
+    return int(e)
+
+
+def _e4m3_bytes(t: torch.Tensor, what: str) -> torch.Tensor:
+    """e4m3 storage is torch.uint8; a torch.float8_e4m3fn tensor is the same bytes."""
+    if isinstance(t, torch.Tensor) and t.dtype == torch.float8_e4m3fn:
+        t = t.view(torch.uint8)
+    return _dev(t, torch.uint8, what)
+
+
+def quantize_e4m3(x: torch.Tensor, scale_exp: int = 8) -> torch.Tensor:
+    """OCP e4m3fn bytes of x * 2^scale_exp (fz_quantize_e4m3_f16): float16 device tensor in, uint8 tensor of the same shape out.  Round to
+    nearest-even, subnormals kept, +-448 saturation (inf included), NaN -> 0x7f | sign.  The default 8: L2-normalised components have
+    |x| <= 1, so |y| <= 256 < 448, and components down to 2^-14 stay in the normal range."""
+    _dev(x, torch.float16, "quantize_e4m3(x)")
+    scale_exp = _e4m3_exp(scale_exp, "quantize_e4m3")
+    x = x.contiguous()
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    check(_lib.lib().fz_quantize_e4m3_f16(_ptr(x), x.numel(), scale_exp, _ptr(out), _stream(x)), "fz_quantize_e4m3_f16")
+    return out
+
+
+_E4M3_TABLE: dict = {}
+
+
+def e4m3_table() -> np.ndarray:
+    """The 256 values of OCP e4m3fn as float32 (0x7f / 0xff: NaN)."""
+    b = np.arange(256)
+    e, m = (b >> 3) & 15, (b & 7).astype(np.float64)
+    v = np.where(e == 0, m * 2.0 ** -9, (1 + m / 8) * 2.0 ** (e - 7.0))
+    v[(b & 0x7f) == 0x7f] = np.nan
+    return np.where(b & 0x80, -v, v).astype(np.float32)
+
+
+def dequantize_e4m3(b: torch.Tensor, scale_exp: int = 8) -> torch.Tensor:
+    """float32 values of e4m3 bytes, divided by 2^scale_exp: a 256-entry table gather in torch (tests and tools; no kernel)."""
+    b = _e4m3_bytes(b, "dequantize_e4m3(b)")
+    scale_exp = _e4m3_exp(scale_exp, "dequantize_e4m3")
+    key = (b.device, scale_exp)
+    if key not in _E4M3_TABLE:
+        _E4M3_TABLE[key] = torch.from_numpy(e4m3_table() * np.float32(2.0 ** -scale_exp)).to(b.device)
+    return _E4M3_TABLE[key][b.long()]
+
+
+def maxsim_e4m3(Q8: torch.Tensor, D8: torch.Tensor, Doff: torch.Tensor, *, q_exp: int = 8, d_exp: int = 8, out: torch.Tensor | None = None,
+                max_doc_len: int | None = None) -> torch.Tensor:
+    """ops.maxsim over e4m3 token bytes (fz_maxsim_e4m3): the exact MaxSim of the dequantised tokens, Q8 [Q, Lq, 128] and D8 [sumL, 128]
+    uint8 (or torch.float8_e4m3fn) as quantize_e4m3 wrote them with q_exp and d_exp.  Every dot product is accumulated in float32 on the
+    16x16x128 block-scaled MFMA; the finished sum is multiplied by 2^-(q_exp + d_exp)."""
+    Q8 = _e4m3_bytes(Q8, "maxsim_e4m3(Q8)")
+    D8 = _e4m3_bytes(D8, "maxsim_e4m3(D8)")
+    _dev(Doff, torch.int64, "maxsim_e4m3(Doff)")
+    q_exp, d_exp = _e4m3_exp(q_exp, "maxsim_e4m3(q_exp)"), _e4m3_exp(d_exp, "maxsim_e4m3(d_exp)")
+    _need(Q8.dim() == 3, "maxsim_e4m3: Q8 must be [Q, Lq, dim]")
+    Q8, D8, Doff = Q8.contiguous(), D8.contiguous(), Doff.contiguous()
+    Q, Lq, dim = Q8.shape
+    N = Doff.numel() - 1
+    _need(D8.dim() == 2 and D8.shape[1] == dim, f"maxsim_e4m3: D8 must be [sumL, {dim}]")
+    _need(N >= 0, "maxsim_e4m3: Doff must hold N + 1 offsets")
+    if out is None:
+        out = alloc_plane(Q, N, torch.float32, Q8.device)
+    else:
+        _dev(out, torch.float32, "maxsim_e4m3(out)")
+        _need(tuple(out.shape) == (Q, N), f"maxsim_e4m3(out): expected shape {(Q, N)}, got {tuple(out.shape)}")
+    if max_doc_len is None:
+        max_doc_len = max(int((Doff[1:] - Doff[:-1]).max().item()), 1) if N > 0 else 1
+    _need(int(max_doc_len) >= 1, f"maxsim_e4m3: max_doc_len = {max_doc_len} must be positive")
+    check(_lib.lib().fz_maxsim_e4m3(_ptr(Q8), _ptr(D8), _ptr(Doff), int(D8.shape[0]), int(max_doc_len), Q, Lq, N, dim, q_exp + d_exp,
+                                    _ptr(out), _ld(out), _stream(Q8)), "fz_maxsim_e4m3")
+    return out
+
+
 def _maxsim_pairs_args(what: str, Qtok: torch.Tensor, Doff: torch.Tensor, cand: torch.Tensor, cand_len, out, max_doc_len):
     """What the two candidate-list MaxSim ops check whatever the token rows are stored as: Qtok [Q, Lq, dim] float16, Doff [N + 1] int64,
     the candidate side (_pairs_args) and max_doc_len.  -> (Qtok, Doff, cand_len, out, (Q, Lq, dim, N, k))."""

@@ -151,9 +151,12 @@ class Ranker:
 
     @staticmethod
     def multi_vector_search(queries: list[str], corpus: dict[int, str], model_name_or_path: str, output_dir: str = "output",
-                            return_topk: int = None, *, encoder=None, as_device: bool = False, cache_dir: str | None = None):
+                            return_topk: int = None, *, encoder=None, as_device: bool = False, cache_dir: str | None = None,
+                            fp8: bool = False):
         """hybrid.py:108-137.  The reference goes through colbert-ai's PLAID index (approximate, candidate-pruned);
-        here every (query, document) pair gets its exact MaxSim score on the device, a superset ranking of PLAID's."""
+        here every (query, document) pair gets its exact MaxSim score on the device, a superset ranking of PLAID's.
+        fp8 (opt-in): the float16 token matrix (same cache, same key) and the queries are quantised on the device to e4m3 at scale 2^8
+        (ops.quantize_e4m3) and scored by ops.maxsim_e4m3: the exact MaxSim of the quantised tokens."""
         from .. import encoders
         documents = list(corpus.values())
         ids = np.array(list(corpus.keys()))
@@ -167,7 +170,10 @@ class Ranker:
         Dtok, Doff = encoders.cached_tensors(cache_dir, key, ["tok", "off"], lambda: model.encode_docs(documents, batch_size=64))
         Dtok, Doff = Dtok.to(_device()), Doff.to(_device())
         Qtok = model.encode_queries(queries, batch_size=64)
-        scores = ops.maxsim(Qtok, Dtok, Doff, max_doc_len=model.max_doc_length)
+        if fp8:
+            scores = ops.maxsim_e4m3(ops.quantize_e4m3(Qtok), ops.quantize_e4m3(Dtok), Doff, max_doc_len=model.max_doc_length)
+        else:
+            scores = ops.maxsim(Qtok, Dtok, Doff, max_doc_len=model.max_doc_length)
         rs = _rank_scores(scores, ids, return_topk)
         del Dtok, Qtok
         if encoder is None:
@@ -933,7 +939,8 @@ def main(args):
         results["splade"] = Ranker.single_vector_search(queries, corpus, MODEL_CKPTS["splade"][args.models_domain], encoder=enc("splade"), as_device=True, cache_dir=cache, amp=amp)
     if args.run_colbert:
         print(f"{sep}\n# Ranking with ColBERT\n{sep}")
-        results["colbert"] = Ranker.multi_vector_search(queries, corpus, MODEL_CKPTS["colbert"][args.models_domain], encoder=enc("colbert"), as_device=True, cache_dir=cache)
+        results["colbert"] = Ranker.multi_vector_search(queries, corpus, MODEL_CKPTS["colbert"][args.models_domain], encoder=enc("colbert"), as_device=True, cache_dir=cache,
+                                                        fp8=bool(getattr(args, "colbert_fp8", False)))
 
     if args.analyze_score_distributions:
         print(f"{sep}\n# Analyzing the score distributions per system\n{sep}")
@@ -1052,6 +1059,8 @@ def build_parser():
     parser.add_argument("--rerank_topk", type=int, default=100, help="candidates per query handed to monoBERT")
     parser.add_argument("--encoder_amp", action="store_true", default=False,
                         help="run the DPR and SPLADE encoders in mixed precision (float16 Linears, attention and SPLADE head; float32 is the reference's arithmetic)")
+    parser.add_argument("--colbert_fp8", action="store_true", default=False,
+                        help="score ColBERT over e4m3 tokens (quantised on the device at scale 2^8; float16 is the default and the reference's storage)")
     return parser
 
 

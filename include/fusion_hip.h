@@ -118,6 +118,20 @@ int fz_dot_topn_f32(const float* X, int ldx, const float* C, int ldc, int rows, 
  * (tests/test_gpu_maxsim_edges.py::test_special_values).  L2-normalised token vectors never get there. */
 int fz_maxsim_f16(const void* Qtok, const void* Dtok, const int64_t* Doff, int64_t sumL, int max_doc_len, int Q, int Lq, int N,
                   int dim, float* scores, int lds, void* stream);
+/* The same score over OCP e4m3fn token storage (csrc/maxsim8.hip), one byte per component.
+ * fz_quantize_e4m3_f16: dst[i] = e4m3(src[i] * 2^scale_exp) for n float16 values: the product is exact in float32 and rounded to
+ * nearest-even (subnormals in steps of 2^-9, -0 keeps its sign); every |y| that rounds above 448, +-inf included, saturates to +-448
+ * (0x7e / 0xfe); NaN -> 0x7f with the sign bit kept.  A fixed function of the float16 value: the same bytes on every device and grid.
+ * scale_exp outside [-8, 15], n < 0 or a null pointer with n > 0 -> FZ_ERR_ARG; n == 0 -> FZ_OK.
+ * fz_maxsim_e4m3: scores[q][j] = 2^-descale_exp * sum_{i<Lq} max_{t in doc j} <Qtok8[q][i], Dtok8[t]> over the DEQUANTISED bytes: each
+ * 128-term dot product is accumulated in float32 by one 16x16x128 block-scaled MFMA with both hardware scales at 2^0, the power-of-two
+ * descale (normally the sum of the two quantiser exponents) multiplies the finished sum once and is exact.  Everything else -- Doff,
+ * sumL, max_doc_len (<= 16384), dim == 128, Lq in {32, 64, 128}, 16-byte aligned pointers, empty documents, the fmaxf definition for
+ * NaN dot products (a 0x7f / 0xff byte is NaN), the order of the argument checks and their status codes -- is fz_maxsim_f16's;
+ * |descale_exp| > 32 -> FZ_ERR_ARG. */
+int fz_quantize_e4m3_f16(const void* src, int64_t n, int scale_exp, void* dst, void* stream);
+int fz_maxsim_e4m3(const void* Qtok8, const void* Dtok8, const int64_t* Doff, int64_t sumL, int max_doc_len, int Q, int Lq, int N,
+                   int dim, int descale_exp, float* scores, int lds, void* stream);
 /* The corpus-scale form (csrc/rerank.hip): every query against ITS OWN candidate list, no [Q][N] plane.
  * scores[q][r] = the MaxSim above of query q and document cand[q][r] - id_base, for r < k.  cand [Q][ldc] int64 global ids;
  * cand_len [Q] int32 (NULL: k for every row); id_base = global id of this shard's document 0 (any int64).  Qtok, Dtok, Doff, sumL,

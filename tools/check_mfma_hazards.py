@@ -11,7 +11,10 @@ import re, sys
 
 # passes (4 cycles each) on gfx950: FLOPs of the instruction / (FLOPs per SIMD and cycle of its type) / 4
 PASSES = {"16x16x4_f32": 8, "32x32x2_f32": 16, "16x16x32_f16": 4, "16x16x32_bf16": 4, "32x32x16_f16": 8, "32x32x16_bf16": 8, "16x16x4_f64": 16,
-          "16x16x16_f16": 8, "16x16x16_bf16": 8, "32x32x8_f16": 16, "32x32x8_bf16": 16}    # the K-halved forms: at most these (conservative)
+          "16x16x16_f16": 8, "16x16x16_bf16": 8, "32x32x8_f16": 16, "32x32x8_bf16": 16,    # the K-halved forms: at most these (conservative)
+          # block-scaled, e4m3 operands: 8 passes (32 cycles per instruction measured, profiles/r24_pmc_maxsim_fp8.json); hipcc pads its result
+          # to 12 wait states inside a basic block, so 10 here (the scan asks for passes + 2)
+          "16x16x128_f8f6f4": 10}
 def need(op):
     for k, p in PASSES.items():
         if k in op:
