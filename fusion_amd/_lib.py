@@ -52,6 +52,7 @@ _PROTOS = {
     "fz_maxsim_pairs_f16": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
     "fz_quantize_e4m3_f16": (_i, [_vp, _i64, _i, _vp, _vp]),
     "fz_maxsim_e4m3": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "fz_maxsim_pairs_e4m3": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
     "fz_residual_compress_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
     "fz_residual_decompress_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp]),
     "fz_maxsim_pairs_residual_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),

@@ -29,6 +29,9 @@
 //     Doc  doc(int64_t t0, int w, int lane) const     the handle of the document whose first token row is t0
 //     void load<NB>(doc, c0, last, lane, af) const    af[rb][ks] = this lane's A fragments of rows c0 + 16 rb + (lane & 15), clamped to last
 //
+// rerank8.hip (e4m3 token rows, one block-scaled MFMA per 16 x 16 block) walks the same slots with a loop of its own over another fragment
+// type; what it shares is stated once below: pair_slot_resolve, readlane64, pair_token_sum and, on the host, pair_slots_args.
+//
 // Where it stands: DESIGN.md section 'Candidate-list MaxSim' and profiles/r10_maxsim_pairs.json.
 #pragma once
 #include <hip/hip_fp16.h>
@@ -60,6 +63,64 @@ struct PairSlots {
     int nslices;              // ceil(k / MP_SLICE)
 };
 
+// Lane `lane` of a wave resolves slot r_first + MP_WAVES * lane of query q: first token row and length (-1: absent, 0: empty document).
+// The three dependent reads (id -> position -> Doff pair) are paid once per wave; the walk takes the result back with v_readlane.
+__device__ __forceinline__ void pair_slot_resolve(const PairSlots& a, int q, int r_first, int nmine, int lane, int64_t& my_t0, int& my_len) {
+    my_t0 = 0;
+    my_len = -1;
+    int klen = a.k;
+    if (a.cand_len) { klen = a.cand_len[q]; klen = klen < 0 ? 0 : klen < a.k ? klen : a.k; }
+    const int r = r_first + MP_WAVES * lane;
+    if (lane < nmine && r < klen) {
+        const int64_t id = a.cand[(size_t)q * a.ldc + r];
+        const uint64_t pos = (uint64_t)id - (uint64_t)a.id_base;
+        if (id >= 0 && id >= a.id_base && pos < (uint64_t)a.N) {
+            const int64_t t0 = a.Doff[pos];
+            int64_t len = a.Doff[pos + 1] - t0;
+            if (len > a.max_doc_len) len = a.max_doc_len;
+            if (len > a.sumL - t0) len = a.sumL - t0;   // offsets that disagree with sumL: never read past the last row
+            if (t0 < 0 || len < 0) len = 0;
+            my_t0 = t0;
+            my_len = (int)len;
+        }
+    }
+}
+
+// lane i's 64-bit value, wave-uniform (two v_readlane)
+__device__ __forceinline__ int64_t readlane64(int64_t v, int i) {
+    return ((int64_t)__builtin_amdgcn_readlane((int)(v >> 32), i) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, i);
+}
+
+// End of a document.  run[b]: this lane's partial maximum of column block b (its query token: lane & 15; its rows: 4 (lane >> 4) ..).
+// The maximum over the four 16-lane rows, then the sum over the query tokens, in maxsim.hip's order: P / S transpose the column blocks'
+// partial maxima onto the rows, row16_sum adds 16 tokens, two swap steps add the blocks in pairs.  Lane 0 holds the score.
+template <int NCB>
+__device__ __forceinline__ float pair_token_sum(const float (&run)[NCB]) {
+    auto P = [&](float A, float B) __attribute__((always_inline)) -> float { swap32(A, B); return fmaxf(A, B); };
+    auto S = [&](float X, float Y) __attribute__((always_inline)) -> float { swap16(X, Y); return fmaxf(X, Y); };
+    auto blk = [&](int b) __attribute__((always_inline)) -> float { return b < NCB ? run[b < NCB ? b : 0] : -INFINITY; };
+    float s0 = row16_sum(S(P(blk(0), blk(2)), P(blk(1), blk(3))));   // rows: column blocks 0, 1, 2, 3
+    float o0 = s0;
+    swap16(s0, o0);
+    s0 += o0;                                                        // rows (0, 1): b0 + b1 | rows (2, 3): b2 + b3
+    if constexpr (NCB >= 4) {
+        o0 = s0;
+        swap32(s0, o0);
+        s0 += o0;                                                    // (b0 + b1) + (b2 + b3)
+    }
+    if constexpr (NCB == 8) {
+        float s1 = row16_sum(S(P(blk(4), blk(6)), P(blk(5), blk(7))));
+        float o1 = s1;
+        swap16(s1, o1);
+        s1 += o1;
+        o1 = s1;
+        swap32(s1, o1);
+        s1 += o1;
+        s0 += s1;                                                    // ((b0 + b1) + (b2 + b3)) + ((b4 + b5) + (b6 + b7))
+    }
+    return s0;
+}
+
 // NCB = Lq / 16 column blocks of 16 query tokens; RB (4 or 2) 16-token row blocks loaded before the MFMAs start.
 template <int NCB, int RB, class Rows>
 __device__ __forceinline__ void maxsim_pairs_walk(const PairSlots& a, const Rows& rows) {
@@ -74,27 +135,9 @@ __device__ __forceinline__ void maxsim_pairs_walk(const PairSlots& a, const Rows
 
     rows.prologue(w, lane);
 
-    // ---- lane i resolves slot r_first + MP_WAVES * i: first token row and length (-1: absent, 0: empty document) ----
-    int64_t my_t0 = 0;
-    int my_len = -1;
-    {
-        int klen = a.k;
-        if (a.cand_len) { klen = a.cand_len[q]; klen = klen < 0 ? 0 : klen < a.k ? klen : a.k; }
-        const int r = r_first + MP_WAVES * lane;
-        if (lane < nmine && r < klen) {
-            const int64_t id = a.cand[(size_t)q * a.ldc + r];
-            const uint64_t pos = (uint64_t)id - (uint64_t)a.id_base;
-            if (id >= 0 && id >= a.id_base && pos < (uint64_t)a.N) {
-                const int64_t t0 = a.Doff[pos];
-                int64_t len = a.Doff[pos + 1] - t0;
-                if (len > a.max_doc_len) len = a.max_doc_len;
-                if (len > a.sumL - t0) len = a.sumL - t0;   // offsets that disagree with sumL: never read past the last row
-                if (t0 < 0 || len < 0) len = 0;
-                my_t0 = t0;
-                my_len = (int)len;
-            }
-        }
-    }
+    int64_t my_t0;
+    int my_len;
+    pair_slot_resolve(a, q, r_first, nmine, lane, my_t0, my_len);
 
     // ---- B fragments of the query, resident for the whole wave:
     //      lane l holds B[k = 8 (l >> 4) + j][col = l & 15] = Qtok[q][16 b + (l & 15)][32 ks + 8 (l >> 4) + j] ----
@@ -115,9 +158,7 @@ __device__ __forceinline__ void maxsim_pairs_walk(const PairSlots& a, const Rows
             if (lane == 0) *dst = len < 0 ? -INFINITY : 0.f;
             continue;
         }
-        const int64_t t0 = ((int64_t)__builtin_amdgcn_readlane((int)(my_t0 >> 32), i) << 32) |
-                           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_t0, i);
-        const auto doc = rows.doc(t0, w, lane);
+        const auto doc = rows.doc(readlane64(my_t0, i), w, lane);
         const int last = len - 1;
 
         float run[NCB];
@@ -160,30 +201,7 @@ __device__ __forceinline__ void maxsim_pairs_walk(const PairSlots& a, const Rows
             }
         }
 
-        // ---- the maximum over the four 16-lane rows, then the sum over the query tokens, in maxsim.hip's order: P / S transpose
-        //      the column blocks' partial maxima onto the rows, row16_sum adds 16 tokens, two swap steps add the blocks in pairs ----
-        auto P = [&](float A, float B) __attribute__((always_inline)) -> float { swap32(A, B); return fmaxf(A, B); };
-        auto S = [&](float X, float Y) __attribute__((always_inline)) -> float { swap16(X, Y); return fmaxf(X, Y); };
-        auto blk = [&](int b) __attribute__((always_inline)) -> float { return b < NCB ? run[b < NCB ? b : 0] : -INFINITY; };
-        float s0 = row16_sum(S(P(blk(0), blk(2)), P(blk(1), blk(3))));   // rows: column blocks 0, 1, 2, 3
-        float o0 = s0;
-        swap16(s0, o0);
-        s0 += o0;                                                        // rows (0, 1): b0 + b1 | rows (2, 3): b2 + b3
-        if constexpr (NCB >= 4) {
-            o0 = s0;
-            swap32(s0, o0);
-            s0 += o0;                                                    // (b0 + b1) + (b2 + b3)
-        }
-        if constexpr (NCB == 8) {
-            float s1 = row16_sum(S(P(blk(4), blk(6)), P(blk(5), blk(7))));
-            float o1 = s1;
-            swap16(s1, o1);
-            s1 += o1;
-            o1 = s1;
-            swap32(s1, o1);
-            s1 += o1;
-            s0 += s1;                                                    // ((b0 + b1) + (b2 + b3)) + ((b4 + b5) + (b6 + b7))
-        }
+        const float s0 = pair_token_sum<NCB>(run);
         if (lane == 0) *dst = s0;
     }
 }

@@ -400,7 +400,13 @@ class ShardedTokenIndex:
     Storage: the float16 token matrix (256 B per token), or after `compress` / from `build_compressed` the residual code of
     include/fusion_hip.h 'Residual-compressed token rows' (the centroid id of the candidate stage + 2 or 4 bits per dimension: 36 or 68 B
     per token).  Decompression is a fixed function of the stored bytes, and fz_maxsim_pairs_residual_f16 scores a compressed shard with the
-    bits ops.maxsim_pairs gives over the decompressed matrix: everything above holds for either storage, with D = the decompressed rows."""
+    bits ops.maxsim_pairs gives over the decompressed matrix: everything above holds for either storage, with D = the decompressed rows.
+    A third storage needs no training at all: after `quantize` / from `build_e4m3` the rows are OCP e4m3 bytes (ops.quantize_e4m3: a fixed
+    function of the float16 token, 128 B per token, no centroid table, no buckets).  fz_maxsim_pairs_e4m3 scores such a shard; the queries
+    are quantised per call at the class's q_exp, and every score is the exact MaxSim of the DEQUANTISED pair, the bits ops.maxsim_e4m3
+    gives it (`dequantized` returns the rows).  The shards still combine by one all_reduce(MAX); every rank must use the same exponents
+    (scale_exp of the documents, q_exp of the queries), or the shards' scores are not on one scale.  One storage decides the score:
+    a shard is either compressed or quantised, never both."""
 
     centroids = None        # [K, dim] float16, the same table on every rank (build_centroids)
     candidates = None       # the ShardedCentroidIndex of this shard
@@ -409,6 +415,9 @@ class ShardedTokenIndex:
     cutoffs = None          # [2^nbits - 1] float32, the same on every rank
     weights = None          # [2^nbits] float16, the same on every rank
     nbits = None
+    tok8 = None             # [sumL, 128] uint8: the e4m3 rows (quantize / build_e4m3)
+    d_exp = None            # their quantiser exponent
+    q_exp = 8               # the exponent the queries are quantised with per call over an e4m3 shard (the same on every rank)
 
     def __init__(self, Dtok_local: torch.Tensor, Doff_local: torch.Tensor, id_base: int, group=None, max_doc_len: int = 512):
         self.Dtok, self.Doff, self.id_base, self.group, self.max_doc_len = Dtok_local, Doff_local, int(id_base), group, int(max_doc_len)
@@ -432,6 +441,8 @@ class ShardedTokenIndex:
             raise ValueError("ShardedTokenIndex.compress: no centroid index (call build_centroids first)")
         if (cutoffs is None) != (weights is None):
             raise ValueError("ShardedTokenIndex.compress: give both cutoffs and weights, or neither")
+        if self.tok8 is not None:
+            raise ValueError("ShardedTokenIndex.compress: the shard is quantised to e4m3 (one storage decides the score)")
         if self.Dtok is None:
             raise ValueError("ShardedTokenIndex.compress: the token matrix is gone (already compressed)")
         nbits = ops._residual_nbits("ShardedTokenIndex.compress", nbits)
@@ -485,12 +496,72 @@ class ShardedTokenIndex:
             raise ValueError("ShardedTokenIndex.decompressed: the shard is not compressed")
         return ops.residual_decompress(self.packed, self.codes, self.centroids, self.weights, row_lo, row_hi)
 
+    def quantize(self, scale_exp: int = 8, keep_tokens: bool = False):
+        """Replace the float16 token matrix by its e4m3 bytes (ops.quantize_e4m3 at 2^scale_exp: 128 B per token, nothing trained) and drop
+        Dtok (None) unless keep_tokens.  From here on every score is the exact MaxSim of the DEQUANTISED queries and rows (`dequantized`;
+        ops.maxsim_e4m3's bits), the same for any number of shards as long as every rank uses the same scale_exp and q_exp.  A centroid
+        index built before (build_centroids) stays: `search` draws its candidates as before and scores them over the e4m3 rows."""
+        if self.packed is not None:
+            raise ValueError("ShardedTokenIndex.quantize: the shard is residual-compressed (one storage decides the score)")
+        if self.tok8 is not None:
+            raise ValueError("ShardedTokenIndex.quantize: the shard is already quantised")
+        if self.Dtok is None:
+            raise ValueError("ShardedTokenIndex.quantize: the token matrix is gone")
+        scale_exp = ops._e4m3_exp(scale_exp, "ShardedTokenIndex.quantize")
+        self.tok8, self.d_exp = ops.quantize_e4m3(self.Dtok, scale_exp), scale_exp
+        if not keep_tokens:
+            self.Dtok = None
+        return self
+
+    @classmethod
+    def build_e4m3(cls, blocks, Doff: torch.Tensor, id_base: int, *, scale_exp: int = 8, C: torch.Tensor | None = None, group=None,
+                   max_doc_len: int = 512, device=None):
+        """An e4m3 shard from an ITERATOR of token-row blocks ([rows_i, 128] float16, in corpus order, together the Doff[N] rows of the shard;
+        as build_compressed takes its blocks): every block is moved to the device and quantised (ops.quantize_e4m3) into its rows of the
+        shard's [sumL, 128] uint8 array, then dropped -- the float16 matrix of the shard is never resident.  With C [K, 128] every block is
+        also assigned (ops.centroid_assign) and the codes and the candidate index are built, so `search` works.  The result equals
+        cls(...).build_centroids(C).quantize(scale_exp) of the whole matrix: the same bytes, codes and candidate index."""
+        scale_exp = ops._e4m3_exp(scale_exp, "ShardedTokenIndex.build_e4m3")
+        if device is None:
+            device = C.device if C is not None and C.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        if C is not None:
+            C = C.to(device=device)
+        Doff = Doff.to(device)
+        sumL = int(Doff[-1]) if Doff.numel() else 0
+        tok8 = torch.empty((sumL, 128), dtype=torch.uint8, device=device)
+        codes = None if C is None else torch.empty(sumL, dtype=torch.int32, device=device)
+        at = 0
+        for blk in blocks:
+            blk = blk.to(device=device, dtype=torch.float16).contiguous()
+            n = blk.shape[0]
+            if at + n > sumL:
+                raise ValueError(f"ShardedTokenIndex.build_e4m3: the blocks hold more than Doff[N] = {sumL} token rows")
+            if n:
+                tok8[at: at + n] = ops.quantize_e4m3(blk, scale_exp)
+                if C is not None:
+                    codes[at: at + n] = ops.centroid_assign(blk, C)
+            at += n
+        if at != sumL:
+            raise ValueError(f"ShardedTokenIndex.build_e4m3: the blocks hold {at} token rows, Doff[N] = {sumL}")
+        self = cls(None, Doff, id_base, group=group, max_doc_len=max_doc_len)
+        if C is not None:
+            self.build_centroids(C, codes=codes)
+        self.tok8, self.d_exp = tok8, scale_exp
+        return self
+
+    def dequantized(self, row_lo: int = 0, row_hi: int | None = None) -> torch.Tensor:
+        """Rows [row_lo, row_hi) of the matrix a quantised shard scores against ([rows, 128] float32; ops.dequantize_e4m3)."""
+        if self.tok8 is None:
+            raise ValueError("ShardedTokenIndex.dequantized: the shard is not quantised")
+        return ops.dequantize_e4m3(self.tok8[row_lo: row_hi], self.d_exp)
+
     def memory_bytes(self) -> dict:
-        """Resident bytes by part: the float16 tokens, the codes, the packed residuals, the candidate index (lists + slice table), and their
-        total.  The centroid and bucket tables are shared by every shard and not counted."""
+        """Resident bytes by part: the token matrix of whatever type (float16 rows, e4m3 rows, or both after quantize(keep_tokens=True)),
+        the codes, the packed residuals, the candidate index (lists + slice table), and their total.  The centroid and bucket tables are
+        shared by every shard and not counted."""
         size = lambda t: 0 if t is None else t.numel() * t.element_size()      # noqa: E731
         ix = None if self.candidates is None else self.candidates.index
-        out = dict(tokens=size(self.Dtok), codes=size(self.codes), packed=size(self.packed),
+        out = dict(tokens=size(self.Dtok) + size(self.tok8), codes=size(self.codes), packed=size(self.packed),
                    candidates=0 if ix is None else size(ix.coff) + size(ix.cdoc) + size(ix.slice_off))
         out["total"] = sum(out.values())
         return out
@@ -537,10 +608,14 @@ class ShardedTokenIndex:
 
     def local_scores(self, Qtok: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
         """[Q, k] float32: exact MaxSim of query q and candidate cand_ids[q, r]; -inf for a slot this shard does not own (r >= cand_len[q],
-        a negative id, a document of another shard).  A compressed shard scores its decompressed rows (also when compress kept the tokens)."""
+        a negative id, a document of another shard).  A compressed shard scores its decompressed rows (also when compress kept the tokens);
+        a quantised shard scores its dequantised rows against the queries quantised at q_exp (also when quantize kept the tokens)."""
         if self.packed is not None:
             return ops.maxsim_pairs_residual(Qtok, self.packed, self.codes, self.centroids, self.weights, self.Doff, cand_ids, cand_len,
                                              id_base=self.id_base, max_doc_len=self.max_doc_len)
+        if self.tok8 is not None:
+            return ops.maxsim_pairs_e4m3(ops.quantize_e4m3(Qtok, self.q_exp), self.tok8, self.Doff, cand_ids, cand_len, q_exp=self.q_exp,
+                                         d_exp=self.d_exp, id_base=self.id_base, max_doc_len=self.max_doc_len)
         return ops.maxsim_pairs(Qtok, self.Dtok, self.Doff, cand_ids, cand_len, id_base=self.id_base, max_doc_len=self.max_doc_len)
 
     def pair_scores(self, Qtok: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:

@@ -389,6 +389,32 @@ def maxsim_pairs(Qtok: torch.Tensor, Dtok: torch.Tensor, Doff: torch.Tensor, can
     return out
 
 
+def maxsim_pairs_e4m3(Q8: torch.Tensor, D8: torch.Tensor, Doff: torch.Tensor, cand: torch.Tensor, cand_len: torch.Tensor | None = None, *,
+                      q_exp: int = 8, d_exp: int = 8, id_base: int = 0, max_doc_len: int = 512, out: torch.Tensor | None = None) -> torch.Tensor:
+    """maxsim_pairs over e4m3 token bytes (fz_maxsim_pairs_e4m3): out[q, r] = the score ops.maxsim_e4m3 gives query q and document
+    cand[q, r] - id_base, bit for bit -- the exact MaxSim of the dequantised tokens -- with no [Q, N] plane.  Q8 [Q, Lq, 128] and D8
+    [sumL, 128] uint8 (or torch.float8_e4m3fn) as quantize_e4m3 wrote them with q_exp and d_exp; cand, cand_len, id_base, max_doc_len, out
+    and the -inf / 0 slots as in maxsim_pairs (rows of cand may be strided, `out` may be a view of a wider plane).  No host
+    synchronisation."""
+    what = "maxsim_pairs_e4m3"
+    Q8 = _e4m3_bytes(Q8, f"{what}(Q8)")
+    D8 = _e4m3_bytes(D8, f"{what}(D8)")
+    _dev(Doff, torch.int64, f"{what}(Doff)")
+    q_exp, d_exp = _e4m3_exp(q_exp, f"{what}(q_exp)"), _e4m3_exp(d_exp, f"{what}(d_exp)")
+    _need(Q8.dim() == 3, f"{what}: Q8 must be [Q, Lq, dim]")
+    Q8, D8, Doff = Q8.contiguous(), D8.contiguous(), Doff.contiguous()
+    Q, Lq, dim = Q8.shape
+    N = Doff.numel() - 1
+    _need(Doff.dim() == 1 and N >= 0, f"{what}: Doff must hold N + 1 offsets")
+    _need(D8.dim() == 2 and D8.shape[1] == dim, f"{what}: D8 must be [sumL, {dim}]")
+    cand_len, out, k = _pairs_args(what, Q, Q8.device, cand, cand_len, out)
+    _need(int(max_doc_len) >= 1, f"{what}: max_doc_len must be at least 1")
+    check(_lib.lib().fz_maxsim_pairs_e4m3(_ptr(Q8), _ptr(D8), _ptr(Doff), int(D8.shape[0]), int(max_doc_len), Q, Lq, N, dim, q_exp + d_exp,
+                                          _ptr(cand), _ld(cand), _ptr(cand_len), k, int(id_base), _ptr(out), _ld(out), _stream(Q8)),
+          "fz_maxsim_pairs_e4m3")
+    return out
+
+
 # ---------------------------------------------------------------------------------------
 # K5a / K6 sort
 # ---------------------------------------------------------------------------------------

@@ -187,7 +187,9 @@ class Ranker:
         encoded corpus), `candidates` a planes.RankedTopk or a [Q, k] int64 tensor of global document ids (another system's lists, or
         their union).  The queries are encoded with the ColBERT `encoder` and every candidate gets its exact MaxSim score -- the bits
         multi_vector_search's plane holds for that pair -- with no plane over the corpus.  -> planes.RankedTopk in descending score order
-        (ties keep candidate order), cut to return_topk: what Aggregator.fuse_topk takes next to the dense, sparse and BM25 lists."""
+        (ties keep candidate order), cut to return_topk: what Aggregator.fuse_topk takes next to the dense, sparse and BM25 lists.
+        Works unchanged on a residual-compressed or an e4m3-quantised index (ShardedTokenIndex.compress / quantize): the scores are then
+        the exact MaxSim over the decompressed rows, or over the dequantised queries and rows (ops.maxsim_e4m3's bits)."""
         Qtok = encoder.encode_queries(queries, batch_size=64)
         return index.rerank(Qtok, candidates, k=return_topk)
 
@@ -197,7 +199,9 @@ class Ranker:
         centroids, then scores them exactly): `index` is a fusion_amd.distributed.ShardedTokenIndex with a centroid index
         (build_centroids).  The queries are encoded with the ColBERT `encoder` and `index.search` finds each one's candidates and scores
         them exactly -> planes.RankedTopk, what Aggregator.fuse_topk takes next to the dense, sparse and BM25 lists.  The candidate set is
-        approximate (nprobe, ncand: ShardedTokenIndex.search_defaults), every returned score is the exact MaxSim of its pair."""
+        approximate (nprobe, ncand: ShardedTokenIndex.search_defaults), every returned score is the exact MaxSim of its pair.  Works
+        unchanged on an e4m3-quantised index (build_centroids, then quantize; or build_e4m3 with C): the probes still use the float16
+        queries against the float16 centroids, the scores are the exact MaxSim of the dequantised pair."""
         Qtok = encoder.encode_queries(queries, batch_size=64)
         return index.search(Qtok, k=return_topk, nprobe=nprobe, ncand=ncand)
 

@@ -147,6 +147,23 @@ int fz_maxsim_e4m3(const void* Qtok8, const void* Dtok8, const int64_t* Doff, in
 int fz_maxsim_pairs_f16(const void* Qtok, const void* Dtok, const int64_t* Doff, int64_t sumL, int max_doc_len, int Q, int Lq, int N,
                         int dim, const int64_t* cand, int ldc, const int32_t* cand_len, int k, int64_t id_base, float* scores,
                         int lds, void* stream);
+/* The corpus-scale form over e4m3 token storage (csrc/rerank8.hip): fz_maxsim_pairs_f16's slots over fz_maxsim_e4m3's bytes, 128 B per
+ * token and nothing trained.  scores[q][r] = 2^-descale_exp * sum_{i<Lq} max_t <Qtok8[q][i], Dtok8[t]> over the DEQUANTISED bytes of
+ * query q and document cand[q][r] - id_base: for every slot whose document is in range, fz_maxsim_e4m3's scores[q][cand[q][r] - id_base]
+ * bit for bit on any input (the same one 16x16x128 block-scaled MFMA per 16 x 16 dot products with both hardware scales at 2^0, the same
+ * fmaxf maximum from -inf, the same summation tree, the same single exact multiply of the finished sum).  Qtok8 [Q][Lq][128] and Dtok8
+ * [sumL][128] are the bytes fz_quantize_e4m3_f16 writes; descale_exp is normally the sum of the two quantiser exponents.
+ * Slots as in fz_maxsim_pairs_f16: -inf when r >= cand_len[q], when the id is negative or outside [id_base, id_base + N); 0 for an
+ * empty document; duplicates scored independently; columns k .. lds-1 untouched.  A row past the document's end, past max_doc_len or
+ * past row sumL - 1 is never read.
+ * Argument checks in fz_maxsim_pairs_f16's classes and order: negative sizes, Lq <= 0, ldc < k, lds < k, a null pointer where a
+ * non-empty tensor is needed (Dtok8 with sumL != 0 included) or |descale_exp| > 32 -> FZ_ERR_ARG; then dim != 128, Lq outside
+ * {32, 64, 128}, Qtok8 or Dtok8 not 16-byte aligned -> FZ_ERR_UNSUPPORTED; then Q == 0 or k == 0 -> FZ_OK with nothing launched; then
+ * sumL < 0 or max_doc_len <= 0 -> FZ_ERR_ARG and max_doc_len > 16384 -> FZ_ERR_UNSUPPORTED.  Every refusal comes before the first HIP
+ * call.  No workspace. */
+int fz_maxsim_pairs_e4m3(const void* Qtok8, const void* Dtok8, const int64_t* Doff, int64_t sumL, int max_doc_len, int Q, int Lq, int N,
+                         int dim, int descale_exp, const int64_t* cand, int ldc, const int32_t* cand_len, int k, int64_t id_base,
+                         float* scores, int lds, void* stream);
 
 /* ---- K5a/K6: stable descending row sort ---------------------------------------------- */
 /* Python sorted(..., reverse=True) is stable (bm25.py:104, hybrid.py:306).  For each row:
