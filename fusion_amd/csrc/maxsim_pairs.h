@@ -1,7 +1,7 @@
 // maxsim_pairs.h -- exact ColBERT MaxSim of every query against ITS OWN candidate list (the corpus-scale rerank stage): the slot walk
 // of rerank.hip (float16 token rows) and rerank_residual.hip (the 2-/4-bit residual-compressed index), stated once.
 //
-// scores[q][r] = s(q, cand[q][r] - id_base) with s as in maxsim.hip, bit for bit: the same v_mfma_f32_16x16x32_f16 mapping (A = 16
+// scores[q][r] = s(q, cand[q][r] - id_base) with s as in maxsim.hip (the walk of maxsim_tiles.h), bit for bit: the same v_mfma_f32_16x16x32_f16 mapping (A = 16
 // document tokens x 32 dims, B = 32 dims x 16 query tokens, k-steps 0..3 from a zero accumulator), the same fmaxf maximum from -inf
 // and the same sum (row16_sum per 16-token column block, then the pair tree (b0+b1)+(b2+b3) ...), so a system's all-pairs plane and
 // its candidate lists are interchangeable -- and so are the two storages, which differ in nothing but how a row block's A fragments
@@ -92,7 +92,7 @@ __device__ __forceinline__ int64_t readlane64(int64_t v, int i) {
 }
 
 // End of a document.  run[b]: this lane's partial maximum of column block b (its query token: lane & 15; its rows: 4 (lane >> 4) ..).
-// The maximum over the four 16-lane rows, then the sum over the query tokens, in maxsim.hip's order: P / S transpose the column blocks'
+// The maximum over the four 16-lane rows, then the sum over the query tokens, in maxsim_tiles.h's order: P / S transpose the column blocks'
 // partial maxima onto the rows, row16_sum adds 16 tokens, two swap steps add the blocks in pairs.  Lane 0 holds the score.
 template <int NCB>
 __device__ __forceinline__ float pair_token_sum(const float (&run)[NCB]) {
@@ -154,7 +154,7 @@ __device__ __forceinline__ void maxsim_pairs_walk(const PairSlots& a, const Rows
     for (int i = 0; i < nmine; ++i) {
         const int len = __builtin_amdgcn_readlane(my_len, i);
         float* const dst = out + MP_WAVES * i;
-        if (len <= 0) {   // absent slot / empty document (sum of an empty max := 0, as in maxsim.hip)
+        if (len <= 0) {   // absent slot / empty document (sum of an empty max := 0, as in maxsim_tiles.h)
             if (lane == 0) *dst = len < 0 ? -INFINITY : 0.f;
             continue;
         }

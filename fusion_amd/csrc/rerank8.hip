@@ -2,8 +2,8 @@
 //
 //     scores[q][r] = 2^-descale_exp * sum_i max_{t < min(len_d, max_doc_len)} <Q8[q, i], D8[t]>,   d = cand[q][r] - id_base,
 // bit for bit what fz_maxsim_e4m3 (maxsim8.hip) gives that pair: the same ONE v_mfma_scale_f32_16x16x128_f8f6f4 per 16 x 16 block of
-// dot products (both hardware scales E8M0 127, C = 0), the same fmaxf maximum from -inf, the same sum (row16_sum per column block, then
-// the pair tree) and the same single multiply by the power of two on the finished sum.
+// dot products (both hardware scales E8M0 127, C = 0), the same fmaxf maximum from -inf, the same sum (maxsim_tiles.h's: row16_sum per column block,
+// then the pair tree) and the same single multiply by the power of two on the finished sum.
 //
 // The kernel is the slot walk of maxsim_pairs.h -- read its header first: one workgroup = 4 waves = one (query, 128 slots), lane i
 // resolves slot i once per wave (pair_slot_resolve), v_readlane brings it back into SGPRs, the query's B fragments stay resident, rows
@@ -82,7 +82,7 @@ void maxsim_pairs8_kernel(Pairs8Args k) {
     for (int i = 0; i < nmine; ++i) {
         const int len = __builtin_amdgcn_readlane(my_len, i);
         float* const dst = out + MP_WAVES * i;
-        if (len <= 0) {   // absent slot / empty document (sum of an empty max := 0, as in maxsim8.hip)
+        if (len <= 0) {   // absent slot / empty document (sum of an empty max := 0, as in maxsim_tiles.h)
             if (lane == 0) *dst = len < 0 ? -INFINITY : 0.f;
             continue;
         }

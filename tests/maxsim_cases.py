@@ -10,7 +10,7 @@ magnitude: 128 * (1024 + 127) < 2^18 with 2^-4 granularity: 22 significant bits,
 alternate with guard documents made of poison only (odd positions); rows before Doff[0], rows after Doff[N] and the tail of a document
 past max_doc_len are poison too.  Both kinds of document are compared.
 
-The case table restates the launcher's arithmetic of csrc/maxsim.hip in plain Python (launch_plan) and names, for every case, the
+The case table restates the launcher's arithmetic of csrc/maxsim_tiles.h in plain Python (launch_plan) and names, for every case, the
 branches of the kernel it is there for (branches_of); BRANCHES lists every branch that must be landed on."""
 import dataclasses
 import zlib
@@ -21,7 +21,7 @@ DIM = 128
 POISON = 1024.0
 LQS = (32, 64, 128)
 
-# csrc/maxsim.hip
+# csrc/maxsim_tiles.h (MT_*); the blocks per wave: csrc/maxsim.hip and csrc/maxsim8.hip
 MS_WAVES, MS_BLOCKS_PER_WAVE, MS_DOCS_PER_WG, MS_TABLE = 8, 4, 32, 512
 
 

@@ -12,8 +12,8 @@ query token carries 1 and every clean document row 0: a clean document scores at
 (a masked row, a truncated tail, a neighbour, a clamped row) adds 8 * 448 = 3,584.  Largest magnitude: 128 * (3,584 + 480) < 2^19.
 Guard documents, poisoned rows before Doff[0] and after Doff[N] and poisoned tails past max_doc_len follow maxsim_cases.grid_corpus.
 
-The case table.  csrc/maxsim8.hip keeps the float16 kernel's launch plan (8 waves, 4 query blocks per wave, 32 documents per workgroup,
-32-row tiles, groups of 4 in a ring of 8), so the shapes are maxsim_cases.CASES and maxsim_cases.launch_plan / branches_of / BRANCHES
+The case table.  csrc/maxsim8.hip and the float16 kernel run one tile walk, csrc/maxsim_tiles.h, and so one launch plan (8 waves, 4 query
+blocks per wave, 32 documents per workgroup, 32-row tiles, groups of 4 in a ring of 8), so the shapes are maxsim_cases.CASES and maxsim_cases.launch_plan / branches_of / BRANCHES
 say which branch a case lands on; REQUIRED spells out what the table must reach at the least."""
 import functools
 
@@ -33,7 +33,7 @@ maxsim_ref = M.maxsim_ref
 maxsim_fmax_ref = M.maxsim_fmax_ref
 exact_f32 = M.exact_f32
 
-# csrc/maxsim8.hip: the float16 kernel's plan
+# csrc/maxsim8.hip walks csrc/maxsim_tiles.h as the float16 kernel does: one plan
 assert (M.MS_WAVES, M.MS_BLOCKS_PER_WAVE, M.MS_DOCS_PER_WG, M.MS_TABLE) == (8, 4, 32, 512)
 RING_TOKENS = 8 * 32
 

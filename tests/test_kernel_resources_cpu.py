@@ -28,6 +28,7 @@ NO_SPILL = {
     "fuse_rank_kernel<true>": "rrf / bcf plane (top-k selection, long rows)",
     "bm25_kernel": "bm25_score",
     "maxsim_kernel": "ColBERT MaxSim",
+    "maxsim8_kernel": "ColBERT MaxSim over e4m3 tokens: the same tile walk",
     "sparse_dot_kernel": "SPLADE inverted-index scoring",
     "lexical_range_kernel": "BM25 / TF-IDF over a document range: plane and streaming top-k filter",
     "centroid_scores_kernel": "ColBERT candidate stage: plane and streaming top-k filter",
@@ -109,7 +110,7 @@ def test_allow_listed_spills_stay_within_their_measured_bounds(resources, name):
 
 def test_the_dot_product_and_encoder_kernels_do_not_spill(resources):
     for k, r in resources.items():
-        if r["file"] in ("score", "encoder", "maxsim", "bm25", "bm25_stream", "sparse", "centroid", "util"):
+        if r["file"] in ("score", "encoder", "maxsim", "maxsim8", "bm25", "bm25_stream", "sparse", "centroid", "util"):
             assert r["vgpr_spill"] == 0, f"{k}: {r['vgpr_spill']} spilled VGPRs"
 
 
