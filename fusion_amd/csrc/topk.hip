@@ -331,26 +331,49 @@ extern "C" int fz_select_topk_f(const void* fused, int key_bits, const int32_t* 
 static const int TOPK_CHUNK = SORT_ROW_F64;   // the width both key widths share (the chunk sorts here have float32 keys: any width <= SORT_ROW_F32 would do)
 extern "C" int fz_topk_max_k(void) { return 8192; }
 
-static void topk_plan(int n, int k, int* levels_out, size_t* elems_out) {
-    // level l: cur columns -> chunks of TOPK_CHUNK -> kk = min(k, TOPK_CHUNK) survivors per chunk
-    int cur = n, levels = 0;
-    size_t elems = 0;
-    while (cur > SORT_ROW_F32) {
-        int nch = (cur + TOPK_CHUNK - 1) / TOPK_CHUNK;
-        int kk = k < TOPK_CHUNK ? k : TOPK_CHUNK;
-        cur = nch * kk;
-        elems += (size_t)cur;
-        ++levels;
+// The chunk-sort-truncate levels of fz_topk_rows_f32, host arithmetic only: the entry runs the plan it gets from here and
+// fz_topk_rows_plan shows it on a machine without a GPU (tests/topk_cases.py lands every branch below through it).
+constexpr int TOPK_MAX_LEVELS = 12;   // k <= 8192: a level shrinks its row 3.5 times, 2^31 columns take 9
+struct TopkLevel { int width, chunks, kk, fill; };
+struct TopkPlan {
+    int levels, pad, last;            // pad: n < k, the tail of the outputs is (-inf, -1); last: the width the finishing sort reads
+    size_t elems;                     // candidates kept over all levels, per row
+    TopkLevel lv[TOPK_MAX_LEVELS];
+};
+static TopkPlan topk_plan(int n, int k) {
+    // level l: width columns -> chunks of TOPK_CHUNK -> kk = min(k, TOPK_CHUNK) survivors per chunk
+    TopkPlan p{};
+    p.pad = n < k ? 1 : 0;
+    int cur = n;
+    while (cur > SORT_ROW_F32 && p.levels < TOPK_MAX_LEVELS) {
+        TopkLevel& l = p.lv[p.levels++];
+        l.width = cur;
+        l.chunks = (cur + TOPK_CHUNK - 1) / TOPK_CHUNK;
+        l.kk = k < TOPK_CHUNK ? k : TOPK_CHUNK;
+        l.fill = cur - (l.chunks - 1) * TOPK_CHUNK < l.kk ? 1 : 0;   // the short last chunk leaves a tail of its kk slots unwritten
+        cur = l.chunks * l.kk;
+        p.elems += (size_t)cur;
     }
-    *levels_out = levels;
-    *elems_out = elems;
+    p.last = cur;
+    return p;
+}
+
+// out[FZ_TOPK_ROWS_PLAN_FIELDS = 3 + 4 * 12]: levels, pad, last, then (width, chunks, kk, fill) of every level
+extern "C" int fz_topk_rows_plan(int n, int k, int32_t* out) {
+    if (n < 0 || k <= 0 || !out) return FZ_ERR_ARG;
+    if (k > fz_topk_max_k()) return FZ_ERR_UNSUPPORTED;
+    const TopkPlan p = topk_plan(n, k);
+    if (p.last > SORT_ROW_F32) return FZ_ERR_UNSUPPORTED;
+    out[0] = p.levels; out[1] = p.pad; out[2] = p.last;
+    for (int l = 0; l < TOPK_MAX_LEVELS; ++l) {
+        out[3 + 4 * l] = p.lv[l].width; out[4 + 4 * l] = p.lv[l].chunks; out[5 + 4 * l] = p.lv[l].kk; out[6 + 4 * l] = p.lv[l].fill;
+    }
+    return FZ_OK;
 }
 
 extern "C" size_t fz_topk_workspace_bytes(int rows, int n, int k) {
     if (rows <= 0 || n <= 0 || k <= 0) return 0;
-    int levels; size_t elems;
-    topk_plan(n, k, &levels, &elems);
-    return (size_t)rows * elems * 8 + 256;  // fp32 score + int32 column per surviving candidate
+    return (size_t)rows * topk_plan(n, k).elems * 8 + 256;  // fp32 score + int32 column per surviving candidate
 }
 
 extern "C" int fz_topk_rows_f32(const float* scores, int rows, int n, int ld, int k, int64_t id_base, float* out_scores,
@@ -359,47 +382,46 @@ extern "C" int fz_topk_rows_f32(const float* scores, int rows, int n, int ld, in
     if (k > fz_topk_max_k()) return FZ_ERR_UNSUPPORTED;
     if (rows == 0) return FZ_OK;
     if (!out_scores || !out_ids || (!scores && n > 0)) return FZ_ERR_ARG;
+    const TopkPlan p = topk_plan(n, k);
+    if (p.last > SORT_ROW_F32) return FZ_ERR_UNSUPPORTED;
+    if (n > 0 && workspace_bytes < fz_topk_workspace_bytes(rows, n, k)) return FZ_ERR_WORKSPACE;
+    if (n > SORT_ROW_F32 && !workspace) return FZ_ERR_WORKSPACE;
     hipStream_t st = as_stream(stream);
     const int have = n < k ? n : k;
-    if (have < k) {
+    if (p.pad) {
         dim3 g((unsigned)((k - have + 255) / 256), (unsigned)rows);
         topk_pad_kernel<<<g, 256, 0, st>>>(out_scores, out_ids, rows, k, have);
         FZ_LAUNCH_CHECK();
     }
     if (n == 0) return FZ_OK;
-    if (workspace_bytes < fz_topk_workspace_bytes(rows, n, k)) return FZ_ERR_WORKSPACE;
-    if (n > SORT_ROW_F32 && !workspace) return FZ_ERR_WORKSPACE;
 
     const float* cur_keys = scores;
     const int32_t* cur_cols = nullptr;
     long cur_stride = ld;
-    int cur = n;
     char* ws = reinterpret_cast<char*>(workspace);
-    while (cur > SORT_ROW_F32) {
-        const int per = TOPK_CHUNK;
-        int nch = (cur + per - 1) / per;
-        int kk = k < per ? k : per;
-        int next = nch * kk;
+    for (int l = 0; l < p.levels; ++l) {
+        const TopkLevel& lv = p.lv[l];
+        const int next = lv.chunks * lv.kk;
         float* nk = reinterpret_cast<float*>(ws); ws += (size_t)rows * next * 4;
         int32_t* nc = reinterpret_cast<int32_t*>(ws); ws += (size_t)rows * next * 4;
-        if (cur - (nch - 1) * per < kk) {
+        if (lv.fill) {
             // the short last chunk leaves a tail unwritten: make it (-inf, col -1) so it cannot win
             fill_absent_kernel<float><<<1024, 256, 0, st>>>(nk, nc, (size_t)rows * next);
             FZ_LAUNCH_CHECK();
         }
         SortArgs a{};
-        a.keys = cur_keys; a.n_total = cur; a.key_row_stride = cur_stride; a.seg_len = cur; a.chunks = nch; a.chunk_len = per;
-        a.order = nc; a.sorted_keys = nk; a.out_row_stride = next; a.out_chunk_stride = kk; a.out_limit = kk;
+        a.keys = cur_keys; a.n_total = lv.width; a.key_row_stride = cur_stride; a.seg_len = lv.width; a.chunks = lv.chunks; a.chunk_len = TOPK_CHUNK;
+        a.order = nc; a.sorted_keys = nk; a.out_row_stride = next; a.out_chunk_stride = lv.kk; a.out_limit = lv.kk;
         a.colmap = cur_cols; a.colmap_row_stride = cur_stride;
-        int rc = launch_sort(a, 1, rows * nch, per, st);
+        int rc = launch_sort(a, 1, rows * lv.chunks, TOPK_CHUNK, st);
         if (rc != FZ_OK) return rc;
-        cur_keys = nk; cur_cols = nc; cur_stride = next; cur = next;
+        cur_keys = nk; cur_cols = nc; cur_stride = next;
     }
     SortArgs a{};
-    a.keys = cur_keys; a.n_total = cur; a.key_row_stride = cur_stride; a.seg_len = cur; a.chunks = 1; a.chunk_len = cur;
+    a.keys = cur_keys; a.n_total = p.last; a.key_row_stride = cur_stride; a.seg_len = p.last; a.chunks = 1; a.chunk_len = p.last;
     a.sorted_keys = out_scores; a.out_ids = out_ids; a.id_base = id_base; a.out_row_stride = k; a.out_limit = have;
     a.colmap = cur_cols; a.colmap_row_stride = cur_stride;
-    return launch_sort(a, 1, rows, cur, st);
+    return launch_sort(a, 1, rows, p.last, st);
 }
 
 extern "C" size_t fz_topk_update_workspace_bytes(int rows, int k, int cap) {
@@ -490,6 +512,11 @@ __global__ __launch_bounds__(256) void topk_tiefix_kernel(const float* tmp_s, co
     if (bad) atomicExch(overflow, 1);
 }
 
+// The largest k fz_topk_fold_f32 takes: the unordered form holds the first k + TIE_MARGIN entries of a row in LDS (12 bytes each, 60 KiB);
+// the ordered form is bound by k + cap <= one sort row alone.
+constexpr size_t TIE_LDS_MAX = 60 * 1024;
+extern "C" int fz_topk_fold_max_k(int unordered) { return unordered ? (int)(TIE_LDS_MAX / (8 + 4)) - TIE_MARGIN : SORT_ROW_F32 - 1; }
+
 extern "C" size_t fz_topk_fold_workspace_bytes(int rows, int k, int cap) {
     if (rows <= 0 || k <= 0 || cap <= 0) return 0;
     return fz_topk_update_workspace_bytes(rows, k, cap) + (size_t)rows * (k + TIE_MARGIN) * (4 + 8) + 256;
@@ -499,7 +526,7 @@ extern "C" int fz_topk_fold_f32(const float* run_scores, const int64_t* run_ids,
                                 int32_t* cand_len, int cap, int unordered, float* new_scores, int64_t* new_ids, float* tau_out, int32_t* overflow,
                                 void* workspace, size_t workspace_bytes, void* stream) {
     if (rows < 0 || k <= 0 || cap <= 0) return FZ_ERR_ARG;
-    if ((long)k + cap > SORT_ROW_F32) return FZ_ERR_UNSUPPORTED;
+    if ((long)k + cap > SORT_ROW_F32 || k > fz_topk_fold_max_k(unordered)) return FZ_ERR_UNSUPPORTED;   // (before any launch: a refusal leaves everything as it was)
     if (rows == 0) return FZ_OK;
     if (!run_scores || !run_ids || !cand_scores || !cand_ids || !cand_len || !new_scores || !new_ids || (unordered && !overflow)) return FZ_ERR_ARG;
     if (!workspace || workspace_bytes < fz_topk_fold_workspace_bytes(rows, k, cap)) return FZ_ERR_WORKSPACE;
@@ -517,8 +544,7 @@ extern "C" int fz_topk_fold_f32(const float* run_scores, const int64_t* run_ids,
     a.row_len = buf_len;
     if (int rc = launch_sort(a, 1, rows, k + cap, st)) return rc;
     if (unordered) {
-        const size_t lds = (size_t)lim * (8 + 4);
-        if (lds > 60 * 1024) return FZ_ERR_UNSUPPORTED;
+        const size_t lds = (size_t)lim * (8 + 4);                  // <= TIE_LDS_MAX: k <= fz_topk_fold_max_k(1)
         topk_tiefix_kernel<<<rows, 256, lds, st>>>(tmp_scores, tmp_ids, buf_len, k, lim, new_scores, new_ids, overflow);
         FZ_LAUNCH_CHECK();
     }

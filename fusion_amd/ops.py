@@ -10,6 +10,7 @@ starts on a 256-byte boundary (16-byte vector loads).
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
@@ -522,7 +523,8 @@ def select_topk(fused: torch.Tensor, pos: torch.Tensor | None, k: int, cap: int 
     fused lists main() actually reads (predictions(1000), hybrid.py:537).  fused [Q, N] float32 / float64 plane, pos [Q, N] int32 plane =
     first-insertion position of every column (< 0: in no list; None: the column index).  Returns (cols [Q, k] int32 -- -1 past a row's
     length --, scores [Q, k], lens [Q] int32), or None when a row has more than `cap` candidates (a long tie run at the k-th place) or
-    the row is longer than one workgroup holds: the caller then sorts in full."""
+    the row is longer than one workgroup holds: the caller then sorts in full.  cap (default: k + 1024 rounded up to 1024) is rounded up to
+    a multiple of 64."""
     _dev(fused, None, "select_topk(fused)")
     if fused.dtype not in (torch.float32, torch.float64):
         raise TypeError("select_topk(fused): float32 or float64 expected")
@@ -535,7 +537,9 @@ def select_topk(fused: torch.Tensor, pos: torch.Tensor | None, k: int, cap: int 
         _dev(pos, torch.int32, "select_topk(pos)")
         _same_shape([fused, pos], "select_topk")
         _need(Q <= 1 or _ld(pos) == _ld(fused), "select_topk: fused and pos must share the row stride")
-    cap = int(cap) if cap else round_up(k + 1024, 1024)
+    # the kernel numbers a row's candidates in rows of `cap` slots, so cap is a whole plane row: a given cap is rounded up to one (a narrower
+    # view hid the slots between cap and the row stride from the two sorts below: candidates lost, no flag)
+    cap = round_up(int(cap), _PAD) if cap else round_up(k + 1024, 1024)
     dev = fused.device
     cols = alloc_plane(Q, cap, torch.int32, dev)
     vals = alloc_plane(Q, cap, fused.dtype, dev)
@@ -1155,7 +1159,10 @@ def topk_rows(scores: torch.Tensor, k: int, id_base: int = 0):
 def topk_update(scores: torch.Tensor, id_base: int, run_scores: torch.Tensor, run_ids: torch.Tensor, cap: int = 7168,
                 overflow: torch.Tensor | None = None):
     """Merge one more chunk of scores into the running top-k (streaming threshold filter + small sort).
-    Returns (new_scores, new_ids, overflow_flag_tensor); the caller checks the flag once at the end of the search."""
+    Returns (new_scores, new_ids, overflow_flag_tensor); the caller checks the flag once at the end of the search.
+    Precondition (include/fusion_hip.h, fz_topk_update_f32): the running list is full (k real entries) or no score is -inf -- against a
+    short list's threshold of -inf a later score of exactly -inf is dropped and stays (-inf, -1) padding, where topk_rows of the whole
+    matrix lists its id."""
     _dev(scores, torch.float32, "topk_update(scores)")
     _dev(run_scores, torch.float32, "topk_update(run_scores)")
     _dev(run_ids, torch.int64, "topk_update(run_ids)")
@@ -1175,6 +1182,13 @@ def topk_update(scores: torch.Tensor, id_base: int, run_scores: torch.Tensor, ru
     check(lib.fz_topk_update_f32(_ptr(scores), rows, n, _ld(scores), int(id_base), _ptr(run_scores.contiguous()), _ptr(run_ids.contiguous()), k, cap,
                                  _ptr(ns), _ptr(ni), _ptr(overflow), _ptr(ws), wsb, _stream(scores)), "fz_topk_update_f32")
     return ns, ni, overflow
+
+
+@functools.lru_cache(maxsize=None)
+def fold_max_k(unordered: bool) -> int:
+    """The largest k fz_topk_fold_f32 takes (fz_topk_fold_max_k): 5,056 for candidates in arrival order, 35,839 for ordered ones.  A constant
+    of the library: asked once."""
+    return int(_lib.lib().fz_topk_fold_max_k(1 if unordered else 0))
 
 
 def stream_window(seen: int, k: int, cap: int) -> int:
@@ -1253,12 +1267,16 @@ class TopkStream:
     `windows_redone` counts them.  That needs what the window was fed with: feed_gemm's and feed_sparse's pieces are views of their
     inputs (kept: no copies); feed()'s score buffers are kept only on request (hold=True) -- otherwise, and without exact_on_overflow,
     the flag stays set and the caller redoes the search.  The feeds differ only in their _Source; the loop is _feed's.  The float64
-    ranking (TopkStream64) shares all of it, fold's overflow protocol included: a ranking is _alloc, _fold_candidates, plane_topk, _merge."""
+    ranking (TopkStream64) shares all of it, fold's overflow protocol included: a ranking is _alloc, _fold_candidates, plane_topk, _merge.
+    Precondition: the list the stream starts from is full (k real entries; the index classes start from a head of >= 8 k documents) or no
+    score is -inf -- a short list's threshold is -inf and the filter keeps !(s <= tau), so a later score of exactly -inf stays padding.
+    An unordered source (feed_gemm, feed_sparse) needs k <= fold_max_k(True) = 5,056: ValueError before the first filter launch."""
 
     dtype = torch.float32        # of the lists, the thresholds and the candidate scores
     _fold_writes_tau = True      # fz_topk_fold_f32 rewrites tau and clears cand_len itself
     _can_redo = True             # plane_topk is there for an overflowed window
     _ranking = {}                # what plane_topk takes besides (plane, k, base)
+    _fold_limits_k = True        # the fold is fz_topk_fold_f32: k <= fold_max_k(unordered)
 
     def __init__(self, run_scores: torch.Tensor, run_ids: torch.Tensor, seen: int, cap: int = 7168, exact_on_overflow: bool = True):
         what = type(self).__name__
@@ -1310,6 +1328,10 @@ class TopkStream:
 
     def _feed(self, source, lo: int, hi: int, mark=None):
         """The source's documents [lo, hi), cut at the fold windows (stream_pieces): one filter launch per piece, a fold where planned."""
+        unordered = self.unordered or source.unordered
+        if self._fold_limits_k and self.k > fold_max_k(unordered):     # (before anything is launched or latched: the fold would refuse this k)
+            raise ValueError(f"{type(self).__name__}: k = {self.k} exceeds what the fold of {'unordered' if unordered else 'ordered'} "
+                             f"candidates takes ({fold_max_k(unordered)})")
         self.unordered = self.unordered or source.unordered
         for lo, hi, fold in stream_pieces(lo, hi, self.seen, self.pending, self.k, self.cap, source.grain):
             source.filter(self, lo, hi)
@@ -1753,6 +1775,7 @@ class TopkStream64(TopkStream):
 
     dtype = torch.float64
     _fold_writes_tau = False     # the fold is torch ops and a row sort: the host rewrites tau and clears cand_len
+    _fold_limits_k = False       # ... and has no limit of its own beyond _alloc's k + cap
 
     def __init__(self, run_scores: torch.Tensor, run_ids: torch.Tensor, seen: int, cap: int = 7168, exact_on_overflow: bool = True,
                  top_positions=None):

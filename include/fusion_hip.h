@@ -367,11 +367,26 @@ int fz_topk_max_k(void);
 size_t fz_topk_workspace_bytes(int rows, int n, int k);
 int fz_topk_rows_f32(const float* scores, int rows, int n, int ld, int k, int64_t id_base, float* out_scores,
                      int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream);
+/* (ABI 20, additive) What fz_topk_rows_f32 does with a row of n columns at this k: the function the entry itself runs, host arithmetic
+ * only, no HIP call, no GPU needed (tests/topk_cases.py proves which branches a shape takes through it).  A row wider than one sort row
+ * (35,840) goes through chunk-sort-truncate levels: chunks of 28,672 columns each keep their kk = min(k, 28,672) best.
+ * out[FZ_TOPK_ROWS_PLAN_FIELDS]: levels | pad (n < k: the outputs end in (-inf, -1)) | the width the finishing sort reads | then per level
+ * l < FZ_TOPK_ROWS_PLAN_LEVELS: its input width, chunks, kk, fill (1: the last chunk holds fewer than kk keys and the level's output is
+ * pre-filled with (-inf, -1)); zeros past the last level.  n < 0, k <= 0 or out == NULL -> FZ_ERR_ARG, k > fz_topk_max_k() ->
+ * FZ_ERR_UNSUPPORTED, as the entry answers; nothing is written then. */
+#define FZ_TOPK_ROWS_PLAN_LEVELS 12
+#define FZ_TOPK_ROWS_PLAN_FIELDS 51
+int fz_topk_rows_plan(int n, int k, int32_t* out);
 /* streaming form of the same loop: merge one more chunk of scores into the running per-row top-k.  Only scores strictly
  * above a row's current k-th best can enter (chunks arrive in ascending id order, so ties lose), so the chunk is filtered
  * in one streaming pass and only the survivors (+ the running list) are sorted.  run_* [rows][k] -> new_* [rows][k]
  * (distinct buffers, sorted by score desc, id asc; (-inf,-1) padding).  *overflow (device int32, zeroed by the caller)
- * is set when a row had more than `cap` survivors: redo that chunk with fz_topk_rows_f32 + fz_topk_merge. */
+ * is set when a row had more than `cap` survivors: redo that chunk with fz_topk_rows_f32 + fz_topk_merge.
+ * PRECONDITION of the streamed forms (this entry, fz_topk_filter_append_f32 + fz_topk_fold_f32): the filter keeps !(score <= tau) with
+ * tau = the running list's k-th score, so while the running list is SHORT (fewer than k real entries: (-inf, -1) padding, tau = -inf) a
+ * score of exactly -inf in a later chunk is dropped, where fz_topk_rows_f32 of the whole matrix lists it, with its id, ahead of the padding.
+ * The streamed forms equal fz_topk_rows_f32 of the whole matrix when every running list is full (k real entries) OR no score is -inf;
+ * otherwise they differ exactly in that -inf documents are listed as padding.  The index classes start from a head of >= 8 k documents. */
 size_t fz_topk_update_workspace_bytes(int rows, int k, int cap);
 int fz_topk_update_f32(const float* scores, int rows, int n, int ld, int64_t id_base, const float* run_scores,
                        const int64_t* run_ids, int k, int cap, float* new_scores, int64_t* new_ids, int32_t* overflow,
@@ -384,7 +399,11 @@ int fz_topk_update_f32(const float* scores, int rows, int n, int ld, int64_t id_
  * call); *overflow becomes 1 if a row's list would exceed cap (the caller then redoes the search exactly).  k + cap <= 35840.
  * unordered != 0: the candidates are in no particular order (fz_dot_scores_filter_f32 appends them as its waves finish); the fold
  * then also puts every run of equal scores that reaches into the first k into ascending id order -- the same lists as from ordered
- * candidates -- and sets *overflow if such a run is longer than it looks at (64 entries past k, 512 in all). */
+ * candidates -- and sets *overflow if such a run is longer than it looks at (64 entries past k, 512 in all).
+ * (ABI 20, additive) fz_topk_fold_max_k(unordered): the largest k the fold takes -- 5,056 for the unordered form (k + 64 entries of 12 bytes
+ * in 60 KiB of LDS), 35,839 otherwise; beyond it, as for k + cap > 35840, fz_topk_fold_f32 answers FZ_ERR_UNSUPPORTED before its first
+ * launch: new_*, tau_out, cand_len and *overflow stay as they were. */
+int fz_topk_fold_max_k(int unordered);
 int fz_topk_filter_append_f32(const float* scores, int rows, int n, int ld, int64_t id_base, const float* tau, float* cand_scores,
                               int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow, void* stream);
 size_t fz_topk_fold_workspace_bytes(int rows, int k, int cap);
