@@ -1,6 +1,8 @@
-// bm25_stream.hip -- the lexical posting walk (csrc/bm25.hip) over a RANGE of documents, with slices.h's two epilogues: the float64
-// score plane of the range, or the streaming top-k's threshold filter in its place (no plane at all) -- what csrc/sparse.hip's
-// sparse_dot_kernel<FILTER> is to float32 SPLADE, for BM25 / AtireBM25 (posting-value table) and TF-IDF in float64.
+// bm25_stream.hip -- the lexical posting walk (csrc/bm25.hip) over a RANGE of documents, with slices.h's three epilogues: the float64
+// score plane of the range; the streaming top-k's threshold filter in its place (no plane at all) -- what csrc/sparse.hip's
+// sparse_dot_kernel<FILTER> is to float32 SPLADE, for BM25 / AtireBM25 (posting-value table) and TF-IDF in float64; or, per listed
+// ("gold") document, the count of the range's documents that the stable float64 ranking puts before it (BM25.tune's grid search: a gold's
+// rank is a COUNT; counts over disjoint ranges, chunks and shards add as integers).  One kernel, the epilogue its template parameter.
 //
 // Bits: per document the score is the chain of float64 adds, in QUERY-TERM order, that bm25_kernel<MODE> makes (query terms not
 // de-duplicated, id -1 adds nothing, BM25_TERMS terms resolved per batch; -ffp-contract=off) whatever the range or the grid: a range's
@@ -22,11 +24,16 @@ struct LexArgs {
     DocRange r;                                // the documents scored (NS: grains of the index)
     double* scores; int lds;                   // plane epilogue: [Q][lds], column j = document doc_lo + j
     FilterSink<double> f;                      // filter epilogue: no plane
+    CountSink c;                               // count epilogue: no plane, no list
 };
 
-// grid (slices of [doc_lo, doc_hi), Q): workgroup (x, q) scores global slice doc_lo / slice + x.  FILTER: the epilogue.
-template <int MODE, bool FILTER>
-__global__ __launch_bounds__(slice_threads<MODE>()) void lexical_range_kernel(LexArgs a) {
+// grid (slices of [doc_lo, doc_hi), Q): workgroup (x, q) scores global slice doc_lo / slice + x.  EPI: the epilogue (LEX_PLANE / LEX_FILTER /
+// LEX_COUNT).  Plane and filter ask for what the launch bounds give anyway (2 / 4 waves per SIMD at least); for the count, 8 waves per SIMD
+// is what the LDS allows (four workgroups of 8 waves / two of 16 per CU): without the attribute the epilogue's four group widths take 101
+// SGPRs, i.e. 7 waves and a workgroup per CU less -- with it 72, nothing spilled.
+template <int MODE, int EPI>
+__global__ __launch_bounds__(slice_threads<MODE>()) __attribute__((amdgpu_waves_per_eu(EPI == LEX_COUNT ? 8 : slice_threads<MODE>() / 256, 8)))
+void lexical_range_kernel(LexArgs a) {
     constexpr bool PVAL = MODE == BM25_PVAL;
     constexpr int SL = slice_grains<MODE>(), SLICE = slice_docs<MODE>();
     __shared__ __attribute__((aligned(16))) double acc[SLICE];            // the slice's accumulators: 28 / 56 KiB, static (with the term tables under 64 KiB)
@@ -88,72 +95,86 @@ __global__ __launch_bounds__(slice_threads<MODE>()) void lexical_range_kernel(Le
         }
     }
     __syncthreads();
-    if constexpr (FILTER) filter_candidates(acc, n, d0, q, a.f);
-    else store_plane(acc, n, a.scores, a.lds, q, d0 - a.r.doc_lo);
-}
-
-template <int MODE, bool FILTER>
-static int lx_launch(const LexArgs& a, int Q, hipStream_t st) {
-    lexical_range_kernel<MODE, FILTER><<<slice_grid(a.r, slice_docs<MODE>(), Q), slice_threads<MODE>(), 0, st>>>(a);
-    FZ_LAUNCH_CHECK();
-    return FZ_OK;
+    if constexpr (EPI == LEX_PLANE) store_plane(acc, n, a.scores, a.lds, q, d0 - a.r.doc_lo);
+    else if constexpr (EPI == LEX_FILTER) filter_candidates(acc, n, d0, q, a.f);
+    else count_beaters(acc, n, d0, q, a.c);
 }
 
 }  // namespace fz
 
 using namespace fz;
 
-// the scorer's own fields by name: ptf / pdoc and idf / pval are the same types
-static LexArgs lx_args(const int64_t* toff, const int32_t* pdoc, const int64_t* slice_off, const int64_t* qoff, const int32_t* qterms, int N, int doc_lo,
-                       int doc_hi) {
+// the index and the queries: what every range entry takes.  The scorer's own fields (ptf / pdoc and idf / pval are the same types) and the
+// epilogue's sink are set by name in the entry.
+static LexArgs lx_args(const int64_t* toff, const int32_t* pdoc, const int64_t* slice_off, const int64_t* qoff, const int32_t* qterms) {
     LexArgs a{};
     a.toff = toff; a.pdoc = pdoc; a.slice_off = slice_off; a.qoff = qoff; a.qterms = qterms;
-    a.r = doc_range(N, doc_lo, doc_hi, BM25_GRAIN);
     return a;
+}
+
+// the host side of the six range entries: sizes, the range and the epilogue's own size; "nothing to do"; the pointers; the launch
+template <int MODE, int EPI>
+static int lx_run(LexArgs a, int Q, int N, int doc_lo, int doc_hi, void* stream) {
+    constexpr bool PVAL = MODE == BM25_PVAL;
+    if (Q < 0 || !range_ok(N, doc_lo, doc_hi, slice_docs<MODE>())) return FZ_ERR_ARG;
+    if (EPI == LEX_PLANE ? a.lds < doc_hi - doc_lo : EPI == LEX_FILTER ? a.f.cap <= 0 : a.c.G < 1) return FZ_ERR_ARG;
+    if (Q == 0 || doc_hi == doc_lo) return FZ_OK;   // empty tensors carry null pointers
+    if (!a.toff || !a.pdoc || !(PVAL ? a.pval != nullptr : a.ptf && a.idf) || !a.qoff || !a.qterms) return FZ_ERR_ARG;
+    if (EPI == LEX_PLANE ? !a.scores
+        : EPI == LEX_FILTER ? !a.f.tau || !a.f.cand_s || !a.f.cand_i || !a.f.cand_len || !a.f.overflow
+                            : !a.c.gold_scores || !a.c.gold_ids || !a.c.counts) return FZ_ERR_ARG;
+    a.r = doc_range(N, doc_lo, doc_hi, BM25_GRAIN);
+    lexical_range_kernel<MODE, EPI><<<slice_grid(a.r, slice_docs<MODE>(), Q), slice_threads<MODE>(), 0, as_stream(stream)>>>(a);
+    FZ_LAUNCH_CHECK();
+    return FZ_OK;
 }
 
 extern "C" int fz_lexical_slice_docs(int tfidf) { return tfidf ? slice_docs<BM25_TFIDF>() : slice_docs<BM25_PVAL>(); }
 
 extern "C" int fz_bm25_scores_range_pv_f64(const int64_t* toff, const int32_t* pdoc, const double* pval, const int64_t* slice_off, const int64_t* qoff,
                                            const int32_t* qterms, int Q, int N, int doc_lo, int doc_hi, double* scores, int lds, void* stream) {
-    if (Q < 0 || !range_ok(N, doc_lo, doc_hi, slice_docs<BM25_PVAL>()) || lds < doc_hi - doc_lo) return FZ_ERR_ARG;
-    if (Q == 0 || doc_hi == doc_lo) return FZ_OK;   // empty tensors carry null pointers
-    if (!toff || !pdoc || !pval || !qoff || !qterms || !scores) return FZ_ERR_ARG;
-    LexArgs a = lx_args(toff, pdoc, slice_off, qoff, qterms, N, doc_lo, doc_hi);
+    LexArgs a = lx_args(toff, pdoc, slice_off, qoff, qterms);
     a.pval = pval; a.scores = scores; a.lds = lds;
-    return lx_launch<BM25_PVAL, false>(a, Q, as_stream(stream));
+    return lx_run<BM25_PVAL, LEX_PLANE>(a, Q, N, doc_lo, doc_hi, stream);
 }
 
 extern "C" int fz_tfidf_scores_range_f64(const int64_t* toff, const int32_t* pdoc, const int32_t* ptf, const double* idf, const int64_t* slice_off,
                                          const int64_t* qoff, const int32_t* qterms, int Q, int N, int doc_lo, int doc_hi, double* scores, int lds,
                                          void* stream) {
-    if (Q < 0 || !range_ok(N, doc_lo, doc_hi, slice_docs<BM25_TFIDF>()) || lds < doc_hi - doc_lo) return FZ_ERR_ARG;
-    if (Q == 0 || doc_hi == doc_lo) return FZ_OK;
-    if (!toff || !pdoc || !ptf || !idf || !qoff || !qterms || !scores) return FZ_ERR_ARG;
-    LexArgs a = lx_args(toff, pdoc, slice_off, qoff, qterms, N, doc_lo, doc_hi);
+    LexArgs a = lx_args(toff, pdoc, slice_off, qoff, qterms);
     a.ptf = ptf; a.idf = idf; a.scores = scores; a.lds = lds;
-    return lx_launch<BM25_TFIDF, false>(a, Q, as_stream(stream));
+    return lx_run<BM25_TFIDF, LEX_PLANE>(a, Q, N, doc_lo, doc_hi, stream);
 }
 
 extern "C" int fz_bm25_filter_pv_f64(const int64_t* toff, const int32_t* pdoc, const double* pval, const int64_t* slice_off, const int64_t* qoff,
                                      const int32_t* qterms, int Q, int N, int doc_lo, int doc_hi, int64_t id_base, const double* tau,
                                      double* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow, void* stream) {
-    if (Q < 0 || !range_ok(N, doc_lo, doc_hi, slice_docs<BM25_PVAL>()) || cap <= 0) return FZ_ERR_ARG;
-    if (Q == 0 || doc_hi == doc_lo) return FZ_OK;
-    if (!toff || !pdoc || !pval || !qoff || !qterms || !tau || !cand_scores || !cand_ids || !cand_len || !overflow) return FZ_ERR_ARG;
-    LexArgs a = lx_args(toff, pdoc, slice_off, qoff, qterms, N, doc_lo, doc_hi);
+    LexArgs a = lx_args(toff, pdoc, slice_off, qoff, qterms);
     a.pval = pval; a.f = {tau, cand_scores, cand_ids, cand_len, overflow, cap, id_base};
-    return lx_launch<BM25_PVAL, true>(a, Q, as_stream(stream));
+    return lx_run<BM25_PVAL, LEX_FILTER>(a, Q, N, doc_lo, doc_hi, stream);
 }
 
 extern "C" int fz_tfidf_filter_f64(const int64_t* toff, const int32_t* pdoc, const int32_t* ptf, const double* idf, const int64_t* slice_off,
                                    const int64_t* qoff, const int32_t* qterms, int Q, int N, int doc_lo, int doc_hi, int64_t id_base,
                                    const double* tau, double* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow,
                                    void* stream) {
-    if (Q < 0 || !range_ok(N, doc_lo, doc_hi, slice_docs<BM25_TFIDF>()) || cap <= 0) return FZ_ERR_ARG;
-    if (Q == 0 || doc_hi == doc_lo) return FZ_OK;
-    if (!toff || !pdoc || !ptf || !idf || !qoff || !qterms || !tau || !cand_scores || !cand_ids || !cand_len || !overflow) return FZ_ERR_ARG;
-    LexArgs a = lx_args(toff, pdoc, slice_off, qoff, qterms, N, doc_lo, doc_hi);
+    LexArgs a = lx_args(toff, pdoc, slice_off, qoff, qterms);
     a.ptf = ptf; a.idf = idf; a.f = {tau, cand_scores, cand_ids, cand_len, overflow, cap, id_base};
-    return lx_launch<BM25_TFIDF, true>(a, Q, as_stream(stream));
+    return lx_run<BM25_TFIDF, LEX_FILTER>(a, Q, N, doc_lo, doc_hi, stream);
+}
+
+extern "C" int fz_bm25_count_pv_f64(const int64_t* toff, const int32_t* pdoc, const double* pval, const int64_t* slice_off, const int64_t* qoff,
+                                    const int32_t* qterms, int Q, int N, int doc_lo, int doc_hi, int64_t id_base, const double* gold_scores,
+                                    const int64_t* gold_ids, int G, int32_t* counts, void* stream) {
+    LexArgs a = lx_args(toff, pdoc, slice_off, qoff, qterms);
+    a.pval = pval; a.c = {gold_scores, gold_ids, counts, G, id_base};
+    return lx_run<BM25_PVAL, LEX_COUNT>(a, Q, N, doc_lo, doc_hi, stream);
+}
+
+extern "C" int fz_tfidf_count_f64(const int64_t* toff, const int32_t* pdoc, const int32_t* ptf, const double* idf, const int64_t* slice_off,
+                                  const int64_t* qoff, const int32_t* qterms, int Q, int N, int doc_lo, int doc_hi, int64_t id_base,
+                                  const double* gold_scores, const int64_t* gold_ids, int G, int32_t* counts, void* stream) {
+    LexArgs a = lx_args(toff, pdoc, slice_off, qoff, qterms);
+    a.ptf = ptf; a.idf = idf; a.c = {gold_scores, gold_ids, counts, G, id_base};
+    return lx_run<BM25_TFIDF, LEX_COUNT>(a, Q, N, doc_lo, doc_hi, stream);
 }

@@ -161,12 +161,12 @@ extern "C" int fz_centroid_slice_offsets(const int64_t* coff, const int32_t* cdo
 }
 
 // [doc_lo, doc_hi) of an index of N documents: doc_lo a whole slice, doc_hi a whole slice or N; a probe table of Lq >= 1 tokens x nprobe >= 1
-static bool ct_args_ok(int Q, int Lq, int nprobe, int N, int K, int doc_lo, int doc_hi) {
+static bool cen_args_ok(int Q, int Lq, int nprobe, int N, int K, int doc_lo, int doc_hi) {
     return Q >= 0 && Lq >= 1 && nprobe >= 1 && (int64_t)Lq * nprobe <= INT32_MAX && K >= 0 &&
            range_ok(N, doc_lo, doc_hi, CT_SLICE);
 }
 
-static CentroidArgs ct_args(const int64_t* coff, const int32_t* cdoc, const int64_t* slice_off, const int32_t* pc, const float* ps, int Lq, int nprobe,
+static CentroidArgs cen_args(const int64_t* coff, const int32_t* cdoc, const int64_t* slice_off, const int32_t* pc, const float* ps, int Lq, int nprobe,
                             int K, int N, int doc_lo, int doc_hi) {
     CentroidArgs a{};
     a.coff = coff; a.cdoc = cdoc; a.slice_off = slice_off; a.pc = pc; a.ps = ps; a.Lq = Lq; a.nprobe = nprobe; a.K = K;
@@ -174,7 +174,7 @@ static CentroidArgs ct_args(const int64_t* coff, const int32_t* cdoc, const int6
     return a;
 }
 
-static int ct_launch(const CentroidArgs& a, int Q, bool filter, hipStream_t st) {
+static int cen_launch(const CentroidArgs& a, int Q, bool filter, hipStream_t st) {
     const dim3 grid = slice_grid(a.r, CT_SLICE, Q);
     if (filter) centroid_scores_filter_kernel<<<grid, CT_THREADS, 0, st>>>(a);
     else centroid_scores_kernel<<<grid, CT_THREADS, 0, st>>>(a);
@@ -185,21 +185,21 @@ static int ct_launch(const CentroidArgs& a, int Q, bool filter, hipStream_t st) 
 extern "C" int fz_centroid_scores_range_f32(const int64_t* coff, const int32_t* cdoc, const int64_t* slice_off, const int32_t* pc, const float* ps,
                                             int Q, int Lq, int nprobe, int N, int K, int doc_lo, int doc_hi, float* scores, int lds,
                                             void* stream) {
-    if (!ct_args_ok(Q, Lq, nprobe, N, K, doc_lo, doc_hi) || lds < doc_hi - doc_lo) return FZ_ERR_ARG;
+    if (!cen_args_ok(Q, Lq, nprobe, N, K, doc_lo, doc_hi) || lds < doc_hi - doc_lo) return FZ_ERR_ARG;
     if (Q == 0 || doc_hi == doc_lo) return FZ_OK;   // empty tensors carry null pointers
     if (!coff || !pc || !ps || !scores) return FZ_ERR_ARG;
-    CentroidArgs a = ct_args(coff, cdoc, slice_off, pc, ps, Lq, nprobe, K, N, doc_lo, doc_hi);
+    CentroidArgs a = cen_args(coff, cdoc, slice_off, pc, ps, Lq, nprobe, K, N, doc_lo, doc_hi);
     a.scores = scores; a.lds = lds;
-    return ct_launch(a, Q, false, as_stream(stream));
+    return cen_launch(a, Q, false, as_stream(stream));
 }
 
 extern "C" int fz_centroid_scores_filter_f32(const int64_t* coff, const int32_t* cdoc, const int64_t* slice_off, const int32_t* pc, const float* ps,
                                              int Q, int Lq, int nprobe, int N, int K, int doc_lo, int doc_hi, int64_t id_base, const float* tau,
                                              float* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow, void* stream) {
-    if (!ct_args_ok(Q, Lq, nprobe, N, K, doc_lo, doc_hi) || cap <= 0) return FZ_ERR_ARG;
+    if (!cen_args_ok(Q, Lq, nprobe, N, K, doc_lo, doc_hi) || cap <= 0) return FZ_ERR_ARG;
     if (Q == 0 || doc_hi == doc_lo) return FZ_OK;
     if (!coff || !pc || !ps || !tau || !cand_scores || !cand_ids || !cand_len || !overflow) return FZ_ERR_ARG;
-    CentroidArgs a = ct_args(coff, cdoc, slice_off, pc, ps, Lq, nprobe, K, N, doc_lo, doc_hi);
+    CentroidArgs a = cen_args(coff, cdoc, slice_off, pc, ps, Lq, nprobe, K, N, doc_lo, doc_hi);
     a.f = {tau, cand_scores, cand_ids, cand_len, overflow, cap, id_base};
-    return ct_launch(a, Q, true, as_stream(stream));
+    return cen_launch(a, Q, true, as_stream(stream));
 }

@@ -1612,29 +1612,40 @@ def _lexical_args(what: str, mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: 
     return _doc_range(what, N, lexical_slice_docs(mode), doc_lo, doc_hi)
 
 
+def _lexical_call(mode: str, stem: str, toff, pdoc, vals, idf, *rest) -> None:
+    """The one place the two modes' twin C entries part: fz_bm25_<stem>_pv_f64(toff, pdoc, vals, *rest, stream) for 'pv',
+    fz_tfidf_<stem>_f64(toff, pdoc, vals, idf, *rest, stream) for 'tfidf' -- the same argument list with idf after the posting values."""
+    name = f"fz_bm25_{stem}_pv_f64" if mode == "pv" else f"fz_tfidf_{stem}_f64"
+    values = (_ptr(vals),) if mode == "pv" else (_ptr(vals), _ptr(idf))
+    check(getattr(_lib.lib(), name)(_ptr(toff), _ptr(pdoc), *values, *rest, _stream(toff)), name)
+
+
 def _range_plane64(Q: int, n: int, dev) -> torch.Tensor:
     return torch.empty((max(Q, 1), max(round_up(n, _PAD), _PAD)), dtype=torch.float64, device=dev)[:Q, :n]
 
 
+def lexical_scores_range(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int, doc_lo: int = 0, doc_hi: int | None = None,
+                         slice_off: torch.Tensor | None = None) -> torch.Tensor:
+    """Columns [doc_lo, doc_hi) of the full float64 plane, bit for bit, without the rest of it (fz_bm25_scores_range_pv_f64 /
+    fz_tfidf_scores_range_f64): [Q, doc_hi - doc_lo], column j = document doc_lo + j.  doc_lo a multiple of lexical_slice_docs(mode), doc_hi
+    a multiple of it or N.  vals: pval ('pv') or ptf ('tfidf', with idf)."""
+    what = ("bm25" if mode == "pv" else "tfidf") + "_scores_range"      # the public wrappers' names: what a caller reads in an error
+    doc_lo, doc_hi = _lexical_args(what, mode, toff, pdoc, vals, idf, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
+    out = _range_plane64(Q, doc_hi - doc_lo, toff.device)
+    _lexical_call(mode, "scores_range", toff, pdoc, vals, idf, _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi, _ptr(out), _ld(out))
+    return out
+
+
 def bm25_scores_range(toff, pdoc, pval, qoff, qterms, Q: int, N: int, doc_lo: int = 0, doc_hi: int | None = None,
                       slice_off: torch.Tensor | None = None) -> torch.Tensor:
-    """Columns [doc_lo, doc_hi) of bm25_scores(pval=...)'s float64 plane, bit for bit, without the rest of it (fz_bm25_scores_range_pv_f64):
-    [Q, doc_hi - doc_lo], column j = document doc_lo + j.  doc_lo a multiple of lexical_slice_docs('pv'), doc_hi a multiple of it or N."""
-    doc_lo, doc_hi = _lexical_args("bm25_scores_range", "pv", toff, pdoc, pval, None, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
-    out = _range_plane64(Q, doc_hi - doc_lo, toff.device)
-    check(_lib.lib().fz_bm25_scores_range_pv_f64(_ptr(toff), _ptr(pdoc), _ptr(pval), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi,
-                                                 _ptr(out), _ld(out), _stream(toff)), "fz_bm25_scores_range_pv_f64")
-    return out
+    """lexical_scores_range('pv'): columns [doc_lo, doc_hi) of bm25_scores(pval=...)'s float64 plane; slices of lexical_slice_docs('pv')."""
+    return lexical_scores_range("pv", toff, pdoc, pval, None, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
 
 
 def tfidf_scores_range(toff, pdoc, ptf, idf, qoff, qterms, Q: int, N: int, doc_lo: int = 0, doc_hi: int | None = None,
                        slice_off: torch.Tensor | None = None) -> torch.Tensor:
-    """Columns [doc_lo, doc_hi) of tfidf_scores' float64 plane, bit for bit (fz_tfidf_scores_range_f64); slices of lexical_slice_docs('tfidf')."""
-    doc_lo, doc_hi = _lexical_args("tfidf_scores_range", "tfidf", toff, pdoc, ptf, idf, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
-    out = _range_plane64(Q, doc_hi - doc_lo, toff.device)
-    check(_lib.lib().fz_tfidf_scores_range_f64(_ptr(toff), _ptr(pdoc), _ptr(ptf), _ptr(idf), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo,
-                                               doc_hi, _ptr(out), _ld(out), _stream(toff)), "fz_tfidf_scores_range_f64")
-    return out
+    """lexical_scores_range('tfidf'): columns [doc_lo, doc_hi) of tfidf_scores' float64 plane; slices of lexical_slice_docs('tfidf')."""
+    return lexical_scores_range("tfidf", toff, pdoc, ptf, idf, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
 
 
 def lexical_filter(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int, doc_lo: int, doc_hi: int, id_base: int, tau, cand_s, cand_i,
@@ -1644,14 +1655,9 @@ def lexical_filter(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: in
     past cap, nothing is stored there, `overflow` (int32 [1]) is set.  vals: pval ('pv') or ptf ('tfidf', with idf)."""
     what = "lexical_filter"
     doc_lo, doc_hi = _lexical_args(what, mode, toff, pdoc, vals, idf, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
-    cap, lib = _cand_buffers(what, torch.float64, Q, tau, cand_s, cand_i, cand_len, overflow), _lib.lib()
-    if mode == "pv":
-        check(lib.fz_bm25_filter_pv_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi, int(id_base),
-                                        _ptr(tau), _ptr(cand_s), _ptr(cand_i), _ptr(cand_len), cap, _ptr(overflow), _stream(toff)), "fz_bm25_filter_pv_f64")
-    else:
-        check(lib.fz_tfidf_filter_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(idf), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi,
-                                      int(id_base), _ptr(tau), _ptr(cand_s), _ptr(cand_i), _ptr(cand_len), cap, _ptr(overflow), _stream(toff)),
-              "fz_tfidf_filter_f64")
+    cap = _cand_buffers(what, torch.float64, Q, tau, cand_s, cand_i, cand_len, overflow)
+    _lexical_call(mode, "filter", toff, pdoc, vals, idf, _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi, int(id_base), _ptr(tau),
+                  _ptr(cand_s), _ptr(cand_i), _ptr(cand_len), cap, _ptr(overflow))
 
 
 def _query_blocks(Q: int, block: int):
@@ -1666,15 +1672,10 @@ def lexical_doc_scores(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N
     _lexical_args(what, mode, toff, pdoc, vals, idf, qoff, qterms, Q, N, 0, None, None)
     _need(_dev(docs, torch.int32, f"{what}(docs)").is_contiguous() and docs.dim() == 2 and docs.shape[0] == Q and docs.shape[1] >= 1,
           f"{what}: docs must be a contiguous [Q, G >= 1] int32 tensor")
-    G, lib = docs.shape[1], _lib.lib()
+    G = docs.shape[1]
     out = torch.empty((Q, G), dtype=torch.float64, device=toff.device)
     for lo, hi in _query_blocks(Q, block):
-        if mode == "pv":
-            check(lib.fz_bm25_doc_scores_pv_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(qoff[lo:]), _ptr(qterms), hi - lo, N, _ptr(docs[lo:]), G,
-                                                _ptr(out[lo:]), _stream(toff)), "fz_bm25_doc_scores_pv_f64")
-        else:
-            check(lib.fz_tfidf_doc_scores_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(idf), _ptr(qoff[lo:]), _ptr(qterms), hi - lo, N, _ptr(docs[lo:]),
-                                              G, _ptr(out[lo:]), _stream(toff)), "fz_tfidf_doc_scores_f64")
+        _lexical_call(mode, "doc_scores", toff, pdoc, vals, idf, _ptr(qoff[lo:]), _ptr(qterms), hi - lo, N, _ptr(docs[lo:]), G, _ptr(out[lo:]))
     return out
 
 
@@ -1690,17 +1691,11 @@ def lexical_doc_scores_fwd(mode: str, toff, pdoc, vals, idf, forward: "ForwardIn
     _need(forward.N == N and forward.nnz == pdoc.numel(), f"{what}: the forward index must be the one built from these postings")
     _need(_dev(docs, torch.int32, f"{what}(docs)").is_contiguous() and docs.dim() == 2 and docs.shape[0] == Q and docs.shape[1] >= 1,
           f"{what}: docs must be a contiguous [Q, G >= 1] int32 tensor")
-    G, lib, f = docs.shape[1], _lib.lib(), forward
+    G, f = docs.shape[1], forward
     out = torch.empty((Q, G), dtype=torch.float64, device=toff.device)
     for lo, hi in _query_blocks(Q, block):
-        if mode == "pv":
-            check(lib.fz_bm25_doc_scores_fwd_pv_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(f.foff), _ptr(f.fterm), _ptr(f.fpos), _ptr(qoff[lo:]),
-                                                    _ptr(qterms), hi - lo, N, _ptr(docs[lo:]), G, _ptr(out[lo:]), _stream(toff)),
-                  "fz_bm25_doc_scores_fwd_pv_f64")
-        else:
-            check(lib.fz_tfidf_doc_scores_fwd_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(idf), _ptr(f.foff), _ptr(f.fterm), _ptr(f.fpos),
-                                                  _ptr(qoff[lo:]), _ptr(qterms), hi - lo, N, _ptr(docs[lo:]), G, _ptr(out[lo:]), _stream(toff)),
-                  "fz_tfidf_doc_scores_fwd_f64")
+        _lexical_call(mode, "doc_scores_fwd", toff, pdoc, vals, idf, _ptr(f.foff), _ptr(f.fterm), _ptr(f.fpos), _ptr(qoff[lo:]), _ptr(qterms), hi - lo,
+                      N, _ptr(docs[lo:]), G, _ptr(out[lo:]))
     return out
 
 
@@ -1716,16 +1711,9 @@ def lexical_count(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int
     G = gold_scores.shape[1] if gold_scores.dim() == 2 else 0
     _need(G >= 1 and all(t.is_contiguous() and tuple(t.shape) == (Q, G) for t in (gold_scores, gold_ids, counts)),
           f"{what}: gold_scores, gold_ids and counts must be contiguous [Q, G >= 1] tensors")
-    lib = _lib.lib()
     for lo, hi in _query_blocks(Q, block):
-        if mode == "pv":
-            check(lib.fz_bm25_count_pv_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(slice_off), _ptr(qoff[lo:]), _ptr(qterms), hi - lo, N, doc_lo, doc_hi,
-                                           int(id_base), _ptr(gold_scores[lo:]), _ptr(gold_ids[lo:]), G, _ptr(counts[lo:]), _stream(toff)),
-                  "fz_bm25_count_pv_f64")
-        else:
-            check(lib.fz_tfidf_count_f64(_ptr(toff), _ptr(pdoc), _ptr(vals), _ptr(idf), _ptr(slice_off), _ptr(qoff[lo:]), _ptr(qterms), hi - lo, N, doc_lo,
-                                         doc_hi, int(id_base), _ptr(gold_scores[lo:]), _ptr(gold_ids[lo:]), G, _ptr(counts[lo:]), _stream(toff)),
-                  "fz_tfidf_count_f64")
+        _lexical_call(mode, "count", toff, pdoc, vals, idf, _ptr(slice_off), _ptr(qoff[lo:]), _ptr(qterms), hi - lo, N, doc_lo, doc_hi, int(id_base),
+                      _ptr(gold_scores[lo:]), _ptr(gold_ids[lo:]), G, _ptr(counts[lo:]))
 
 
 def _lexical_source(model, qoff, qterms, id_base: int) -> _Source:
@@ -1741,9 +1729,7 @@ def _lexical_source(model, qoff, qterms, id_base: int) -> _Source:
                        st.overflow, slice_off=so)
 
     def plane(lo, hi):
-        if mode == "pv":
-            return bm25_scores_range(model.toff, model.pdoc, vals, qoff, qterms, Q, N, lo, hi, slice_off=so), id_base + lo
-        return tfidf_scores_range(model.toff, model.pdoc, vals, idf, qoff, qterms, Q, N, lo, hi, slice_off=so), id_base + lo
+        return lexical_scores_range(mode, model.toff, model.pdoc, vals, idf, qoff, qterms, Q, N, lo, hi, slice_off=so), id_base + lo
     return _Source(N, filter, plane, grain=lexical_slice_docs(mode), unordered=True, mark="shard_lexical_filter")
 
 

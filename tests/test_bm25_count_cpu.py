@@ -1,6 +1,6 @@
-"""The gold-rank counting kernels without a GPU: the four entries of csrc/bm25_count.hip are exported, declared and refuse bad arguments
-before any HIP call, in the order of the range entries of csrc/bm25_stream.hip; the kernels' resource reports (no spills, no scratch,
-the count kernels' LDS exactly the walk's)."""
+"""The gold-rank counting kernels without a GPU: the two entries of csrc/bm25_count.hip and the two count entries of csrc/bm25_stream.hip are
+exported, declared and refuse bad arguments before any HIP call, in the order of the other range entries of csrc/bm25_stream.hip; the
+kernels' resource reports (no spills, no scratch, the count kernels' LDS exactly the walk's, their registers what they were)."""
 import ctypes as C
 import os
 import re
@@ -104,11 +104,20 @@ def resources():
 
 def test_count_kernels_hold_everything_in_registers_and_exactly_the_walks_lds(resources):
     ks = {kernel_resources.short(n): k for n, k in resources["bm25_count"].items()}
-    assert sorted(ks) == sorted([f"lexical_doc_scores_kernel<{m}>" for m in (1, 2)] + [f"lexical_count_kernel<{m}>" for m in (1, 2)])
+    assert sorted(ks) == sorted(f"lexical_doc_scores_kernel<{m}>" for m in (1, 2))
+    # the counting walk: csrc/bm25_stream.hip's lexical_range_kernel<MODE, EPI> with EPI = 2 (LEX_COUNT)
+    counts = {kernel_resources.short(n): k for n, k in resources["bm25_stream"].items() if kernel_resources.short(n).endswith(", 2>")}
+    assert sorted(counts) == sorted(f"lexical_range_kernel<{m}, 2>" for m in (1, 2))
+    ks.update(counts)
     tables = 3 * 256 * 8                                              # s_e0, s_e1, s_w: BM25_TERMS entries each
     for name, k in ks.items():
         assert k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0 and k["scratch"] == 0, (name, k)
-        if "count" in name:                                           # accumulators + term tables: the epilogue has no LDS of its own
-            assert k["lds"] == (28 if "<2>" in name else 56) * 1024 + tables, (name, k["lds"])
+        if name in counts:                                            # accumulators + term tables: the epilogue has no LDS of its own
+            assert k["lds"] == (28 if "<2," in name else 56) * 1024 + tables, (name, k["lds"])
         else:
             assert k["lds"] == 0, (name, k["lds"])
+    # VGPRs, SGPRs, LDS, occupancy of the count when it was a kernel of its own in csrc/bm25_count.hip (waves_per_eu(8, 8): 72 SGPRs, not 101)
+    want = {"lexical_range_kernel<2, 2>": (58, 72, 34816, 8), "lexical_range_kernel<1, 2>": (51, 72, 63488, 8)}
+    for name, (vgprs, sgprs, lds, occupancy) in want.items():
+        k = counts[name]
+        assert (k["vgprs"], k["sgprs"], k["agprs"], k["lds"], k["occupancy"]) == (vgprs, sgprs, 0, lds, occupancy), (name, k)

@@ -144,13 +144,22 @@ def resources():
 
 def test_range_kernels_hold_everything_in_registers_and_the_stated_lds(resources):
     ks = {kernel_resources.short(n): k for n, k in resources["bm25_stream"].items()}
-    assert sorted(ks) == sorted(f"lexical_range_kernel<{mode}, {f}>" for mode in (1, 2) for f in ("false", "true"))
+    # <MODE, EPI>: MODE 1 = BM25_TFIDF, 2 = BM25_PVAL; EPI 0 = LEX_PLANE, 1 = LEX_FILTER, 2 = LEX_COUNT (tests/test_bm25_count_cpu.py's)
+    assert sorted(ks) == sorted(f"lexical_range_kernel<{mode}, {epi}>" for mode in (1, 2) for epi in (0, 1, 2))
+    ks = {name: k for name, k in ks.items() if not name.endswith(", 2>")}
     tables = 3 * 256 * 8                                              # s_e0, s_e1, s_w: BM25_TERMS entries each
     for name, k in ks.items():
         assert k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0 and k["scratch"] == 0, (name, k)
         acc = (28 if "<2," in name else 56) * 1024                    # the slice's float64 accumulators: BM25_PVAL 28 KiB, BM25_TFIDF 56 KiB
         extra = k["lds"] - acc - tables
-        assert extra == 0 if "false" in name else 0 <= extra <= 256, (name, k["lds"])   # (the filter's workgroup-wide overflow vote)
+        assert extra == 0 if ", 0>" in name else 0 <= extra <= 256, (name, k["lds"])   # (the filter's workgroup-wide overflow vote)
+    # VGPRs, SGPRs, LDS, occupancy of lexical_range_kernel<MODE, bool FILTER> before the count became its third epilogue
+    want = {"lexical_range_kernel<2, 0>": (60, 56, 34816, 8), "lexical_range_kernel<1, 0>": (32, 58, 63488, 8),
+            "lexical_range_kernel<2, 1>": (60, 66, 34816, 8), "lexical_range_kernel<1, 1>": (33, 67, 63488, 8)}
+    assert sorted(want) == sorted(ks)
+    for name, (vgprs, sgprs, lds, occupancy) in want.items():
+        k = ks[name]
+        assert (k["vgprs"], k["sgprs"], k["agprs"], k["lds"], k["occupancy"]) == (vgprs, sgprs, 0, lds, occupancy), (name, k)
 
 
 def test_bm25_kernel_resources_are_what_they_were(resources):

@@ -30,7 +30,7 @@ NO_SPILL = {
     "maxsim_kernel": "ColBERT MaxSim",
     "maxsim8_kernel": "ColBERT MaxSim over e4m3 tokens: the same tile walk",
     "sparse_dot_kernel": "SPLADE inverted-index scoring",
-    "lexical_range_kernel": "BM25 / TF-IDF over a document range: plane and streaming top-k filter",
+    "lexical_range_kernel": "BM25 / TF-IDF over a document range: plane, streaming top-k filter and gold-rank count",
     "centroid_scores_kernel": "ColBERT candidate stage: plane and streaming top-k filter",
     "insertion_order_kernel": "first-insertion order of partial lists",
 }
