@@ -1107,7 +1107,10 @@ def gold_ranks(T: list[torch.Tensor], pos: torch.Tensor, weights: torch.Tensor, 
     ld = _same_ld(*T, pos)
     out = torch.zeros((W, Q, G), dtype=torch.int32, device=T[0].device)
     fn = lib.fz_gold_ranks_f64w if weights.dtype == torch.float64 else lib.fz_gold_ranks_f32
-    check(fn(_ptr_array(T), _ptr(pos), _ptr(weights.contiguous()), _ptr(gold.contiguous()), S, W, Q, N, ld, _ptr(out), _stream(T[0])),
+    # the contiguous copies stay referenced until the launch is queued: a copy made inside the argument list dies at once, and the
+    # allocator hands its block to the NEXT copy made there (strided weights AND strided gold: the sweep read the golds as weights)
+    weights, gold = weights.contiguous(), gold.contiguous()
+    check(fn(_ptr_array(T), _ptr(pos), _ptr(weights), _ptr(gold), S, W, Q, N, ld, _ptr(out), _stream(T[0])),
           "fz_gold_ranks")
     return out
 
@@ -1132,8 +1135,9 @@ def tune_metrics(ranks: torch.Tensor, gold: torch.Tensor, pos: torch.Tensor, n_g
     pos = as_plane(pos)
     cuts_dev = torch.tensor(flat if flat else [0], dtype=torch.int32, device=ranks.device)
     out = torch.empty((W, len(flat) + 1), dtype=torch.float64, device=ranks.device)
-    check(lib.fz_tune_metrics_f64(_ptr(ranks.contiguous()), _ptr(gold.contiguous()), _ptr(pos), pos.stride(0), _ptr(n_gold.contiguous()),
-                                  _ptr(idcg.contiguous()), _ptr(disc.contiguous()), int(disc.numel()) - 1, _ptr(cuts_dev), len(fam[0]),
+    ranks, gold, n_gold, idcg, disc = (t.contiguous() for t in (ranks, gold, n_gold, idcg, disc))   # referenced until the launch is queued (see gold_ranks)
+    check(lib.fz_tune_metrics_f64(_ptr(ranks), _ptr(gold), _ptr(pos), pos.stride(0), _ptr(n_gold),
+                                  _ptr(idcg), _ptr(disc), int(disc.numel()) - 1, _ptr(cuts_dev), len(fam[0]),
                                   len(fam[1]), len(fam[2]), len(fam[3]), W, Q, _ptr(out), _stream(ranks)), "fz_tune_metrics_f64")
     return out
 
@@ -1179,7 +1183,8 @@ def topk_update(scores: torch.Tensor, id_base: int, run_scores: torch.Tensor, ru
     ni = torch.empty((rows, k), dtype=torch.int64, device=dev)
     wsb = int(lib.fz_topk_update_workspace_bytes(rows, k, cap))
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-    check(lib.fz_topk_update_f32(_ptr(scores), rows, n, _ld(scores), int(id_base), _ptr(run_scores.contiguous()), _ptr(run_ids.contiguous()), k, cap,
+    run_scores, run_ids = run_scores.contiguous(), run_ids.contiguous()     # referenced until the launch is queued (see gold_ranks)
+    check(lib.fz_topk_update_f32(_ptr(scores), rows, n, _ld(scores), int(id_base), _ptr(run_scores), _ptr(run_ids), k, cap,
                                  _ptr(ns), _ptr(ni), _ptr(overflow), _ptr(ws), wsb, _stream(scores)), "fz_topk_update_f32")
     return ns, ni, overflow
 
