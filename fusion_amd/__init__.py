@@ -11,5 +11,6 @@ Layout (only what the encode -> score -> fuse hot path needs):
   utils/metrics.py      Metrics
   encoders.py           PyTorch-ROCm transformer forwards (DPR mean-pool, SPLADE, ColBERT)
   distributed.py        corpus-sharded top-k with one RCCL all-gather
+  passages.py           long documents: passage windows, passage lists -> document lists (MaxP)
 """
 __version__ = "0.1.0"

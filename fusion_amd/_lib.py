@@ -97,6 +97,12 @@ _PROTOS = {
     "fz_lists_join": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "fz_lists_columns_workspace_bytes": (_sz, [_i, _i]),
     "fz_lists_columns": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "fz_lists_collapse_workspace_bytes": (_sz, [_i]),
+    "fz_lists_collapse": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "fz_group_expand_workspace_bytes": (_sz, [_i]),
+    "fz_group_expand": (_i, [_vp, _i, _vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "fz_group_max_f32": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    "fz_group_max_f64": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
     "fz_topk_max_k": (_i, []),
     "fz_topk_rows_plan": (_i, [_i, _i, _vp]),
     "fz_topk_fold_max_k": (_i, [_i]),

@@ -1082,6 +1082,132 @@ def lists_columns(ids: list[torch.Tensor], lens: list[torch.Tensor], values: lis
     return out_ids, T, pos, out_len, gold_col
 
 
+def _flag_word(ws: torch.Tensor) -> int:
+    """The one flag read of a call: the int32 at offset 0 of its workspace."""
+    return int(ws[:4].view(torch.int32).item())
+
+
+def lists_collapse(ids: torch.Tensor, scores: torch.Tensor, lens: torch.Tensor, group_of: torch.Tensor, *, id_base: int = 0,
+                   doc_id_base: int = 0, scores64: torch.Tensor | None = None):
+    """One PASSAGE top-k list per query -> the DOCUMENT list, MaxP (fz_lists_collapse).  ids [Q, n] int64 passage ids in
+    (score desc, id asc) order, scores [Q, n] float32, scores64 [Q, n] float64 or None, lens [Q] int32 (entries past a list's length are
+    never read); passage id p + id_base belongs to document group_of[p] + doc_id_base (group_of [P] int32, non-decreasing).
+    Returns (doc_ids [Q, n] int64, doc_scores [Q, n] float32, doc_scores64 or None, best [Q, n] int64, out_len [Q] int32): column c is
+    the c-th distinct document of the list -- in a ranked list its MaxP rank --, with the score bits and the passage id of the document's
+    first (= best) entry; (-1, -inf, -1) from out_len on.  ValueError for a passage id outside [id_base, id_base + P), for a row whose
+    scores are not non-increasing (NaN included) and for n beyond lists_max_entries() (one flag read per call)."""
+    _dev(ids, torch.int64, "lists_collapse(ids)")
+    _dev(scores, torch.float32, "lists_collapse(scores)")
+    _dev(lens, torch.int32, "lists_collapse(lens)")
+    _dev(group_of, torch.int32, "lists_collapse(group_of)")
+    _need(ids.dim() == 2, f"lists_collapse(ids): expected a [Q, n] tensor, got {tuple(ids.shape)}")
+    Q, n = int(ids.shape[0]), int(ids.shape[1])
+    _need(tuple(scores.shape) == (Q, n), f"lists_collapse(scores): ids are {(Q, n)} but scores {tuple(scores.shape)}")
+    _need(lens.numel() == Q, f"lists_collapse(lens): expected {Q} lengths, got {lens.numel()}")
+    _need(group_of.dim() == 1, f"lists_collapse(group_of): expected a [P] tensor, got {tuple(group_of.shape)}")
+    if scores64 is not None:
+        _dev(scores64, torch.float64, "lists_collapse(scores64)")
+        _need(tuple(scores64.shape) == (Q, n), f"lists_collapse(scores64): ids are {(Q, n)} but scores64 {tuple(scores64.shape)}")
+    cap = lists_max_entries()
+    _need(n <= cap, f"lists_collapse: the list of one query holds up to {n} entries, a collapse takes at most {cap} (fz_lists_max_entries)")
+    planes = [ids, scores] + ([scores64] if scores64 is not None else [])
+    if len({max(_ld(t), n) for t in planes}) > 1:      # one row stride for the list's planes
+        planes = [t.contiguous() for t in planes]
+    ids, scores = planes[0], planes[1]
+    scores64 = planes[2] if scores64 is not None else None
+    lens, group_of = lens.contiguous(), group_of.contiguous()
+    dev = ids.device
+    out_ids = alloc_plane(Q, n, torch.int64, dev)
+    out_sc = alloc_plane(Q, n, torch.float32, dev)
+    out_sc64 = alloc_plane(Q, n, torch.float64, dev) if scores64 is not None else None
+    best = alloc_plane(Q, n, torch.int64, dev)
+    out_len = torch.zeros(Q, dtype=torch.int32, device=dev)
+    if Q == 0 or n == 0:
+        return out_ids, out_sc, out_sc64, best, out_len
+    ld_out = _same_ld(out_ids, out_sc, best, out_sc64)
+    lib = _lib.lib()
+    ws = torch.empty(max(int(lib.fz_lists_collapse_workspace_bytes(Q)), 4), dtype=torch.uint8, device=dev)
+    check(lib.fz_lists_collapse(_ptr(ids), _ptr(scores), _ptr(scores64), _ptr(lens), max(_ld(ids), n), n, Q, _ptr(group_of),
+                                int(group_of.numel()), int(id_base), int(doc_id_base), _ptr(out_ids), _ptr(out_sc), _ptr(out_sc64),
+                                _ptr(best), _ptr(out_len), ld_out, _ptr(ws), ws.numel(), _stream(ids)), "fz_lists_collapse")
+    flag = _flag_word(ws)
+    if flag & 1:
+        raise ValueError(f"lists_collapse: a list holds a passage id outside [{int(id_base)}, {int(id_base) + int(group_of.numel())}) "
+                         "(the passages of the group table)")
+    if flag & 2:
+        raise ValueError("lists_collapse: a list is not in descending score order (or holds NaN): MaxP by first occurrence needs a ranked list")
+    return out_ids, out_sc, out_sc64, best, out_len
+
+
+def group_expand(cand: torch.Tensor, cand_len: torch.Tensor | None, poff: torch.Tensor, ldp: int, *, id_base: int = 0,
+                 doc_id_base: int = 0):
+    """Candidate DOCUMENT ids -> their passages (fz_group_expand).  cand [Q, W] int64 (rows may be strided), cand_len [Q] int32 or None
+    (= W everywhere), poff [D + 1] int64: document d + doc_id_base owns passages poff[d] + id_base .. poff[d + 1] + id_base - 1.
+    Returns (pcand [Q, ldp] int64 -- slot 0's passages first, then slot 1's, ...; -1 from pcand_len on --, seg [Q, W + 1] int32 segment
+    offsets, pcand_len [Q] int32).  A padded slot, a negative or unknown id and a document without passages get an empty segment.
+    ValueError when a row needs more than ldp slots (one flag read per call)."""
+    _dev(cand, torch.int64, "group_expand(cand)")
+    _dev(poff, torch.int64, "group_expand(poff)")
+    _need(cand.dim() == 2, f"group_expand(cand): expected a [Q, W] tensor, got {tuple(cand.shape)}")
+    _need(poff.dim() == 1 and poff.numel() >= 1, f"group_expand(poff): expected a [D + 1] tensor, got {tuple(poff.shape)}")
+    Q, W, ldp = int(cand.shape[0]), int(cand.shape[1]), int(ldp)
+    _need(ldp >= 0, f"group_expand: ldp = {ldp} is negative")
+    if cand_len is not None:
+        _dev(cand_len, torch.int32, "group_expand(cand_len)")
+        _need(tuple(cand_len.shape) == (Q,), f"group_expand(cand_len): expected shape {(Q,)}, got {tuple(cand_len.shape)}")
+    poff = poff.contiguous()
+    dev = cand.device
+    pcand = torch.empty((Q, ldp), dtype=torch.int64, device=dev)
+    seg = torch.empty((Q, W + 1), dtype=torch.int32, device=dev)
+    pcand_len = torch.empty(Q, dtype=torch.int32, device=dev)
+    if Q == 0:
+        return pcand, seg, pcand_len
+    lib = _lib.lib()
+    ws = torch.empty(max(int(lib.fz_group_expand_workspace_bytes(Q)), 4), dtype=torch.uint8, device=dev)
+    check(lib.fz_group_expand(_ptr(cand), max(_ld(cand), W), _ptr(cand_len), W, Q, _ptr(poff), int(poff.numel()) - 1, int(id_base),
+                              int(doc_id_base), _ptr(pcand), ldp, _ptr(seg), _ptr(pcand_len), _ptr(ws), ws.numel(), _stream(cand)),
+          "fz_group_expand")
+    if _flag_word(ws) != 0:
+        raise ValueError(f"group_expand: the passages of one query's candidates do not fit ldp = {ldp} slots")
+    return pcand, seg, pcand_len
+
+
+def group_max(pscores: torch.Tensor, pcand: torch.Tensor, seg: torch.Tensor, cand_len: torch.Tensor | None = None,
+              out: torch.Tensor | None = None, best: torch.Tensor | None = None):
+    """The maximum over every slot's segment of passage scores (fz_group_max_f32 / _f64).  pscores [Q, ldp] float32 or float64 (the pair
+    scores of group_expand's pcand [Q, ldp]), seg [Q, W + 1] int32, cand_len [Q] int32 or None.  Returns (out [Q, W] of pscores' dtype,
+    best [Q, W] int64): the winning entry's own bits and the passage id of the first maximum (the lowest passage id among equals);
+    (-inf, -1) for an empty segment and for a slot past cand_len.  `out` / `best` may be views into wider planes of one row stride."""
+    _dev(pscores, None, "group_max(pscores)")
+    if pscores.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"group_max: passage scores must be float32 or float64, got {pscores.dtype}")
+    _dev(pcand, torch.int64, "group_max(pcand)")
+    _dev(seg, torch.int32, "group_max(seg)")
+    _need(pcand.dim() == 2 and seg.dim() == 2 and seg.shape[0] == pcand.shape[0] and seg.shape[1] >= 1,
+          f"group_max: pcand [Q, ldp] and seg [Q, W + 1] expected, got {tuple(pcand.shape)} and {tuple(seg.shape)}")
+    Q, ldp, W = int(pcand.shape[0]), int(pcand.shape[1]), int(seg.shape[1]) - 1
+    _need(tuple(pscores.shape) == (Q, ldp), f"group_max(pscores): pcand is {(Q, ldp)} but the scores are {tuple(pscores.shape)}")
+    pcand, seg = pcand.contiguous(), seg.contiguous()
+    if cand_len is not None:
+        _dev(cand_len, torch.int32, "group_max(cand_len)")
+        _need(tuple(cand_len.shape) == (Q,), f"group_max(cand_len): expected shape {(Q,)}, got {tuple(cand_len.shape)}")
+    dev = pscores.device
+    if out is None:
+        out = alloc_plane(Q, W, pscores.dtype, dev)
+    if best is None:
+        best = alloc_plane(Q, W, torch.int64, dev)
+    _dev(out, pscores.dtype, "group_max(out)")
+    _dev(best, torch.int64, "group_max(best)")
+    _need(tuple(out.shape) == (Q, W) and tuple(best.shape) == (Q, W), f"group_max: out and best must be {(Q, W)}")
+    if Q == 0 or W == 0:
+        return out, best
+    ld_out = _same_ld(out, best)
+    fn = _lib.lib().fz_group_max_f32 if pscores.dtype == torch.float32 else _lib.lib().fz_group_max_f64
+    check(fn(_ptr(pscores), max(_ld(pscores), ldp), _ptr(pcand), ldp, _ptr(seg), _ptr(cand_len), W, Q, _ptr(out), _ptr(best), ld_out,
+             _stream(pscores)), "fz_group_max")
+    return out, best
+
+
 def gold_ranks(T: list[torch.Tensor], pos: torch.Tensor, weights: torch.Tensor, gold: torch.Tensor) -> torch.Tensor:
     """Fused ranks of the gold documents for every weight vector (N1, hybrid.py:404-426).
     T[s] [Q,N] normalised planes, pos [Q,N] int32 insertion positions (-1 absent), weights [W,S] fp32,

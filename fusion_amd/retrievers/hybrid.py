@@ -243,6 +243,15 @@ class Ranker:
         dev = index.Doff.device
         return index.rerank(model, qtok.to(dev), qlen.to(dev), candidates, k=return_topk, depth=depth)
 
+    @staticmethod
+    def collapse_passages(topk, groups, return_topk: int = None):
+        """Long documents (the systems above keep the reference's max_doc_length = 512 and lose a longer document's tail): split the corpus
+        with passages.split_passages, index and search the PASSAGES, then collapse.  `topk`: a passage-level planes.RankedTopk from any
+        corpus-scale search, `groups`: the passages.PassageGroups of the split.  -> (RankedTopk over DOCUMENT ids, best_passage [Q, k]
+        int64): every document at the rank and with the score of its best passage (MaxP), cut to return_topk -- what Aggregator.fuse_topk
+        joins with a BM25 list over the whole documents."""
+        return groups.collapse(topk, return_topk)
+
 
 def _pack_by_dicts(ranked_lists: dict):
     """The reference's own data flow, entry by entry (any hashable id): corpus position = first-seen order of the ids."""

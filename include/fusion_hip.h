@@ -468,6 +468,48 @@ int fz_lists_columns(const int64_t* const* ids_h, const int32_t* const* lens_h, 
                      const int32_t* ld_h, int S, int Q, const int64_t* gold_ids, int G, int64_t* out_ids, float* const* T_h,
                      int32_t* pos, int32_t* out_len, int32_t* gold_col, int ld_out, void* workspace, size_t workspace_bytes,
                      void* stream);
+/* (ABI 20, additive) PASSAGE lists to DOCUMENT lists, MaxP (csrc/lists_collapse.hip).  A long document is indexed as passages;
+ * passage id p + id_base belongs to document group_of[p] + doc_id_base (group_of device [P] int32, non-decreasing).
+ * Inputs, ONE list per query in (score desc, id asc) order, one row stride ld >= n for all three planes:
+ *   ids [Q][ld] int64, scores [Q][ld] fp32, scores64 [Q][ld] fp64 (nullable: BM25's raw scores), lens [Q] int32 clamped to [0, n];
+ *   slots past a row's length are never read.
+ * Outputs, per query, one row stride ld_out >= n; column c is the c-th DISTINCT document of the list, which in a ranked list is the
+ * MaxP ranking (a document's first occurrence is its best passage; equal scores keep list order):
+ *   out_ids [Q][ld_out] int64 the document id, out_scores (and out_scores64, given exactly when scores64 is) the score of the
+ *   entry that opened the column -- its own bits --, out_best [Q][ld_out] int64 that entry's passage id, out_len [Q] the number of
+ *   distinct documents.  From out_len on the rows hold (-1, -inf, -1) up to ld_out: the kernel defines every element of every
+ *   output row itself (no pre-fill is needed) and two calls give the same bytes.
+ * n <= fz_lists_max_entries(), FZ_ERR_UNSUPPORTED beyond.  Workspace: fz_lists_collapse_workspace_bytes(Q) device bytes; its first
+ * int32 is a FLAG WORD, zeroed by the call: bit 0 = a listed passage id outside [id_base, id_base + P), bit 1 = a row that is not
+ * non-increasing, !(s[r-1] >= s[r]) for some 1 <= r < len (NaN included; equal scores and -inf are fine).  With a bit set the
+ * outputs are unspecified, never out of bounds.  A repeated DOCUMENT is the normal case and sets nothing.
+ * Every argument is checked before the first HIP call.  Q == 0 or n == 0: FZ_OK, nothing launched, nothing written. */
+size_t fz_lists_collapse_workspace_bytes(int Q);
+int fz_lists_collapse(const int64_t* ids, const float* scores, const double* scores64, const int32_t* lens, int ld, int n, int Q,
+                      const int32_t* group_of, int64_t P, int64_t id_base, int64_t doc_id_base, int64_t* out_ids, float* out_scores,
+                      double* out_scores64, int64_t* out_best, int32_t* out_len, int ld_out, void* workspace,
+                      size_t workspace_bytes, void* stream);
+/* (ABI 20, additive) Exact MaxP score of candidate DOCUMENTS: expand, score the passages with any pair kernel, reduce.
+ * fz_group_expand: cand [Q][ld] int64 document ids (W per row, ld >= W), cand_len [Q] int32 (nullable = W), CSR poff device [D + 1]
+ * int64 (document d owns passages poff[d] .. poff[d + 1] - 1) ->
+ *   pcand [Q][ldp] int64   the passage ids (+ id_base), slot 0's passages first, then slot 1's, ...; -1 from pcand_len on;
+ *   seg   [Q][W + 1] int32 slot w's passages are pcand[q][seg[w] .. seg[w + 1] - 1];   pcand_len [Q] int32 = seg[q][W].
+ * A slot past cand_len, a negative id, an id outside [doc_id_base, doc_id_base + D) or a document without passages gets an empty
+ * segment.  A row that needs more than ldp slots sets the flag (first int32 of the workspace, fz_group_expand_workspace_bytes(Q)
+ * device bytes, zeroed by the call): its segments are cut at ldp, nothing is written out of bounds.
+ * fz_group_max_f32 / _f64: pscores [Q][ld_s] (ld_s >= ldp: the pair kernel's scores of pcand) ->
+ *   out [Q][ld_out] the maximum over slot w's segment, the winning entry's own bits; best [Q][ld_out] int64 (the same stride) the
+ *   passage id of the FIRST maximum (the lowest passage id among equals); (-inf, -1) for an empty segment and for w >= cand_len.
+ * Scores are finite or -inf (the pair kernels' contract).  Arguments are checked before the first HIP call; Q == 0 (or W == 0 for
+ * the maximum): FZ_OK, nothing launched. */
+size_t fz_group_expand_workspace_bytes(int Q);
+int fz_group_expand(const int64_t* cand, int ld, const int32_t* cand_len, int W, int Q, const int64_t* poff, int64_t D,
+                    int64_t id_base, int64_t doc_id_base, int64_t* pcand, int ldp, int32_t* seg, int32_t* pcand_len,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int fz_group_max_f32(const float* pscores, int ld_s, const int64_t* pcand, int ldp, const int32_t* seg, const int32_t* cand_len,
+                     int W, int Q, float* out, int64_t* best, int ld_out, void* stream);
+int fz_group_max_f64(const double* pscores, int ld_s, const int64_t* pcand, int ldp, const int32_t* seg, const int32_t* cand_len,
+                     int W, int Q, double* out, int64_t* best, int ld_out, void* stream);
 
 /* ---- A1: BM25 scoring on device, bm25.py:149-156 -------------------------------------- */
 /* scores[q][j] (fp64) = sum over query terms in query order of idf*tf*(k1+1)/(tf+k1*(1-b+b*dl/avgdl)).
