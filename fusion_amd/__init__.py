@@ -12,5 +12,6 @@ Layout (only what the encode -> score -> fuse hot path needs):
   encoders.py           PyTorch-ROCm transformer forwards (DPR mean-pool, SPLADE, ColBERT)
   distributed.py        corpus-sharded top-k with one RCCL all-gather
   passages.py           long documents: passage windows, passage lists -> document lists (MaxP)
+  feedback.py           pseudo-relevance feedback: coefficients from top-k lists, the multi-shard row gather
 """
 __version__ = "0.1.0"

@@ -62,6 +62,10 @@ _PROTOS = {
     "fz_sparse_fwd_pairs_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
     "fz_tfidf_doc_scores_fwd_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "fz_bm25_doc_scores_fwd_pv_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "fz_sparse_feedback_max_vocab": (_i, []),
+    "fz_sparse_feedback_f32": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, C.c_float, _i, _vp, _vp, _i, _i, _vp,
+                                    _vp, _vp]),
+    "fz_dense_feedback_f32": (_i, [_vp, _i, _vp, _i, _i, _i64, _i, _i64, _vp, _i, _vp, _vp, _i, _i, C.c_float, _vp, _i, _vp]),
     "fz_sort_max_n": (_i, []),
     "fz_sort_max_n_f64": (_i, []),
     "fz_sort_workspace_bytes": (_sz, [_i, _i, _i]),

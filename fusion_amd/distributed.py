@@ -225,6 +225,29 @@ class ShardedDenseIndex(_ShardedIndex):
         ids, cand_len = _candidates(candidates)
         return rank_pairs(ids, self.pair_scores(Qn, ids, cand_len), k)
 
+    def feedback(self, Qn: torch.Tensor, topk, *, fb_docs: int = 10, alpha: float = 1.0, beta: float = 1.0, weighting: str = "uniform",
+                 normalize: bool = True) -> torch.Tensor:
+        """Pseudo-relevance feedback: the queries moved towards the first fb_docs documents of their own lists (topk: a planes.RankedTopk
+        of a first search), q' = alpha * q + sum_r coef_r * d_r in list order (ops.dense_feedback; feedback.coefficients gives coef from
+        beta and `weighting`).  -> [Q, dim] float32, L2-normalised by ops.normalize_rows when `normalize`.  With more than one rank the
+        rows are gathered first (feedback.gather_rows): the result does not depend on the number of shards."""
+        from . import feedback as fb
+        fb_ids, fb_len, coef = fb.coefficients(topk, fb_docs, beta, weighting)
+        Dn = self.Dn[:, :Qn.shape[1]]                       # (a corpus matrix padded past the queries' width)
+        if fb._world(self.group) > 1:
+            rows, slots = fb.gather_rows(Dn, fb_ids, self.id_base, self.group)
+            out = ops.dense_feedback(Qn, rows, slots, fb_len, coef, alpha)
+        else:
+            out = ops.dense_feedback(Qn, Dn, fb_ids, fb_len, coef, alpha, id_base=self.id_base)
+        return ops.normalize_rows(out) if normalize else out
+
+    def search_feedback(self, Qn: torch.Tensor, k: int = 1000, *, mark=None, **feedback):
+        """search -> feedback -> search: the first pass's lists feed the queries back, the expanded queries are searched again.
+        -> planes.RankedTopk of the second pass.  **feedback: the keyword arguments of feedback()."""
+        from .planes import RankedTopk
+        first = RankedTopk.from_search(*self.search(Qn, k, mark=mark))
+        return RankedTopk.from_search(*self.search(self.feedback(Qn, first, **feedback), k, mark=mark))
+
 
 class ShardedSparseIndex(_ShardedIndex):
     """One rank's shard of a SPLADE corpus as an inverted index (ops.SparseIndex, documents 0 .. N-1 = global ids id_base ..) + the
@@ -272,6 +295,33 @@ class ShardedSparseIndex(_ShardedIndex):
         """As ShardedDenseIndex.rerank, for the queries' term lists."""
         ids, cand_len = _candidates(candidates)
         return rank_pairs(ids, self.pair_scores(qoff, qterms, qw, ids, cand_len), k)
+
+    def feedback(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, topk, *, fb_docs: int = 10, fb_terms: int = 32,
+                 alpha: float = 1.0, beta: float = 1.0, weighting: str = "uniform", normalize: bool = True):
+        """Pseudo-relevance feedback: the queries expanded from the first fb_docs documents of their own lists (topk: a planes.RankedTopk
+        of a first search).  q' = alpha * q + sum_r coef_r * d_r in list order over the shard's forward rows (ops.sparse_feedback); of the
+        terms the documents bring in, the fb_terms strongest are kept.  -> (qoff', qterms', qw') as search() takes them, L2-normalised
+        when `normalize`.  ValueError without build_forward() and for a vocabulary beyond ops.sparse_feedback_max_vocab().  With more
+        than one rank the rows are gathered first (feedback.gather_rows): the result does not depend on the number of shards."""
+        from . import feedback as fb
+        fwd = self.index.forward
+        if fwd is None:
+            raise ValueError("ShardedSparseIndex.feedback: the index has no forward index (build_forward())")
+        if self.index.V > ops.sparse_feedback_max_vocab():
+            raise ValueError(f"ShardedSparseIndex.feedback: V = {self.index.V} is beyond the kernel's accumulator "
+                             f"({ops.sparse_feedback_max_vocab()} terms, ops.sparse_feedback_max_vocab)")
+        fb_ids, fb_len, coef = fb.coefficients(topk, fb_docs, beta, weighting)
+        base = self.id_base
+        if fb._world(self.group) > 1:
+            fwd, fb_ids = fb.gather_rows(fwd, fb_ids, self.id_base, self.group)
+            base = 0
+        return ops.sparse_feedback(fwd, self.index.V, qoff, qterms, qw, fb_ids, fb_len, coef, alpha, fb_terms, id_base=base, normalize=normalize)
+
+    def search_feedback(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, k: int = 1000, *, mark=None, **feedback):
+        """search -> feedback -> search (see ShardedDenseIndex.search_feedback) -> planes.RankedTopk of the second pass."""
+        from .planes import RankedTopk
+        first = RankedTopk.from_search(*self.search(qoff, qterms, qw, k, mark=mark))
+        return RankedTopk.from_search(*self.search(*self.feedback(qoff, qterms, qw, first, **feedback), k, mark=mark))
 
 
 class ShardedLexicalIndex:

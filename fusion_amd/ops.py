@@ -2196,6 +2196,96 @@ def sparse_dot_pairs(index: SparseIndex, qoff: torch.Tensor, qterms: torch.Tenso
     return out
 
 
+# ---------------------------------------------------------------------------------------
+# pseudo-relevance feedback (csrc/feedback.hip)
+# ---------------------------------------------------------------------------------------
+def sparse_feedback_max_vocab() -> int:
+    """The largest vocabulary whose accumulator fz_sparse_feedback_f32 holds in LDS."""
+    return int(_lib.lib().fz_sparse_feedback_max_vocab())
+
+
+def _feedback_args(what: str, Q: int, fb_ids, fb_len, coef):
+    """The feedback lists of both kernels: fb_ids [Q, F] int64 and coef [Q, F] float32 (rows may be strided), fb_len [Q] int32 or None."""
+    _dev(fb_ids, torch.int64, f"{what}(fb_ids)")
+    _dev(coef, torch.float32, f"{what}(coef)")
+    _need(fb_ids.dim() == 2 and fb_ids.shape[0] == Q, f"{what}: fb_ids must be [Q = {Q}, F], got {tuple(fb_ids.shape)}")
+    _need(tuple(coef.shape) == tuple(fb_ids.shape), f"{what}(coef): fb_ids are {tuple(fb_ids.shape)} but coef {tuple(coef.shape)}")
+    if fb_len is not None:
+        _dev(fb_len, torch.int32, f"{what}(fb_len)")
+        _need(tuple(fb_len.shape) == (Q,), f"{what}(fb_len): expected shape {(Q,)}, got {tuple(fb_len.shape)}")
+        fb_len = fb_len.contiguous()
+    return fb_len, int(fb_ids.shape[1])
+
+
+def sparse_feedback(forward: SparseForward, V: int, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, fb_ids: torch.Tensor,
+                    fb_len: torch.Tensor | None, coef: torch.Tensor, alpha: float, m: int, *, id_base: int = 0, normalize: bool = False):
+    """Rocchio expansion of weighted sparse queries from feedback documents (fz_sparse_feedback_f32): q' = alpha * q + sum_r coef[q, r] *
+    d_r over the slots r < fb_len[q] whose id is one of the forward index's documents (id_base ..), in slot order; of the terms the
+    documents bring in, the m with the largest sums are kept (ties: the lower term), the query's own terms always.  One rounding per
+    product and per add: the bits are defined (include/fusion_hip.h states the arithmetic).  The queries as sparse_rows gives them,
+    forward a SparseForward over V terms, fb_ids [Q, F] int64, fb_len [Q] int32 or None, coef [Q, F] float32.
+    -> (qoff', qterms', qw') in the same form; normalize=True: qw' L2-normalised per query (normalize_rows over the padded rows).
+    One host read for the row width (the longest query + m, at most V) and one of the kernel's flag word; ValueError for V beyond
+    sparse_feedback_max_vocab()."""
+    if not isinstance(forward, SparseForward):
+        raise TypeError(f"sparse_feedback(forward): expected an ops.SparseForward, got {type(forward).__name__}")
+    Q = _sparse_queries(qoff, qterms, qw, "sparse_feedback")
+    fb_len, F = _feedback_args("sparse_feedback", Q, fb_ids, fb_len, coef)
+    V, m = int(V), int(m)
+    _need(m >= 0, f"sparse_feedback: m = {m} must not be negative")
+    _need(1 <= V <= sparse_feedback_max_vocab(),
+          f"sparse_feedback: V = {V} is outside 1 .. {sparse_feedback_max_vocab()}, the accumulator the kernel holds (sparse_feedback_max_vocab)")
+    _need(forward.V <= V, f"sparse_feedback: the forward index is over {forward.V} terms, more than V = {V}")
+    _dev(forward.foff, torch.int64, "sparse_feedback(forward.foff)")
+    _dev(forward.rows, torch.int32, "sparse_feedback(forward.rows)")
+    _need(forward.foff.is_contiguous() and forward.foff.numel() == forward.N + 1 and forward.rows.is_contiguous(),
+          "sparse_feedback: forward.foff must be a contiguous [N + 1] tensor and forward.rows contiguous")
+    dev = qoff.device
+    nq_max = int((qoff[1:] - qoff[:-1]).max().item()) if Q > 0 else 0      # the one host read of the plan
+    width = min(nq_max + m, V)                                             # (a row holds at most V terms)
+    out_terms = alloc_plane(Q, width, torch.int32, dev)
+    out_w = alloc_plane(Q, width, torch.float32, dev)
+    out_len = torch.zeros(Q, dtype=torch.int32, device=dev)
+    if Q > 0:
+        flag = torch.empty(4, dtype=torch.uint8, device=dev)
+        check(_lib.lib().fz_sparse_feedback_f32(_ptr(forward.foff), _ptr(forward.rows), V, forward.N, int(id_base), _ptr(qoff), _ptr(qterms),
+                                                _ptr(qw), Q, _ptr(fb_ids), max(_ld(fb_ids), F), _ptr(fb_len), _ptr(coef), max(_ld(coef), F),
+                                                F, float(alpha), m, _ptr(out_terms), _ptr(out_w), _same_ld(out_terms, out_w), width,
+                                                _ptr(out_len), _ptr(flag), _stream(qoff)), "fz_sparse_feedback_f32")
+        if _flag_word(flag) & 1:
+            raise ValueError(f"sparse_feedback: an expanded query does not fit {width} terms (query terms out of order or repeated?)")
+    if normalize and Q > 0 and width > 0:
+        out_w = normalize_rows(out_w)[:, :width]                           # the padding is +0.0: the norm of the expanded query
+    kept = out_terms >= 0
+    noff = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+    noff[1:] = torch.cumsum(out_len, 0)
+    return noff, out_terms[kept].contiguous(), out_w[kept].contiguous()
+
+
+def dense_feedback(Qn: torch.Tensor, Dn: torch.Tensor, fb_ids: torch.Tensor, fb_len: torch.Tensor | None, coef: torch.Tensor, alpha: float, *,
+                   id_base: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Rocchio for dense queries (fz_dense_feedback_f32): out[q] = alpha * Qn[q], then + coef[q, r] * Dn[fb_ids[q, r] - id_base] slot
+    after slot with sparse_feedback's slot rules, one rounding per product and per add.  Qn [Q, dim], Dn [N, dim] float32 (any row
+    stride), fb_ids [Q, F] int64, fb_len [Q] int32 or None, coef [Q, F] float32 -> [Q, dim] float32, not normalised (normalize_rows)."""
+    _dev(Qn, torch.float32, "dense_feedback(Qn)")
+    _dev(Dn, torch.float32, "dense_feedback(Dn)")
+    _need(Qn.dim() == 2 and Dn.dim() == 2, "dense_feedback: Qn [Q, dim] and Dn [N, dim] expected")
+    if Qn.shape[1] != Dn.shape[1]:
+        raise ValueError(f"embedding dims differ: {Qn.shape[1]} vs {Dn.shape[1]}")
+    Q, N, dim = int(Qn.shape[0]), int(Dn.shape[0]), int(Qn.shape[1])
+    _need(dim >= 1, "dense_feedback: dim must be at least 1")
+    fb_len, F = _feedback_args("dense_feedback", Q, fb_ids, fb_len, coef)
+    if out is None:
+        out = alloc_plane(Q, dim, torch.float32, Qn.device)
+    else:
+        _dev(out, torch.float32, "dense_feedback(out)")
+        _need(tuple(out.shape) == (Q, dim), f"dense_feedback(out): expected shape {(Q, dim)}, got {tuple(out.shape)}")
+    check(_lib.lib().fz_dense_feedback_f32(_ptr(Qn), max(_ld(Qn), dim), _ptr(Dn), max(_ld(Dn), dim), Q, N, dim, int(id_base), _ptr(fb_ids),
+                                           max(_ld(fb_ids), F), _ptr(fb_len), _ptr(coef), max(_ld(coef), F), F, float(alpha), _ptr(out),
+                                           max(_ld(out), dim), _stream(Qn)), "fz_dense_feedback_f32")
+    return out
+
+
 def sparse_cos_scores(Qe: torch.Tensor, index: SparseIndex, max_query_density: float = 0.05) -> torch.Tensor:
     """Cosine scores of dense query vectors Qe [Q, >= V] against a SparseIndex (whose rows were normalised before indexing).  Queries that are
     not sparse themselves (an untrained head activates half the vocabulary: one barrier per term and query) take the dense GEMM against the

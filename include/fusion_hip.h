@@ -773,6 +773,40 @@ int fz_bm25_doc_scores_fwd_pv_f64(const int64_t* toff, const int32_t* pdoc, cons
                                   const int32_t* fpos, const int64_t* qoff, const int32_t* qterms, int Q, int N, const int32_t* docs, int G,
                                   double* out, void* stream);
 
+/* ---- pseudo-relevance feedback: query expansion from top-k lists (csrc/feedback.hip; ABI 20, additive) -------------------------------------
+ * Rocchio: q' = alpha * q + sum_r coef[q][r] * d_r over the feedback slots r = 0 .. F-1 of query q, IN SLOT ORDER.  fb_ids [Q][ldf] int64
+ * global ids, fb_len [Q] int32 (NULL: F for every query; clamped to [0, F]), coef [Q][ldc] float32, id_base = global id of this index's
+ * document 0 (any int64).  A slot is SKIPPED when r >= fb_len[q], fb_ids[q][r] < id_base or fb_ids[q][r] >= id_base + N; the same document
+ * in two slots is added twice.  Every product and every add is rounded to float32 once, nothing is fused, and the contributions to one term
+ * (dimension) are added in slot order: the bits are defined and two calls give the same bytes.  Weights are finite by contract.
+ * fz_sparse_feedback_f32: queries as weighted sparse rows (qoff [Q + 1] int64, qterms int32 unique and ascending inside [0, V), qw float32),
+ * documents as the forward rows of fz_sparse_fwd_pairs_f32 (foff [N + 1], rows of 8-byte {int32 term, float32 weight}, terms unique in a row).
+ *   1. acc[t] = +0.0 for all t; per query term (t, w): acc[t] = acc[t] + alpha * w, t marked a QUERY term;
+ *   2. per counted slot, per posting (t, w) of its document: acc[t] = acc[t] + coef[q][r] * w, t marked TOUCHED;
+ *   3. the candidates are the touched terms that are no query terms (a sum that came out as 0 included), ranked by desc_key_f32(acc[t])
+ *      ascending -- larger sums first, -0.0 == +0.0 --, ties by ascending term; the first min(m, #candidates) are kept;
+ *   4. out_terms [Q][ldo] int32 / out_w [Q][ldo] float32: the query terms and the kept candidates in ascending term order with their
+ *      acc[t] bits, out_len[q] of them; columns out_len[q] .. width-1 hold (-1, +0.0).  The kernel writes all `width` columns of every
+ *      row and nothing else (no pre-fill is needed).  A row that does not fit `width` is cut there and raises bit 0 of *flag (a device
+ *      int32 the call zeroes first).
+ *   One workgroup per query; the accumulator is a float32 array over the vocabulary in LDS: V <= fz_sparse_feedback_max_vocab() = 32,768.
+ *   Checks, all before the first HIP call: a negative Q / N / F / m / width, ldf < F, ldc < F, ldo < width, V <= 0, V beyond the cap, or
+ *   (Q > 0) a null pointer among qoff, out_len, flag, fb_ids / coef (F > 0), out_terms / out_w (width > 0), foff (F > 0 and N > 0)
+ *   -> FZ_ERR_ARG; rows not 8-byte aligned -> FZ_ERR_UNSUPPORTED; Q == 0 -> FZ_OK, nothing launched, nothing written.
+ * fz_dense_feedback_f32: out[q][j] = alpha * Qn[q][j], then per counted slot out[q][j] = out[q][j] + coef[q][r] * Dn[d][j]; Qn [Q][ldq],
+ *   Dn [N][ldd], out [Q][ldo] float32, j < dim (columns dim .. ldo-1 are left untouched); not normalised.  Any strides and alignments are
+ *   taken (16-byte vector accesses where ldq, ldd, ldo are multiples of 4 and the three pointers 16-byte aligned).  Checks: a negative
+ *   Q / N / F, dim <= 0, ldf < F, ldc < F, ldq / ldd / ldo < dim, or (Q > 0) a null pointer among Qn, out, fb_ids / coef (F > 0),
+ *   Dn (F > 0 and N > 0) -> FZ_ERR_ARG; Q == 0 -> FZ_OK.  No workspace, no atomics, no host synchronisation. */
+int fz_sparse_feedback_max_vocab(void);
+int fz_sparse_feedback_f32(const int64_t* foff, const void* rows, int V, int64_t N, int64_t id_base, const int64_t* qoff, const int32_t* qterms,
+                           const float* qw, int Q, const int64_t* fb_ids, int ldf, const int32_t* fb_len, const float* coef, int ldc, int F,
+                           float alpha, int m, int32_t* out_terms, float* out_w, int ldo, int width, int32_t* out_len, int32_t* flag,
+                           void* stream);
+int fz_dense_feedback_f32(const float* Qn, int ldq, const float* Dn, int ldd, int Q, int64_t N, int dim, int64_t id_base,
+                          const int64_t* fb_ids, int ldf, const int32_t* fb_len, const float* coef, int ldc, int F, float alpha, float* out,
+                          int ldo, void* stream);
+
 /* ---- cross-encoder pairs assembled from token ids (csrc/crosspack.hip; ABI 20, additive) ---------------------------------------------------
  * The monoBERT rerank (hybrid.py:139-163) over top-k lists: the pair rows "<s> q </s></s> d </s>" of the packed forward are built on the
  * device from the queries' token ids and a token store of the corpus, sharded by document: tok [sumL] int32, Doff [N + 1] int64 (document d
