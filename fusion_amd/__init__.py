@@ -3,7 +3,7 @@ surface of maastrichtlawtech/fusion (Ranker / Aggregator / run_hybrid.sh).
 
 Layout (only what the encode -> score -> fuse hot path needs):
   csrc/                 hand-written HIP kernels for gfx950 + the C ABI (include/fusion_hip.h)
-  _lib.py               ctypes binding of libfusion_hip.so (raises if the library is missing)
+  _lib.py               ctypes binding of libfusion_hip.so, its table parsed from the header (raises if the library is missing)
   ops.py                torch-tensor wrappers: device pointers + current HIP stream -> C ABI
   planes.py             device-resident ranked lists (dense planes by corpus position)
   retrievers/hybrid.py  Ranker, Aggregator, run_evaluation, main()  (mirror of the reference module)

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -36,140 +37,57 @@ def build(force: bool = False) -> str:
 
 _lib = None
 
-_vp, _i, _i64, _sz, _d = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_double
-_PROTOS = {
-    "fz_strerror": (C.c_char_p, [_i]),
-    "fz_last_hip_error": (_i, []),
-    "fz_abi_version": (_i, []),
-    "fz_normalize_rows_f32": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
-    "fz_dot_scores_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "fz_dot_scores_filter_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "fz_dot_scores_plan": (_i, [_i, _i, _i, _i, _i, _vp]),
-    "fz_dot_topn_max": (_i, []),
-    "fz_dot_topn_workspace_bytes": (_sz, [_i, _i, _i]),
-    "fz_dot_topn_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "fz_maxsim_f16": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    "fz_maxsim_pairs_f16": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
-    "fz_quantize_e4m3_f16": (_i, [_vp, _i64, _i, _vp, _vp]),
-    "fz_maxsim_e4m3": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    "fz_maxsim_pairs_e4m3": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
-    "fz_residual_compress_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
-    "fz_residual_decompress_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp]),
-    "fz_maxsim_pairs_residual_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
-    "fz_dot_pairs_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
-    "fz_sparse_dot_pairs_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
-    "fz_sparse_fwd_max_vocab": (_i, []),
-    "fz_sparse_fwd_pairs_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
-    "fz_tfidf_doc_scores_fwd_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
-    "fz_bm25_doc_scores_fwd_pv_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
-    "fz_sparse_feedback_max_vocab": (_i, []),
-    "fz_sparse_feedback_f32": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, C.c_float, _i, _vp, _vp, _i, _i, _vp,
-                                    _vp, _vp]),
-    "fz_dense_feedback_f32": (_i, [_vp, _i, _vp, _i, _i, _i64, _i, _i64, _vp, _i, _vp, _vp, _i, _i, C.c_float, _vp, _i, _vp]),
-    "fz_sort_max_n": (_i, []),
-    "fz_sort_max_n_f64": (_i, []),
-    "fz_sort_workspace_bytes": (_sz, [_i, _i, _i]),
-    "fz_sort_bucket_rank_rows": (_i, [_vp, _i]),
-    "fz_sort_zero_compact_rows": (_i, [_vp, _i]),
-    "fz_sort_rows_desc_lexical": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "fz_sort_rows_desc": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "fz_sort_rows_desc_placed": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "fz_sort_rank_fused_workspace_bytes": (_sz, [_i, _i, _i]),
-    "fz_sort_rank_fused_desc": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "fz_rrf_terms_f64": (_i, [_i, _i, _vp, _vp]),
-    "fz_select_topk_f": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "fz_fuse_rank_f64": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "fz_row_stats_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "fz_rank_to_bitmap": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
-    "fz_fuse_nsf_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
-    "fz_fuse_nsf_stats_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "fz_fuse_nsf_pstats_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "fz_nsf_tables_workspace_bytes": (_sz, [_i, _vp, _i]),
-    "fz_nsf_tables_header_offset": (_sz, [_i, _vp, _i, _i]),
-    "fz_nsf_tables_prepare": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
-    "fz_fuse_nsf_tables_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
-    "fz_nsf_tables_path": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "fz_zero_unlisted_f32": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "fz_minmax_from_orders_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "fz_minmax_from_order_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "fz_fuse_none_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "fz_fuse_wsum_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "fz_insertion_order_workspace_bytes": (_sz, [_i, _i]),
-    "fz_insertion_order": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "fz_lists_max_entries": (_i, []),
-    "fz_lists_join_workspace_bytes": (_sz, [_i, _i]),
-    "fz_lists_join": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
-    "fz_lists_columns_workspace_bytes": (_sz, [_i, _i]),
-    "fz_lists_columns": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
-    "fz_lists_collapse_workspace_bytes": (_sz, [_i]),
-    "fz_lists_collapse": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
-    "fz_group_expand_workspace_bytes": (_sz, [_i]),
-    "fz_group_expand": (_i, [_vp, _i, _vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "fz_group_max_f32": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
-    "fz_group_max_f64": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
-    "fz_topk_max_k": (_i, []),
-    "fz_topk_rows_plan": (_i, [_i, _i, _vp]),
-    "fz_topk_fold_max_k": (_i, [_i]),
-    "fz_topk_workspace_bytes": (_sz, [_i, _i, _i]),
-    "fz_topk_rows_f32": (_i, [_vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
-    "fz_topk_update_workspace_bytes": (_sz, [_i, _i, _i]),
-    "fz_topk_update_f32": (_i, [_vp, _i, _i, _i, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "fz_topk_filter_append_f32": (_i, [_vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "fz_topk_fold_workspace_bytes": (_sz, [_i, _i, _i]),
-    "fz_topk_fold_f32": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "fz_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "fz_topk_allgather_workspace_bytes": (_sz, [_i, _i, _i]),
-    "fz_topk_allgather": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "fz_bm25_doc_norms_f64": (_i, [_vp, _i, _d, _d, _d, _vp, _vp]),
-    "fz_bm25_slice_docs": (_i, []),
-    "fz_bm25_slice_offsets": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
-    "fz_bm25_scores_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _vp, _vp, _i, _i, _vp, _i, _vp]),
-    "fz_bm25_scores_f64_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp]),
-    "fz_bm25_posting_values_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _d, _vp, _vp]),
-    "fz_bm25_scores_pv_f64_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp]),
-    "fz_tfidf_scores_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp]),
-    "fz_tune_max_gold": (_i, []),
-    "fz_gold_ranks_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "fz_gold_ranks_f64w": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "fz_tune_metrics_f64": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "fz_sparse_slice_docs": (_i, []),
-    "fz_sparse_slice_offsets": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
-    "fz_sparse_dot_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
-    "fz_sparse_dot_range_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "fz_sparse_dot_filter_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "fz_lexical_slice_docs": (_i, [_i]),
-    "fz_bm25_scores_range_pv_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "fz_tfidf_scores_range_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "fz_bm25_filter_pv_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "fz_tfidf_filter_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "fz_bm25_doc_scores_pv_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
-    "fz_tfidf_doc_scores_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
-    "fz_bm25_count_pv_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _i, _vp, _vp]),
-    "fz_tfidf_count_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _i, _vp, _vp]),
-    "fz_centroid_slice_docs": (_i, []),
-    "fz_centroid_slice_offsets": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
-    "fz_centroid_scores_range_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    "fz_centroid_scores_filter_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "fz_pair_max_sep": (_i, []),
-    "fz_pair_plan": (_i, [_vp, _i, _vp, _i, _i, _i64, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "fz_pair_fill": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "fz_attn_varlen_f32": (_i, [_vp, _i, _vp, _i, _i, _i, C.c_float, _vp, _i, _vp]),
-    "fz_add_layernorm_f32": (_i, [_vp, _i, _vp, _i, _vp, _vp, C.c_float, _i, _i, _vp, _i, _vp]),
-    "fz_gelu_f32": (_i, [_vp, _vp, _sz, _vp]),
-    "fz_attn_varlen_f16": (_i, [_vp, _i, _vp, _i, _i, _i, C.c_float, _vp, _i, _vp]),
-    "fz_attn_varlen_f16_amp": (_i, [_vp, _i, _vp, _i, _i, _i, C.c_float, _vp, _i, _vp]),
-    "fz_add_layernorm_x16": (_i, [_vp, _i, _vp, _i, _vp, _vp, C.c_float, _i, _i, _vp, _i, _vp, _i, _vp]),
-    "fz_gelu_f16": (_i, [_vp, _vp, _sz, _vp]),
-    "fz_embed_layernorm_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _i, _i, _vp, _i, _vp]),
-    "fz_segment_mean_f32": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp]),
-    "fz_segment_splade_max_f32": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp]),
-    "fz_splade_head_max_f32": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "fz_splade_head_max_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "fz_splade_head_f16_tile": (_i, [_vp, _vp, _vp, _vp]),
-    "fz_fill_i32": (_i, [_vp, _sz, C.c_int32, _vp]),
-    "fz_f64_to_f32": (_i, [_vp, _vp, _sz, _vp]),
-}
-EXPORTS = tuple(_PROTOS)
+_HEADER = os.path.join(_HERE, os.pardir, "include", "fusion_hip.h")
+_RESTYPES = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
+_BY_VALUE = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "double": C.c_double, "float": C.c_float}
+_PROTO = re.compile(r"(?:^|[;{}])\s*(int|size_t|const\s+char\s*\*)\s*(fz_\w+)\s*\(([^()]*)\)\s*(?=;)")
+
+
+def _strip_header(text: str) -> str:
+    """The header without /* */ and // comments and without preprocessor lines (none of them is continued with a backslash)."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    return re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
+
+
+def parse_prototypes(text: str) -> dict:
+    """name -> (restype, [argtypes]) of every `T fz_name(args);` of a C header, T one of _RESTYPES.  It never guesses: a by-value type outside
+    _BY_VALUE raises ImportError, and so does an `fz_name(` that is no such declaration."""
+    text = _strip_header(text)
+    protos = {}
+    for ret, name, params in _PROTO.findall(text):
+        params, args = " ".join(params.split()), []
+        for prm in ([] if params in ("void", "") else params.split(",")):
+            by_value = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s+\w+\s*", prm)
+            if "*" in prm or "[" in prm:
+                args.append(C.c_void_p)
+            elif by_value and by_value.group(1) in _BY_VALUE:
+                args.append(_BY_VALUE[by_value.group(1)])
+            else:
+                raise ImportError(f"fusion_hip.h: unknown by-value parameter {prm.strip()!r} in `{name}({params});`")
+        protos[name] = (_RESTYPES[" ".join(ret.split()).replace(" *", "*")], args)
+    for m in re.finditer(r"\b(fz_\w+)\s*\(", text):
+        if m.group(1) not in protos:
+            line = text[text.rfind("\n", 0, m.start()) + 1:].split("\n", 1)[0].strip()
+            raise ImportError(f"fusion_hip.h: `{line}` names {m.group(1)}( but is no prototype this binding can read")
+    return protos
+
+
+def _table() -> dict:
+    """_PROTOS: the binding table IS the header, parsed once per process on first use, so a prototype cannot drift from its ctypes signature
+    (importing this module for build() or its constants reads no header)."""
+    if "_PROTOS" not in globals():
+        with open(_HEADER, encoding="utf-8") as f:
+            protos = parse_prototypes(f.read())
+        globals().update(_PROTOS=protos, EXPORTS=tuple(protos))
+    return globals()["_PROTOS"]
+
+
+def __getattr__(name):      # _lib._PROTOS and _lib.EXPORTS before the first lib()
+    if name in ("_PROTOS", "EXPORTS"):
+        _table()
+        return globals()[name]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def lib() -> C.CDLL:
@@ -187,7 +105,7 @@ def lib() -> C.CDLL:
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOS.items():
+        for name, (res, args) in _table().items():
             f = getattr(L, name)  # AttributeError if the library does not export what the header declares
             f.restype, f.argtypes = res, args
         v = L.fz_abi_version()

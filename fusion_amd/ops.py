@@ -80,6 +80,21 @@ def _max_systems(S: int, what: str):
     _need(S <= MAX_SYSTEMS, f"{what}: {S} systems, but fusion takes at most {MAX_SYSTEMS} (FZ_MAX_SYSTEMS)")
 
 
+def _contiguous(what: str, *typed):
+    """Every (tensor, dtype, name) is a contiguous device tensor of its dtype: the flat arrays an index or a query batch is made of."""
+    for t, dt, name in typed:
+        _need(_dev(t, dt, f"{what}({name})").is_contiguous(), f"{what}({name}) must be contiguous")
+
+
+def _out(what: str, out, shape: tuple, dtype, dev, plane: bool) -> torch.Tensor:
+    """An op's `out`: None -> a new tensor of this shape (a padded plane, or plain rows); a caller's -> checked to be one of this shape."""
+    if out is None:
+        return alloc_plane(*shape, dtype, dev) if plane else torch.empty(shape, dtype=dtype, device=dev)
+    _dev(out, dtype, f"{what}(out)")
+    _need(tuple(out.shape) == shape, f"{what}(out): expected shape {shape}, got {tuple(out.shape)}")
+    return out
+
+
 def _same_shape(ts, what: str):
     shapes = {tuple(t.shape) for t in ts if t is not None}
     _need(len(shapes) <= 1, f"{what}: planes differ in shape: {sorted(shapes)}")
@@ -174,11 +189,7 @@ def dot_scores(Qn: torch.Tensor, Dn: torch.Tensor, out: torch.Tensor | None = No
     if Qn.shape[1] != Dn.shape[1]:
         raise ValueError(f"embedding dims differ: {Qn.shape[1]} vs {Dn.shape[1]}")
     Q, N, d = Qn.shape[0], Dn.shape[0], Qn.shape[1]
-    if out is None:
-        out = alloc_plane(Q, N, torch.float32, Qn.device)
-    else:
-        _dev(out, torch.float32, "dot_scores(out)")
-        _need(tuple(out.shape) == (Q, N), f"dot_scores(out): expected shape {(Q, N)}, got {tuple(out.shape)}")
+    out = _out("dot_scores", out, (Q, N), torch.float32, Qn.device, plane=True)
     check(_lib.lib().fz_dot_scores_f32(_ptr(Qn), Qn.stride(0) if Q > 1 else d, _ptr(Dn), Dn.stride(0) if N > 1 else d, Q, N, d,
                                        _ptr(out), _ld(out), _stream(Qn)), "fz_dot_scores_f32")
     return out
@@ -226,12 +237,7 @@ def _pairs_args(what: str, Q: int, dev, cand: torch.Tensor, cand_len, out):
     if cand_len is not None:
         _dev(cand_len, torch.int32, f"{what}(cand_len)")
         _need(tuple(cand_len.shape) == (Q,), f"{what}(cand_len): expected shape {(Q,)}, got {tuple(cand_len.shape)}")
-    if out is None:
-        out = alloc_plane(Q, W, torch.float32, dev)
-    else:
-        _dev(out, torch.float32, f"{what}(out)")
-        _need(tuple(out.shape) == (Q, W), f"{what}(out): expected shape {(Q, W)}, got {tuple(out.shape)}")
-    return cand_len, out, W
+    return cand_len, _out(what, out, (Q, W), torch.float32, dev, plane=True), W
 
 
 def dot_pairs(Qn: torch.Tensor, Dn: torch.Tensor, cand: torch.Tensor, cand_len: torch.Tensor | None = None, *, id_base: int = 0,
@@ -257,25 +263,42 @@ def dot_pairs(Qn: torch.Tensor, Dn: torch.Tensor, cand: torch.Tensor, cand_len: 
 # ---------------------------------------------------------------------------------------
 # K2 MaxSim
 # ---------------------------------------------------------------------------------------
+def _token_queries(what: str, Qtok: torch.Tensor, Doff: torch.Tensor, e4m3: bool = False):
+    """The query side of the token-store contract, the element type its parameter (float16, or e4m3 bytes: then the tensor is called Q8):
+    Qtok [Q, Lq, dim], Doff [N + 1] int64.  -> (Qtok, Doff, (Q, Lq, dim, N)), contiguous."""
+    name = "Q8" if e4m3 else "Qtok"
+    Qtok = _e4m3_bytes(Qtok, f"{what}({name})") if e4m3 else _dev(Qtok, torch.float16, f"{what}({name})")
+    _dev(Doff, torch.int64, f"{what}(Doff)")
+    _need(Qtok.dim() == 3, f"{what}: {name} must be [Q, Lq, dim]")
+    Qtok, Doff = Qtok.contiguous(), Doff.contiguous()
+    Q, Lq, dim = Qtok.shape
+    N = Doff.numel() - 1
+    _need(N >= 0, f"{what}: Doff must hold N + 1 offsets")
+    return Qtok, Doff, (Q, Lq, dim, N)
+
+
+def _token_rows(what: str, Dtok: torch.Tensor, dim: int, e4m3: bool = False) -> torch.Tensor:
+    """The document side: Dtok [sumL, dim] of the same element type (D8 for e4m3 bytes), packed.  -> Dtok, contiguous."""
+    name = "D8" if e4m3 else "Dtok"
+    Dtok = (_e4m3_bytes(Dtok, f"{what}({name})") if e4m3 else _dev(Dtok, torch.float16, f"{what}({name})")).contiguous()
+    _need(Dtok.dim() == 2 and Dtok.shape[1] == dim, f"{what}: {name} must be [sumL, {dim}]")
+    return Dtok
+
+
+def _measured_doc_len(Doff: torch.Tensor, N: int) -> int:
+    """max_doc_len's default: the longest document of Doff, at least 1 (one small D2H read)."""
+    return max(int((Doff[1:] - Doff[:-1]).max().item()), 1) if N > 0 else 1
+
+
 def maxsim(Qtok: torch.Tensor, Dtok: torch.Tensor, Doff: torch.Tensor, out: torch.Tensor | None = None,
            max_doc_len: int | None = None) -> torch.Tensor:
     """Exact ColBERT late interaction. Qtok [Q,Lq,128] f16, Dtok [sumL,128] f16 packed, Doff [N+1] int64.
     max_doc_len: upper bound of the document lengths (default: measured from Doff, one small D2H read)."""
-    _dev(Qtok, torch.float16, "maxsim(Qtok)")
-    _dev(Dtok, torch.float16, "maxsim(Dtok)")
-    _dev(Doff, torch.int64, "maxsim(Doff)")
-    Qtok, Dtok, Doff = Qtok.contiguous(), Dtok.contiguous(), Doff.contiguous()
-    Q, Lq, dim = Qtok.shape
-    N = Doff.numel() - 1
-    _need(Dtok.dim() == 2 and Dtok.shape[1] == dim, f"maxsim: Dtok must be [sumL, {dim}]")
-    _need(N >= 0, "maxsim: Doff must hold N + 1 offsets")
-    if out is None:
-        out = alloc_plane(Q, N, torch.float32, Qtok.device)
-    else:
-        _dev(out, torch.float32, "maxsim(out)")
-        _need(tuple(out.shape) == (Q, N), f"maxsim(out): expected shape {(Q, N)}, got {tuple(out.shape)}")
+    Qtok, Doff, (Q, Lq, dim, N) = _token_queries("maxsim", Qtok, Doff)
+    Dtok = _token_rows("maxsim", Dtok, dim)
+    out = _out("maxsim", out, (Q, N), torch.float32, Qtok.device, plane=True)
     if max_doc_len is None:
-        max_doc_len = max(int((Doff[1:] - Doff[:-1]).max().item()), 1) if N > 0 else 1
+        max_doc_len = _measured_doc_len(Doff, N)
     check(_lib.lib().fz_maxsim_f16(_ptr(Qtok), _ptr(Dtok), _ptr(Doff), int(Dtok.shape[0]), int(max_doc_len), Q, Lq, N, dim, _ptr(out),
                                    _ld(out), _stream(Qtok)), "fz_maxsim_f16")
     return out
@@ -336,39 +359,23 @@ def maxsim_e4m3(Q8: torch.Tensor, D8: torch.Tensor, Doff: torch.Tensor, *, q_exp
     """ops.maxsim over e4m3 token bytes (fz_maxsim_e4m3): the exact MaxSim of the dequantised tokens, Q8 [Q, Lq, 128] and D8 [sumL, 128]
     uint8 (or torch.float8_e4m3fn) as quantize_e4m3 wrote them with q_exp and d_exp.  Every dot product is accumulated in float32 on the
     16x16x128 block-scaled MFMA; the finished sum is multiplied by 2^-(q_exp + d_exp)."""
-    Q8 = _e4m3_bytes(Q8, "maxsim_e4m3(Q8)")
-    D8 = _e4m3_bytes(D8, "maxsim_e4m3(D8)")
-    _dev(Doff, torch.int64, "maxsim_e4m3(Doff)")
     q_exp, d_exp = _e4m3_exp(q_exp, "maxsim_e4m3(q_exp)"), _e4m3_exp(d_exp, "maxsim_e4m3(d_exp)")
-    _need(Q8.dim() == 3, "maxsim_e4m3: Q8 must be [Q, Lq, dim]")
-    Q8, D8, Doff = Q8.contiguous(), D8.contiguous(), Doff.contiguous()
-    Q, Lq, dim = Q8.shape
-    N = Doff.numel() - 1
-    _need(D8.dim() == 2 and D8.shape[1] == dim, f"maxsim_e4m3: D8 must be [sumL, {dim}]")
-    _need(N >= 0, "maxsim_e4m3: Doff must hold N + 1 offsets")
-    if out is None:
-        out = alloc_plane(Q, N, torch.float32, Q8.device)
-    else:
-        _dev(out, torch.float32, "maxsim_e4m3(out)")
-        _need(tuple(out.shape) == (Q, N), f"maxsim_e4m3(out): expected shape {(Q, N)}, got {tuple(out.shape)}")
+    Q8, Doff, (Q, Lq, dim, N) = _token_queries("maxsim_e4m3", Q8, Doff, e4m3=True)
+    D8 = _token_rows("maxsim_e4m3", D8, dim, e4m3=True)
+    out = _out("maxsim_e4m3", out, (Q, N), torch.float32, Q8.device, plane=True)
     if max_doc_len is None:
-        max_doc_len = max(int((Doff[1:] - Doff[:-1]).max().item()), 1) if N > 0 else 1
+        max_doc_len = _measured_doc_len(Doff, N)
     _need(int(max_doc_len) >= 1, f"maxsim_e4m3: max_doc_len = {max_doc_len} must be positive")
     check(_lib.lib().fz_maxsim_e4m3(_ptr(Q8), _ptr(D8), _ptr(Doff), int(D8.shape[0]), int(max_doc_len), Q, Lq, N, dim, q_exp + d_exp,
                                     _ptr(out), _ld(out), _stream(Q8)), "fz_maxsim_e4m3")
     return out
 
 
-def _maxsim_pairs_args(what: str, Qtok: torch.Tensor, Doff: torch.Tensor, cand: torch.Tensor, cand_len, out, max_doc_len):
-    """What the two candidate-list MaxSim ops check whatever the token rows are stored as: Qtok [Q, Lq, dim] float16, Doff [N + 1] int64,
-    the candidate side (_pairs_args) and max_doc_len.  -> (Qtok, Doff, cand_len, out, (Q, Lq, dim, N, k))."""
-    _dev(Qtok, torch.float16, f"{what}(Qtok)")
-    _dev(Doff, torch.int64, f"{what}(Doff)")
-    _need(Qtok.dim() == 3, f"{what}: Qtok must be [Q, Lq, dim]")
-    Qtok, Doff = Qtok.contiguous(), Doff.contiguous()
-    Q, Lq, dim = Qtok.shape
-    N = Doff.numel() - 1
-    _need(Doff.dim() == 1 and N >= 0, f"{what}: Doff must hold N + 1 offsets")
+def _maxsim_pairs_args(what: str, Qtok: torch.Tensor, Doff: torch.Tensor, cand: torch.Tensor, cand_len, out, max_doc_len, e4m3: bool = False):
+    """What the candidate-list MaxSim ops check whatever the document rows are stored as: the query side of the token store (_token_queries;
+    Doff one-dimensional), the candidate side (_pairs_args) and max_doc_len.  -> (Qtok, Doff, cand_len, out, (Q, Lq, dim, N, k))."""
+    Qtok, Doff, (Q, Lq, dim, N) = _token_queries(what, Qtok, Doff, e4m3)
+    _need(Doff.dim() == 1, f"{what}: Doff must hold N + 1 offsets")
     cand_len, out, k = _pairs_args(what, Q, Qtok.device, cand, cand_len, out)
     _need(int(max_doc_len) >= 1, f"{what}: max_doc_len must be at least 1")
     return Qtok, Doff, cand_len, out, (Q, Lq, dim, N, k)
@@ -382,8 +389,7 @@ def maxsim_pairs(Qtok: torch.Tensor, Dtok: torch.Tensor, Doff: torch.Tensor, can
     (id_base .. id_base + N - 1); an empty document scores 0.  `out` [Q, k] float32 may be a view of a wider plane: only its k columns
     are written.  No host synchronisation."""
     Qtok, Doff, cand_len, out, (Q, Lq, dim, N, k) = _maxsim_pairs_args("maxsim_pairs", Qtok, Doff, cand, cand_len, out, max_doc_len)
-    Dtok = _dev(Dtok, torch.float16, "maxsim_pairs(Dtok)").contiguous()
-    _need(Dtok.dim() == 2 and Dtok.shape[1] == dim, f"maxsim_pairs: Dtok must be [sumL, {dim}]")
+    Dtok = _token_rows("maxsim_pairs", Dtok, dim)
     check(_lib.lib().fz_maxsim_pairs_f16(_ptr(Qtok), _ptr(Dtok), _ptr(Doff), int(Dtok.shape[0]), int(max_doc_len), Q, Lq, N, dim, _ptr(cand),
                                          _ld(cand), _ptr(cand_len), k, int(id_base), _ptr(out), _ld(out), _stream(Qtok)),
           "fz_maxsim_pairs_f16")
@@ -398,18 +404,9 @@ def maxsim_pairs_e4m3(Q8: torch.Tensor, D8: torch.Tensor, Doff: torch.Tensor, ca
     and the -inf / 0 slots as in maxsim_pairs (rows of cand may be strided, `out` may be a view of a wider plane).  No host
     synchronisation."""
     what = "maxsim_pairs_e4m3"
-    Q8 = _e4m3_bytes(Q8, f"{what}(Q8)")
-    D8 = _e4m3_bytes(D8, f"{what}(D8)")
-    _dev(Doff, torch.int64, f"{what}(Doff)")
     q_exp, d_exp = _e4m3_exp(q_exp, f"{what}(q_exp)"), _e4m3_exp(d_exp, f"{what}(d_exp)")
-    _need(Q8.dim() == 3, f"{what}: Q8 must be [Q, Lq, dim]")
-    Q8, D8, Doff = Q8.contiguous(), D8.contiguous(), Doff.contiguous()
-    Q, Lq, dim = Q8.shape
-    N = Doff.numel() - 1
-    _need(Doff.dim() == 1 and N >= 0, f"{what}: Doff must hold N + 1 offsets")
-    _need(D8.dim() == 2 and D8.shape[1] == dim, f"{what}: D8 must be [sumL, {dim}]")
-    cand_len, out, k = _pairs_args(what, Q, Q8.device, cand, cand_len, out)
-    _need(int(max_doc_len) >= 1, f"{what}: max_doc_len must be at least 1")
+    Q8, Doff, cand_len, out, (Q, Lq, dim, N, k) = _maxsim_pairs_args(what, Q8, Doff, cand, cand_len, out, max_doc_len, e4m3=True)
+    D8 = _token_rows(what, D8, dim, e4m3=True)
     check(_lib.lib().fz_maxsim_pairs_e4m3(_ptr(Q8), _ptr(D8), _ptr(Doff), int(D8.shape[0]), int(max_doc_len), Q, Lq, N, dim, q_exp + d_exp,
                                           _ptr(cand), _ld(cand), _ptr(cand_len), k, int(id_base), _ptr(out), _ld(out), _stream(Q8)),
           "fz_maxsim_pairs_e4m3")
@@ -1656,20 +1653,18 @@ def bm25_scores(toff, pdoc, ptf, idf, doc_len, avgdl: float, k1: float, b: float
     this (k1, b) (bm25_posting_values): the walk then adds tabulated terms instead of dividing per posting -- same bits."""
     dev = idf.device
     if pval is not None:
-        for t, dt, what in ((toff, torch.int64, "toff"), (pdoc, torch.int32, "pdoc"), (pval, torch.float64, "pval"), (qoff, torch.int64, "qoff"),
-                            (qterms, torch.int32, "qterms")):
-            _need(_dev(t, dt, f"bm25_scores({what})").is_contiguous(), f"bm25_scores({what}) must be contiguous")
+        _contiguous("bm25_scores", (toff, torch.int64, "toff"), (pdoc, torch.int32, "pdoc"), (pval, torch.float64, "pval"), (qoff, torch.int64, "qoff"),
+                    (qterms, torch.int32, "qterms"))
         _need(pval.numel() == pdoc.numel() and qoff.numel() == Q + 1, "bm25_scores: pval must hold one value per posting and qoff Q + 1 offsets")
         if slice_off is not None:
             _slice_table("bm25_scores", slice_off, toff.numel() - 1, N, "bm25")
-        out = torch.empty((max(Q, 1), max(round_up(N, _PAD), _PAD)), dtype=torch.float64, device=dev)[:Q, :N]
+        out = alloc_plane(Q, N, torch.float64, dev)
         out32 = alloc_plane(Q, N, torch.float32, dev) if want_f32 else None
         check(_lib.lib().fz_bm25_scores_pv_f64_f32(_ptr(toff), _ptr(pdoc), _ptr(pval), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, _ptr(out),
                                                    _ld(out), _ptr(out32), _ld(out32) if want_f32 else 0, _stream(pval)), "fz_bm25_scores_pv_f64_f32")
         return (out, out32) if want_f32 else out
-    for t, dt, what in ((toff, torch.int64, "toff"), (pdoc, torch.int32, "pdoc"), (ptf, torch.int32, "ptf"), (idf, torch.float64, "idf"),
-                        (doc_len, torch.int32, "doc_len"), (qoff, torch.int64, "qoff"), (qterms, torch.int32, "qterms")):
-        _need(_dev(t, dt, f"bm25_scores({what})").is_contiguous(), f"bm25_scores({what}) must be contiguous")
+    _contiguous("bm25_scores", (toff, torch.int64, "toff"), (pdoc, torch.int32, "pdoc"), (ptf, torch.int32, "ptf"), (idf, torch.float64, "idf"),
+                (doc_len, torch.int32, "doc_len"), (qoff, torch.int64, "qoff"), (qterms, torch.int32, "qterms"))
     _need(toff.numel() == idf.numel() + 1, "bm25_scores: toff must hold V + 1 offsets for idf's V terms")
     _need(pdoc.numel() == ptf.numel(), "bm25_scores: pdoc and ptf differ in length")
     _need(doc_len.numel() == N and qoff.numel() == Q + 1, f"bm25_scores: doc_len must hold {N} lengths and qoff {Q + 1} offsets")
@@ -1677,7 +1672,7 @@ def bm25_scores(toff, pdoc, ptf, idf, doc_len, avgdl: float, k1: float, b: float
         _need(_dev(doc_norm, torch.float64, "bm25_scores(doc_norm)").numel() == N and doc_norm.is_contiguous(), f"bm25_scores: doc_norm must hold {N} values")
     if slice_off is not None:
         _slice_table("bm25_scores", slice_off, idf.numel(), N, "bm25")
-    out = torch.empty((max(Q, 1), max(round_up(N, _PAD), _PAD)), dtype=torch.float64, device=dev)[:Q, :N]
+    out = alloc_plane(Q, N, torch.float64, dev)
     out32 = alloc_plane(Q, N, torch.float32, dev) if want_f32 else None
     check(_lib.lib().fz_bm25_scores_f64_f32(_ptr(toff), _ptr(pdoc), _ptr(ptf), _ptr(idf), _ptr(doc_len), _ptr(doc_norm), _ptr(slice_off), float(avgdl),
                                             float(k1), float(b), _ptr(qoff), _ptr(qterms), Q, N, _ptr(out), _ld(out), _ptr(out32),
@@ -1688,9 +1683,8 @@ def bm25_scores(toff, pdoc, ptf, idf, doc_len, avgdl: float, k1: float, b: float
 def bm25_posting_values(toff, pdoc, ptf, idf, doc_norm, k1: float) -> torch.Tensor:
     """[nnz] float64: every posting's BM25 term idf * (tf (k1 + 1)) / (tf + doc_norm[d]) (bm25.py:154) for the (k1, b) doc_norm was made
     with -- per index, like the idf table (fz_bm25_posting_values_f64); bm25_scores(pval=...) then only adds."""
-    for t, dt, what in ((toff, torch.int64, "toff"), (pdoc, torch.int32, "pdoc"), (ptf, torch.int32, "ptf"), (idf, torch.float64, "idf"),
-                        (doc_norm, torch.float64, "doc_norm")):
-        _need(_dev(t, dt, f"bm25_posting_values({what})").is_contiguous(), f"bm25_posting_values({what}) must be contiguous")
+    _contiguous("bm25_posting_values", (toff, torch.int64, "toff"), (pdoc, torch.int32, "pdoc"), (ptf, torch.int32, "ptf"), (idf, torch.float64, "idf"),
+                (doc_norm, torch.float64, "doc_norm"))
     _need(toff.numel() == idf.numel() + 1 and pdoc.numel() == ptf.numel(), "bm25_posting_values: toff [V + 1], idf [V], pdoc / ptf [nnz] expected")
     out = torch.empty(pdoc.numel(), dtype=torch.float64, device=idf.device)
     check(_lib.lib().fz_bm25_posting_values_f64(_ptr(toff), _ptr(pdoc), _ptr(ptf), _ptr(idf), _ptr(doc_norm), idf.numel(), pdoc.numel(), float(k1),
@@ -1702,14 +1696,13 @@ def tfidf_scores(toff, pdoc, ptf, idf, qoff, qterms, Q: int, N: int, slice_off: 
     """TF-IDF scores [Q, N] float64 (TFIDF.score, bm25.py:108-115: sum over the query's terms, in query order, of tf * idf); want_f32: also
     their float32 rounding from the same launch."""
     dev = idf.device
-    for t, dt, what in ((toff, torch.int64, "toff"), (pdoc, torch.int32, "pdoc"), (ptf, torch.int32, "ptf"), (idf, torch.float64, "idf"),
-                        (qoff, torch.int64, "qoff"), (qterms, torch.int32, "qterms")):
-        _need(_dev(t, dt, f"tfidf_scores({what})").is_contiguous(), f"tfidf_scores({what}) must be contiguous")
+    _contiguous("tfidf_scores", (toff, torch.int64, "toff"), (pdoc, torch.int32, "pdoc"), (ptf, torch.int32, "ptf"), (idf, torch.float64, "idf"),
+                (qoff, torch.int64, "qoff"), (qterms, torch.int32, "qterms"))
     _need(toff.numel() == idf.numel() + 1 and pdoc.numel() == ptf.numel() and qoff.numel() == Q + 1,
           "tfidf_scores: toff must hold V + 1 offsets for idf's V terms, pdoc / ptf one entry per posting, qoff Q + 1 offsets")
     if slice_off is not None:
         _slice_table("tfidf_scores", slice_off, idf.numel(), N, "bm25")
-    out = torch.empty((max(Q, 1), max(round_up(N, _PAD), _PAD)), dtype=torch.float64, device=dev)[:Q, :N]
+    out = alloc_plane(Q, N, torch.float64, dev)
     out32 = alloc_plane(Q, N, torch.float32, dev) if want_f32 else None
     check(_lib.lib().fz_tfidf_scores_f64(_ptr(toff), _ptr(pdoc), _ptr(ptf), _ptr(idf), _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N,
                                          _ptr(out), _ld(out), _ptr(out32), _ld(out32) if want_f32 else 0, _stream(idf)), "fz_tfidf_scores_f64")
@@ -1730,9 +1723,8 @@ def lexical_slice_docs(mode: str) -> int:
 
 def _lexical_args(what: str, mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int, doc_lo: int, doc_hi, slice_off):
     """The host-side contract the four lexical range entries share -> (doc_lo, doc_hi)."""
-    for t, dt, name in ((toff, torch.int64, "toff"), (pdoc, torch.int32, "pdoc"), (qoff, torch.int64, "qoff"), (qterms, torch.int32, "qterms"),
-                        (vals, torch.float64 if mode == "pv" else torch.int32, "pval" if mode == "pv" else "ptf")):
-        _need(_dev(t, dt, f"{what}({name})").is_contiguous(), f"{what}({name}) must be contiguous")
+    _contiguous(what, (toff, torch.int64, "toff"), (pdoc, torch.int32, "pdoc"), (qoff, torch.int64, "qoff"), (qterms, torch.int32, "qterms"),
+                (vals, torch.float64 if mode == "pv" else torch.int32, "pval" if mode == "pv" else "ptf"))
     V = toff.numel() - 1
     _need(V >= 0 and vals.numel() == pdoc.numel() > 0 and qoff.numel() == Q + 1 and qterms.numel() > 0,
           f"{what}: toff [V + 1], one value per posting (at least one), qoff [Q + 1] and a non-empty qterms expected")
@@ -1751,10 +1743,6 @@ def _lexical_call(mode: str, stem: str, toff, pdoc, vals, idf, *rest) -> None:
     check(getattr(_lib.lib(), name)(_ptr(toff), _ptr(pdoc), *values, *rest, _stream(toff)), name)
 
 
-def _range_plane64(Q: int, n: int, dev) -> torch.Tensor:
-    return torch.empty((max(Q, 1), max(round_up(n, _PAD), _PAD)), dtype=torch.float64, device=dev)[:Q, :n]
-
-
 def lexical_scores_range(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int, doc_lo: int = 0, doc_hi: int | None = None,
                          slice_off: torch.Tensor | None = None) -> torch.Tensor:
     """Columns [doc_lo, doc_hi) of the full float64 plane, bit for bit, without the rest of it (fz_bm25_scores_range_pv_f64 /
@@ -1762,7 +1750,7 @@ def lexical_scores_range(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int,
     a multiple of it or N.  vals: pval ('pv') or ptf ('tfidf', with idf)."""
     what = ("bm25" if mode == "pv" else "tfidf") + "_scores_range"      # the public wrappers' names: what a caller reads in an error
     doc_lo, doc_hi = _lexical_args(what, mode, toff, pdoc, vals, idf, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
-    out = _range_plane64(Q, doc_hi - doc_lo, toff.device)
+    out = alloc_plane(Q, doc_hi - doc_lo, torch.float64, toff.device)
     _lexical_call(mode, "scores_range", toff, pdoc, vals, idf, _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi, _ptr(out), _ld(out))
     return out
 
@@ -2154,11 +2142,7 @@ def sparse_dot(index: SparseIndex, qoff: torch.Tensor, qterms: torch.Tensor, qw:
     for bit."""
     Q = _sparse_queries(qoff, qterms, qw, "sparse_dot")
     doc_lo, doc_hi = _doc_range("sparse_dot", index.N, sparse_slice_docs(), doc_lo, doc_hi)
-    if out is None:
-        out = alloc_plane(Q, doc_hi - doc_lo, torch.float32, qoff.device)
-    else:
-        _dev(out, torch.float32, "sparse_dot(out)")
-        _need(tuple(out.shape) == (Q, doc_hi - doc_lo), f"sparse_dot(out): expected shape {(Q, doc_hi - doc_lo)}, got {tuple(out.shape)}")
+    out = _out("sparse_dot", out, (Q, doc_hi - doc_lo), torch.float32, qoff.device, plane=True)
     check(_lib.lib().fz_sparse_dot_range_f32(_ptr(index.toff), _ptr(index.pdoc), _ptr(index.pw), _ptr(index.slice_off), _ptr(qoff), _ptr(qterms),
                                              _ptr(qw), Q, index.N, doc_lo, doc_hi, _ptr(out), _ld(out), _stream(qoff)), "fz_sparse_dot_range_f32")
     return out
@@ -2275,11 +2259,7 @@ def dense_feedback(Qn: torch.Tensor, Dn: torch.Tensor, fb_ids: torch.Tensor, fb_
     Q, N, dim = int(Qn.shape[0]), int(Dn.shape[0]), int(Qn.shape[1])
     _need(dim >= 1, "dense_feedback: dim must be at least 1")
     fb_len, F = _feedback_args("dense_feedback", Q, fb_ids, fb_len, coef)
-    if out is None:
-        out = alloc_plane(Q, dim, torch.float32, Qn.device)
-    else:
-        _dev(out, torch.float32, "dense_feedback(out)")
-        _need(tuple(out.shape) == (Q, dim), f"dense_feedback(out): expected shape {(Q, dim)}, got {tuple(out.shape)}")
+    out = _out("dense_feedback", out, (Q, dim), torch.float32, Qn.device, plane=True)
     check(_lib.lib().fz_dense_feedback_f32(_ptr(Qn), max(_ld(Qn), dim), _ptr(Dn), max(_ld(Dn), dim), Q, N, dim, int(id_base), _ptr(fb_ids),
                                            max(_ld(fb_ids), F), _ptr(fb_len), _ptr(coef), max(_ld(coef), F), F, float(alpha), _ptr(out),
                                            max(_ld(out), dim), _stream(Qn)), "fz_dense_feedback_f32")
@@ -2495,11 +2475,7 @@ def centroid_scores(index: CentroidIndex, pc: torch.Tensor, ps: torch.Tensor, Lq
     bit: a range's columns are the full plane's.  doc_lo a multiple of centroid_slice_docs(), doc_hi one too or N.  Probe scores must be
     finite (non-finite query tokens are outside the contract)."""
     Q, Lq, nprobe, doc_lo, doc_hi = _centroid_args("centroid_scores", index, pc, ps, Lq, nprobe, doc_lo, doc_hi)
-    if out is None:
-        out = alloc_plane(Q, doc_hi - doc_lo, torch.float32, pc.device)
-    else:
-        _dev(out, torch.float32, "centroid_scores(out)")
-        _need(tuple(out.shape) == (Q, doc_hi - doc_lo), f"centroid_scores(out): expected shape {(Q, doc_hi - doc_lo)}, got {tuple(out.shape)}")
+    out = _out("centroid_scores", out, (Q, doc_hi - doc_lo), torch.float32, pc.device, plane=True)
     check(_lib.lib().fz_centroid_scores_range_f32(_ptr(index.coff), _ptr(index.cdoc), _ptr(index.slice_off), _ptr(pc), _ptr(ps), Q, Lq, nprobe, index.N,
                                                   index.K, doc_lo, doc_hi, _ptr(out), _ld(out), _stream(pc)), "fz_centroid_scores_range_f32")
     return out
@@ -2783,11 +2759,7 @@ def attn_varlen(qkv: torch.Tensor, strips: torch.Tensor, heads: int, scale: floa
         raise ValueError(f"attn_varlen: qkv is {W} wide, expected 3*{heads}*64 (head_dim 64 only)")
     if strips.dim() != 2 or strips.shape[1] != 4 or not strips.is_contiguous():
         raise ValueError("attn_varlen: strips must be a contiguous [n_strips, 4] int32 tensor (ops.attn_strips)")
-    if out is None:
-        out = torch.empty((T, heads * 64), dtype=torch.float32, device=qkv.device)
-    else:
-        _dev(out, torch.float32, "attn_varlen(out)")
-        _need(tuple(out.shape) == (T, heads * 64), f"attn_varlen(out): expected shape {(T, heads * 64)}, got {tuple(out.shape)}")
+    out = _out("attn_varlen", out, (T, heads * 64), torch.float32, qkv.device, plane=False)
     if scale is not None and not scale > 0:
         raise ValueError("attn_varlen: scale must be positive")
     check(_lib.lib().fz_attn_varlen_f32(_ptr(qkv), qkv.stride(0) if T > 1 else W, _ptr(strips), strips.shape[0], heads, 64,
@@ -2825,11 +2797,7 @@ def add_layernorm_x16(x16: torch.Tensor, res: torch.Tensor | None, gamma: torch.
         if res.shape != x16.shape:
             raise ValueError("add_layernorm_x16: x16 and res differ in shape")
     _need(gamma.numel() == d and beta.numel() == d and gamma.is_contiguous() and beta.is_contiguous(), f"add_layernorm_x16: gamma and beta must hold {d} values")
-    if out is None:
-        out = torch.empty((rows, d), dtype=torch.float32, device=x16.device)
-    else:
-        _dev(out, torch.float32, "add_layernorm_x16(out)")
-        _need(tuple(out.shape) == (rows, d), f"add_layernorm_x16(out): expected shape {(rows, d)}, got {tuple(out.shape)}")
+    out = _out("add_layernorm_x16", out, (rows, d), torch.float32, x16.device, plane=False)
     if out16 is not None:
         _dev(out16, torch.float16, "add_layernorm_x16(out16)")
         _need(tuple(out16.shape) == (rows, d), f"add_layernorm_x16(out16): expected shape {(rows, d)}, got {tuple(out16.shape)}")
@@ -2857,11 +2825,7 @@ def add_layernorm(x: torch.Tensor, res: torch.Tensor | None, gamma: torch.Tensor
         if res.shape != x.shape:
             raise ValueError("add_layernorm: x and res differ in shape")
     _need(gamma.numel() == d and beta.numel() == d and gamma.is_contiguous() and beta.is_contiguous(), f"add_layernorm: gamma and beta must hold {d} values")
-    if out is None:
-        out = torch.empty((rows, d), dtype=torch.float32, device=x.device)
-    else:
-        _dev(out, torch.float32, "add_layernorm(out)")
-        _need(tuple(out.shape) == (rows, d), f"add_layernorm(out): expected shape {(rows, d)}, got {tuple(out.shape)}")
+    out = _out("add_layernorm", out, (rows, d), torch.float32, x.device, plane=False)
     ldr = 0 if res is None else (res.stride(0) if rows > 1 else d)
     check(_lib.lib().fz_add_layernorm_f32(_ptr(x), x.stride(0) if rows > 1 else d, _ptr(res), ldr, _ptr(_dev(gamma, torch.float32, "gamma")),
                                           _ptr(_dev(beta, torch.float32, "beta")), float(eps), rows, d, _ptr(out),

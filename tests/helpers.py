@@ -79,3 +79,19 @@ def planned_search_marks(ops, head, n, chunk, k, cap, grain, plane_mark, filter_
                 marks.append("shard_topk_stream")
                 seen, pending, folds = seen + pending, 0, folds + 1
     return marks + ["shard_topk_stream", "allgather_merge"], folds, inside
+
+
+def dynamic_fz_symbols(path: str) -> set:
+    """The fz_* names a shared library defines in its dynamic symbol table (nm -D --defined-only, or ROCm's llvm-nm); skips the calling test
+    where neither tool is installed."""
+    import os
+    import shutil
+    import subprocess
+    import pytest
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    tools = [shutil.which("nm"), shutil.which("llvm-nm"), os.path.join(rocm, "lib", "llvm", "bin", "llvm-nm"), os.path.join(rocm, "llvm", "bin", "llvm-nm")]
+    tool = next((t for t in tools if t and os.path.exists(t)), None)
+    if tool is None:
+        pytest.skip("neither nm nor llvm-nm is on this machine: the library's dynamic symbol table cannot be read")
+    out = subprocess.run([tool, "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
+    return {line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("fz_")}

@@ -23,7 +23,11 @@ def test_library_loads_and_exports_header_symbols():
     assert len(declared) >= 20
     for name in declared:
         assert hasattr(L, name), f"libfusion_hip.so does not export {name}"
-    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)   # the binding table IS the header
+    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)   # the binding table is parsed from the header: every name it mentions is bound
+    # ... and the other direction, which the table cannot answer: the library's dynamic symbol table defines exactly the declared fz_* names
+    from helpers import dynamic_fz_symbols
+    defined = dynamic_fz_symbols(_lib.LIB_PATH)
+    assert defined == declared, (sorted(declared - defined), sorted(defined - declared))
     assert L.fz_strerror(0) == b"ok" and b"invalid" in L.fz_strerror(-1)
     assert L.fz_sort_max_n() == 35840 and L.fz_topk_max_k() >= 1000
 
