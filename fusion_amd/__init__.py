@@ -10,7 +10,7 @@ Layout (only what the encode -> score -> fuse hot path needs):
   retrievers/bm25.py    BM25 (host index build, device scoring)
   utils/metrics.py      Metrics
   encoders.py           PyTorch-ROCm transformer forwards (DPR mean-pool, SPLADE, ColBERT)
-  distributed.py        corpus-sharded top-k with one RCCL all-gather
+  distributed.py        corpus-sharded top-k with one RCCL all-gather; pair scores and reranks (rank_pairs); world / reduce_max / reduce_sum
   passages.py           long documents: passage windows, passage lists -> document lists (MaxP)
   feedback.py           pseudo-relevance feedback: coefficients from top-k lists, the multi-shard row gather
 """

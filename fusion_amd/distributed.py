@@ -27,48 +27,65 @@ def shard_bounds(n: int, world: int, rank: int) -> tuple[int, int]:
     return lo, lo + base + (1 if rank < extra else 0)
 
 
+def world(group=None) -> int:
+    """How many ranks the group has; 1 without an initialised process group."""
+    import torch.distributed as dist
+    return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+
+
+def reduce_max(t: torch.Tensor, group=None, skip_empty: bool = False) -> torch.Tensor:
+    """The tree's convention for slots a shard does not own: they hold the type's lowest value (-inf in a pair plane), so ONE
+    all_reduce(MAX) leaves every slot its owner's value on every rank.  The collective takes the contiguous block, not a padded plane:
+    a contiguous t is reduced in place.  skip_empty: no collective for an empty t (feedback.pack_rows; the pair planes reduce even then)."""
+    if world(group) > 1 and not (skip_empty and t.numel() == 0):
+        import torch.distributed as dist
+        t = t.contiguous()
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+    return t
+
+
+def reduce_sum(t: torch.Tensor, group=None) -> torch.Tensor:
+    """Per-shard counts -> the whole corpus's: one all_reduce(SUM), as reduce_max takes its block."""
+    if world(group) > 1:
+        import torch.distributed as dist
+        t = t.contiguous()
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t
+
+
 def allgather_rows(local: torch.Tensor, total: int, group=None) -> torch.Tensor:
     """Rows sharded by shard_bounds(total, world, rank) -> the full [total, d] tensor on every rank, in rank order:
     one all-gather of equal-size (zero-padded) blocks."""
-    import torch.distributed as dist
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    if world == 1:
+    G = world(group)
+    if G == 1:
         return local
-    per = -(-total // world)
+    import torch.distributed as dist
+    per = -(-total // G)
     block = local.new_zeros((per, local.shape[1]))
     block[: local.shape[0]] = local
-    out = local.new_empty((world * per, local.shape[1]))
+    out = local.new_empty((G * per, local.shape[1]))
     dist.all_gather_into_tensor(out, block, group=group)
-    if total == world * per:
+    if total == G * per:
         return out
-    return torch.cat([out[r * per: r * per + (hi - lo)] for r in range(world) for lo, hi in [shard_bounds(total, world, r)]])
+    return torch.cat([out[r * per: r * per + (hi - lo)] for r in range(G) for lo, hi in [shard_bounds(total, G, r)]])
 
 
 def allgather_topk(local_scores: torch.Tensor, local_ids: torch.Tensor, group=None, merge_fn=None):
     """local [Q, k] lists (each sorted by score desc, id asc; padding = (-inf, -1)) -> global [Q, k] on every rank.
     merge_fn([G,Q,k] scores, [G,Q,k] ids) -> ([Q,k], [Q,k]); defaults to the HIP merge."""
-    import torch.distributed as dist
     if merge_fn is None:
         merge_fn = ops.topk_merge
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    if world == 1:
+    G = world(group)
+    if G == 1:
         return merge_fn(local_scores.unsqueeze(0).contiguous(), local_ids.unsqueeze(0).contiguous())
-    Q, k = local_scores.shape
-    gs = torch.empty((world, Q, k), dtype=local_scores.dtype, device=local_scores.device)
-    gi = torch.empty((world, Q, k), dtype=local_ids.dtype, device=local_ids.device)
-    # concatenated-along-dim-0 output form: accepted by RCCL and gloo alike
-    dist.all_gather_into_tensor(gs.view(world * Q, k), local_scores.contiguous(), group=group)
-    dist.all_gather_into_tensor(gi.view(world * Q, k), local_ids.contiguous(), group=group)
-    return merge_fn(gs, gi)
-
-
-def _reduce_max(plane: torch.Tensor, group=None) -> torch.Tensor:
-    """Shards' pair planes -> everyone's: a slot a shard does not own holds -inf, so ONE all_reduce(MAX) leaves every slot its owner's score."""
     import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-        plane = plane.contiguous()      # the collective takes the [Q, W] block, not the padded plane
-        dist.all_reduce(plane, op=dist.ReduceOp.MAX, group=group)
-    return plane
+    Q, k = local_scores.shape
+    gs = torch.empty((G, Q, k), dtype=local_scores.dtype, device=local_scores.device)
+    gi = torch.empty((G, Q, k), dtype=local_ids.dtype, device=local_ids.device)
+    # concatenated-along-dim-0 output form: accepted by RCCL and gloo alike
+    dist.all_gather_into_tensor(gs.view(G * Q, k), local_scores.contiguous(), group=group)
+    dist.all_gather_into_tensor(gi.view(G * Q, k), local_ids.contiguous(), group=group)
+    return merge_fn(gs, gi)
 
 
 def rank_order(ids: torch.Tensor, scores: torch.Tensor, row_len: torch.Tensor | None = None) -> torch.Tensor:
@@ -84,11 +101,18 @@ def rank_order(ids: torch.Tensor, scores: torch.Tensor, row_len: torch.Tensor | 
     return order.long()
 
 
-def rank_pairs(ids: torch.Tensor, scores: torch.Tensor, k: int | None = None):
+def rank_pairs(ids: torch.Tensor, scores: torch.Tensor, k: int | None = None, *, row_len: torch.Tensor | None = None, ties: str = "id"):
     """Candidate ids [Q, k0] int64 and their (reduced) pair scores [Q, k0], float32 or float64 -> planes.RankedTopk of the candidates in
-    (score desc, global id asc) order, the order of every corpus-scale search here, cut to the first k.  A slot no shard owned (-inf) goes
-    last as (-inf, -1); lens counts the others.  float64 scores are ranked as float64 and kept as scores64 (scores = their float32 roundings)."""
+    descending score order, cut to the first k: the one place that turns pair scores into lists.  Among equal scores (a NaN ranks first,
+    as in every sort here)
+      ties="id"    the ascending global id decides, the order of every corpus-scale search here (rank_order);
+      ties="list"  the candidates keep their incoming order: the stable row sort alone, no id sort.
+    A slot no shard owned (-inf) goes last as (-inf, -1); lens counts the others.  row_len [Q] int32: only the first row_len[q] columns of
+    row q take part, and exactly those are owned, whatever they score (Aggregator.complete_topk: a listed id keeps its place in the list).
+    float64 scores are ranked as float64 and kept as scores64 (scores = their float32 roundings)."""
     from .planes import RankedTopk
+    if ties not in ("id", "list"):
+        raise ValueError(f"rank_pairs(ties): expected 'id' or 'list', got {ties!r}")
     Q, k0 = ids.shape
     k = k0 if k is None else max(0, min(int(k), k0))
     wide = scores.dtype == torch.float64
@@ -96,9 +120,16 @@ def rank_pairs(ids: torch.Tensor, scores: torch.Tensor, k: int | None = None):
         s32 = torch.empty((Q, k), dtype=torch.float32, device=ids.device)
         return RankedTopk(ids=ids[:, :k].clone(), scores=s32, lens=torch.zeros(Q, dtype=torch.int32, device=ids.device),
                           scores64=s32.double() if wide else None)
-    order = rank_order(ids, scores)[:, :k]
-    ss = torch.gather(scores, 1, order)                      # the scores' own bits (the sort's key plane canonicalises -0.0 and NaN)
-    owned = ss != float("-inf")
+    if ties == "id":
+        order = rank_order(ids, scores, row_len)[:, :k]
+    else:                                                    # the incoming sequence is the list itself; cut before the widening to int64
+        order = ops.sort_rows_desc(scores, row_len=row_len, want_keys=False)[0][:, :k].long()
+    if row_len is None:
+        ss = torch.gather(scores, 1, order)                  # the scores' own bits (the sort's key plane canonicalises -0.0 and NaN)
+        owned = ss != float("-inf")
+    else:                                                    # the order past a row's length is -1
+        owned, order = order >= 0, order.clamp(min=0)
+        ss = torch.gather(scores, 1, order).masked_fill_(~owned, float("-inf"))
     out_ids = torch.where(owned, torch.gather(ids, 1, order), torch.full_like(order, -1))
     return RankedTopk(ids=out_ids, scores=ss.to(torch.float32), lens=owned.sum(1, dtype=torch.int32), scores64=ss if wide else None)
 
@@ -106,6 +137,58 @@ def rank_pairs(ids: torch.Tensor, scores: torch.Tensor, k: int | None = None):
 def _candidates(candidates):
     from .planes import FusedTopk, RankedTopk
     return (candidates.ids, candidates.lens) if isinstance(candidates, (RankedTopk, FusedTopk)) else (candidates, None)
+
+
+class _PairScores:
+    """Exact scores of (query, candidate id) pairs over a sharded corpus, and candidate lists reranked by them.  A subclass supplies
+    local_pair_scores(*query, cand_ids, cand_len=None) -> [Q, W] float32 or float64 over its own shard, -inf for a slot it does not own
+    (r >= cand_len[q], a negative id, a document of another shard), and its tie rule."""
+
+    TIES = "id"             # rank_pairs' rule among equal scores
+    # What an empty candidate batch does.  True: it goes through the scorer and the collective like any other (every rank of the group
+    # must then call, empty or not).  False: it returns before both.  Each class keeps what it always did: changing either side would
+    # leave a rank of an older caller waiting in the collective.
+    EMPTY_REDUCES = True
+
+    def local_pair_scores(self, *args, **kw) -> torch.Tensor:
+        """The token and text indexes call theirs local_scores: that name is the one to override there."""
+        return self.local_scores(*args, **kw)
+
+    def pair_scores(self, *args, **kw) -> torch.Tensor:
+        """pair_scores(*query, cand_ids, cand_len=None): local_pair_scores for the whole corpus -- the shards' planes under ONE
+        all_reduce(MAX) over the group (reduce_max)."""
+        return reduce_max(self.local_pair_scores(*args, **kw), self.group)
+
+    def rerank(self, *args, k: int | None = None):
+        """rerank(*query, candidates, k=None).  candidates: a planes.RankedTopk or FusedTopk (its ids and lens are used) or a [Q, k0]
+        int64 id tensor (negative ids = padding) -> RankedTopk of the candidates by their exact scores in descending order, ties by the
+        class's rule, cut to the first k (rank_pairs).  lens[q] = the slots some shard owned; the others go last as (-inf, -1).  A score
+        of -inf itself -- possible only with non-finite inputs -- is indistinguishable from "owned by no shard" and counts as such."""
+        if not args or isinstance(args[-1], int):
+            raise TypeError(f"{type(self).__name__}.rerank(*query, candidates, k=None): the candidates go last by position, k by keyword")
+        *query, candidates = args
+        return self._rerank(query, *_candidates(candidates), k)
+
+    def _rerank(self, query, ids: torch.Tensor, cand_len, k):
+        if ids.numel() == 0 and not self.EMPTY_REDUCES:
+            return rank_pairs(ids, torch.empty(ids.shape, dtype=torch.float32, device=ids.device), k, ties=self.TIES)
+        return rank_pairs(ids, self.pair_scores(*query, ids, cand_len), k, ties=self.TIES)
+
+
+def _fill_blocks(what: str, blocks, rows: int, device, fill) -> None:
+    """Drive an iterator of token-row blocks that together hold exactly `rows` rows: every block is moved to the device as contiguous
+    float16 and handed to fill(at, blk), at = the row it starts on.  ValueError, under the caller's name `what`, for more or fewer rows."""
+    at = 0
+    for blk in blocks:
+        blk = blk.to(device=device, dtype=torch.float16).contiguous()
+        n = blk.shape[0]
+        if at + n > rows:
+            raise ValueError(f"{what}: the blocks hold more than Doff[N] = {rows} token rows")
+        if n:
+            fill(at, blk)
+        at += n
+    if at != rows:
+        raise ValueError(f"{what}: the blocks hold {at} token rows, Doff[N] = {rows}")
 
 
 class _ShardedIndex:
@@ -165,8 +248,16 @@ class _ShardedIndex:
         if mark: mark("allgather_merge")
         return out
 
+    def _search_feedback(self, q: tuple, k: int, mark, feedback: dict):
+        """search -> feedback -> search: the first pass's lists feed the queries back (the subclass's feedback(*q, first, **feedback): one
+        tensor or a tuple, as its search takes them), the expanded queries are searched again -> planes.RankedTopk of the second pass."""
+        from .planes import RankedTopk
+        first = RankedTopk.from_search(*self.search(*q, k, mark=mark))
+        q = self.feedback(*q, first, **feedback)
+        return RankedTopk.from_search(*self.search(*(q if isinstance(q, tuple) else (q,)), k, mark=mark))
 
-class ShardedDenseIndex(_ShardedIndex):
+
+class ShardedDenseIndex(_PairScores, _ShardedIndex):
     """One rank's shard of the L2-normalised corpus embeddings: the fp32-MFMA GEMM scores it, and after the head the GEMM's epilogue is
     the threshold filter (fz_dot_scores_filter_f32: per shard 4.5 GB less written and 4.5 GB less read than a plane and a filter pass)."""
 
@@ -215,16 +306,6 @@ class ShardedDenseIndex(_ShardedIndex):
         """[Q, W] float32: the GEMM's score of query q and candidate cand_ids[q, r], bit for bit, without the plane (ops.dot_pairs)."""
         return ops.dot_pairs(Qn, self.Dn, cand_ids, cand_len, id_base=self.id_base)
 
-    def pair_scores(self, Qn: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
-        """local_pair_scores for the whole corpus: a slot this shard does not own holds -inf, one all_reduce(MAX) over the group."""
-        return _reduce_max(self.local_pair_scores(Qn, cand_ids, cand_len), self.group)
-
-    def rerank(self, Qn: torch.Tensor, candidates, k: int | None = None):
-        """candidates (a planes.RankedTopk: its ids and lens; or a [Q, k0] int64 id tensor, negative ids = padding) -> RankedTopk of the
-        candidates by their exact scores, in (score desc, global id asc) order, cut to the first k (rank_pairs)."""
-        ids, cand_len = _candidates(candidates)
-        return rank_pairs(ids, self.pair_scores(Qn, ids, cand_len), k)
-
     def feedback(self, Qn: torch.Tensor, topk, *, fb_docs: int = 10, alpha: float = 1.0, beta: float = 1.0, weighting: str = "uniform",
                  normalize: bool = True) -> torch.Tensor:
         """Pseudo-relevance feedback: the queries moved towards the first fb_docs documents of their own lists (topk: a planes.RankedTopk
@@ -234,7 +315,7 @@ class ShardedDenseIndex(_ShardedIndex):
         from . import feedback as fb
         fb_ids, fb_len, coef = fb.coefficients(topk, fb_docs, beta, weighting)
         Dn = self.Dn[:, :Qn.shape[1]]                       # (a corpus matrix padded past the queries' width)
-        if fb._world(self.group) > 1:
+        if world(self.group) > 1:
             rows, slots = fb.gather_rows(Dn, fb_ids, self.id_base, self.group)
             out = ops.dense_feedback(Qn, rows, slots, fb_len, coef, alpha)
         else:
@@ -242,14 +323,11 @@ class ShardedDenseIndex(_ShardedIndex):
         return ops.normalize_rows(out) if normalize else out
 
     def search_feedback(self, Qn: torch.Tensor, k: int = 1000, *, mark=None, **feedback):
-        """search -> feedback -> search: the first pass's lists feed the queries back, the expanded queries are searched again.
-        -> planes.RankedTopk of the second pass.  **feedback: the keyword arguments of feedback()."""
-        from .planes import RankedTopk
-        first = RankedTopk.from_search(*self.search(Qn, k, mark=mark))
-        return RankedTopk.from_search(*self.search(self.feedback(Qn, first, **feedback), k, mark=mark))
+        """search -> feedback -> search -> planes.RankedTopk of the second pass.  **feedback: the keyword arguments of feedback()."""
+        return self._search_feedback((Qn,), k, mark, feedback)
 
 
-class ShardedSparseIndex(_ShardedIndex):
+class ShardedSparseIndex(_PairScores, _ShardedIndex):
     """One rank's shard of a SPLADE corpus as an inverted index (ops.SparseIndex, documents 0 .. N-1 = global ids id_base ..) + the
     chunked score -> top-k loop of splade/base.py:199-251 (BaseModel.search) at corpus scale: ops.sparse_dot scores the head, the rest
     streams through fz_sparse_dot_filter_f32, the posting walk whose epilogue is the filter.  Ties go to the ascending global id (SPLADE
@@ -286,16 +364,6 @@ class ShardedSparseIndex(_ShardedIndex):
         (ops.sparse_dot_pairs, by the route it picks)."""
         return ops.sparse_dot_pairs(self.index, qoff, qterms, qw, cand_ids, cand_len, id_base=self.id_base)
 
-    def pair_scores(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, cand_ids: torch.Tensor,
-                    cand_len: torch.Tensor | None = None) -> torch.Tensor:
-        """local_pair_scores for the whole corpus: one all_reduce(MAX) over the group."""
-        return _reduce_max(self.local_pair_scores(qoff, qterms, qw, cand_ids, cand_len), self.group)
-
-    def rerank(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, candidates, k: int | None = None):
-        """As ShardedDenseIndex.rerank, for the queries' term lists."""
-        ids, cand_len = _candidates(candidates)
-        return rank_pairs(ids, self.pair_scores(qoff, qterms, qw, ids, cand_len), k)
-
     def feedback(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, topk, *, fb_docs: int = 10, fb_terms: int = 32,
                  alpha: float = 1.0, beta: float = 1.0, weighting: str = "uniform", normalize: bool = True):
         """Pseudo-relevance feedback: the queries expanded from the first fb_docs documents of their own lists (topk: a planes.RankedTopk
@@ -312,19 +380,17 @@ class ShardedSparseIndex(_ShardedIndex):
                              f"({ops.sparse_feedback_max_vocab()} terms, ops.sparse_feedback_max_vocab)")
         fb_ids, fb_len, coef = fb.coefficients(topk, fb_docs, beta, weighting)
         base = self.id_base
-        if fb._world(self.group) > 1:
+        if world(self.group) > 1:
             fwd, fb_ids = fb.gather_rows(fwd, fb_ids, self.id_base, self.group)
             base = 0
         return ops.sparse_feedback(fwd, self.index.V, qoff, qterms, qw, fb_ids, fb_len, coef, alpha, fb_terms, id_base=base, normalize=normalize)
 
     def search_feedback(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, k: int = 1000, *, mark=None, **feedback):
-        """search -> feedback -> search (see ShardedDenseIndex.search_feedback) -> planes.RankedTopk of the second pass."""
-        from .planes import RankedTopk
-        first = RankedTopk.from_search(*self.search(qoff, qterms, qw, k, mark=mark))
-        return RankedTopk.from_search(*self.search(*self.feedback(qoff, qterms, qw, first, **feedback), k, mark=mark))
+        """search -> feedback -> search -> planes.RankedTopk of the second pass.  **feedback: the keyword arguments of feedback()."""
+        return self._search_feedback((qoff, qterms, qw), k, mark, feedback)
 
 
-class ShardedLexicalIndex:
+class ShardedLexicalIndex(_PairScores):
     """One rank's shard of a BM25 / AtireBM25 / TF-IDF corpus: a retrievers.bm25 model of the shard's documents built with the WHOLE corpus's
     statistics (`stats=LexicalStats.merge(...)`: global idf and avgdl) and its `id_base`, so every document scores what the whole index
     gives it, bit for bit.  local_topk is the model's own streamed (or plane) top-k in float64; the shards' lists are all-gathered and merged
@@ -357,7 +423,8 @@ class ShardedLexicalIndex:
 
     def local_pair_scores(self, queries: list[str], cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
         """[Q, W] float64: the model's score of query q and candidate cand_ids[q, r] (model.doc_scores on the positions id - id_base: the
-        bits of the full plane's entry); -inf for a slot this shard does not own."""
+        bits of the full plane's entry); -inf for a slot this shard does not own.  rerank ranks by the float64 scores and keeps them as
+        scores64."""
         m = self.model
         ci = torch.as_tensor(cand_ids).to(device=m.device, dtype=torch.int64)
         if ci.dim() != 2 or ci.shape[0] != len(queries):
@@ -370,33 +437,18 @@ class ShardedLexicalIndex:
             mine &= torch.arange(ci.shape[1], device=m.device)[None, :] < cand_len.to(m.device)[:, None]
         return m.doc_scores(queries, torch.where(mine, local, -1))
 
-    def pair_scores(self, queries: list[str], cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
-        """local_pair_scores for the whole corpus (float64): one all_reduce(MAX) over the group, as gold_ranks combines its golds' scores."""
-        return _reduce_max(self.local_pair_scores(queries, cand_ids, cand_len), self.group)
-
-    def rerank(self, queries: list[str], candidates, k: int | None = None):
-        """As ShardedDenseIndex.rerank; ranked by the float64 scores, which the result keeps as scores64."""
-        ids, cand_len = _candidates(candidates)
-        return rank_pairs(ids, self.pair_scores(queries, ids, cand_len), k)
-
     def gold_ranks(self, queries: list[str], gold_ids) -> torch.Tensor:
         """[Q, G] int64: the rank of global id gold_ids[q, g] in query q's ranking of the WHOLE corpus (what the grid search needs of it),
         the same on every rank; an id < 0 gives -1.  Every shard scores the golds it holds (-inf for the others: all_reduce(MAX) leaves each
         gold's score), counts its own documents ranked before each gold (the model's count_before), and the counts add: all_reduce(SUM).
         With the merged statistics a document scores the same in any shard, so the sums are the whole index's ranks for any number of
         shards.  The ids must be documents of the corpus."""
-        import torch.distributed as dist
         m = self.model
         gi = torch.as_tensor(gold_ids).to(device=m.device, dtype=torch.int64)
         local = gi - self.id_base
         mine = (gi >= 0) & (local >= 0) & (local < m.corpus_size)
-        many = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
-        sc = m.doc_scores(queries, torch.where(mine, local, -1))
-        if many:
-            dist.all_reduce(sc, op=dist.ReduceOp.MAX, group=self.group)
-        counts = m.count_before(queries, sc, gi)
-        if many:
-            dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
+        sc = reduce_max(m.doc_scores(queries, torch.where(mine, local, -1)), self.group)
+        counts = reduce_sum(m.count_before(queries, sc, gi), self.group)
         return torch.where(gi >= 0, counts, -1)
 
 
@@ -438,7 +490,7 @@ class ShardedCentroidIndex(_ShardedIndex):
         return self._search((pc, ps, Lq, nprobe), k, mark)
 
 
-class ShardedTokenIndex:
+class ShardedTokenIndex(_PairScores):
     """One rank's shard of a ColBERT corpus as its packed token matrix (Dtok_local [sumL, 128] float16, Doff_local [N + 1] int64;
     documents 0 .. N-1 = global ids id_base ..) + the exact rerank of candidate lists over it: the corpus-scale counterpart of
     ops.maxsim's [Q, N] plane, which the reference never builds either (its PLAID searcher scores candidates only, hybrid.py:108-137).
@@ -468,6 +520,8 @@ class ShardedTokenIndex:
     tok8 = None             # [sumL, 128] uint8: the e4m3 rows (quantize / build_e4m3)
     d_exp = None            # their quantiser exponent
     q_exp = 8               # the exponent the queries are quantised with per call over an e4m3 shard (the same on every rank)
+    TIES = "list"           # rerank keeps candidate-list order among equal scores
+    EMPTY_REDUCES = False   # an empty batch returns before the scorer and the all_reduce
 
     def __init__(self, Dtok_local: torch.Tensor, Doff_local: torch.Tensor, id_base: int, group=None, max_doc_len: int = 512):
         self.Dtok, self.Doff, self.id_base, self.group, self.max_doc_len = Dtok_local, Doff_local, int(id_base), group, int(max_doc_len)
@@ -522,18 +576,12 @@ class ShardedTokenIndex:
         sumL = int(Doff[-1]) if Doff.numel() else 0
         codes = torch.empty(sumL, dtype=torch.int32, device=device)
         packed = torch.empty((sumL, 16 * nbits), dtype=torch.uint8, device=device)
-        at = 0
-        for blk in blocks:
-            blk = blk.to(device=device, dtype=torch.float16).contiguous()
-            n = blk.shape[0]
-            if at + n > sumL:
-                raise ValueError(f"ShardedTokenIndex.build_compressed: the blocks hold more than Doff[N] = {sumL} token rows")
-            if n:
-                codes[at: at + n] = ops.centroid_assign(blk, C)
-                ops.residual_compress(blk, codes[at: at + n], C, cutoffs, nbits, out=packed[at: at + n])
-            at += n
-        if at != sumL:
-            raise ValueError(f"ShardedTokenIndex.build_compressed: the blocks hold {at} token rows, Doff[N] = {sumL}")
+
+        def fill(at, blk):
+            rows = slice(at, at + blk.shape[0])
+            codes[rows] = ops.centroid_assign(blk, C)
+            ops.residual_compress(blk, codes[rows], C, cutoffs, nbits, out=packed[rows])
+        _fill_blocks("ShardedTokenIndex.build_compressed", blocks, sumL, device, fill)
         self = cls(None, Doff, id_base, group=group, max_doc_len=max_doc_len)
         self.centroids, self.codes = C, codes
         self.candidates = ShardedCentroidIndex(ops.centroid_index(codes, Doff, C.shape[0]), self.id_base, group=group)
@@ -580,19 +628,13 @@ class ShardedTokenIndex:
         sumL = int(Doff[-1]) if Doff.numel() else 0
         tok8 = torch.empty((sumL, 128), dtype=torch.uint8, device=device)
         codes = None if C is None else torch.empty(sumL, dtype=torch.int32, device=device)
-        at = 0
-        for blk in blocks:
-            blk = blk.to(device=device, dtype=torch.float16).contiguous()
-            n = blk.shape[0]
-            if at + n > sumL:
-                raise ValueError(f"ShardedTokenIndex.build_e4m3: the blocks hold more than Doff[N] = {sumL} token rows")
-            if n:
-                tok8[at: at + n] = ops.quantize_e4m3(blk, scale_exp)
-                if C is not None:
-                    codes[at: at + n] = ops.centroid_assign(blk, C)
-            at += n
-        if at != sumL:
-            raise ValueError(f"ShardedTokenIndex.build_e4m3: the blocks hold {at} token rows, Doff[N] = {sumL}")
+
+        def fill(at, blk):
+            rows = slice(at, at + blk.shape[0])
+            tok8[rows] = ops.quantize_e4m3(blk, scale_exp)
+            if C is not None:
+                codes[rows] = ops.centroid_assign(blk, C)
+        _fill_blocks("ShardedTokenIndex.build_e4m3", blocks, sumL, device, fill)
         self = cls(None, Doff, id_base, group=group, max_doc_len=max_doc_len)
         if C is not None:
             self.build_centroids(C, codes=codes)
@@ -668,37 +710,8 @@ class ShardedTokenIndex:
                                          d_exp=self.d_exp, id_base=self.id_base, max_doc_len=self.max_doc_len)
         return ops.maxsim_pairs(Qtok, self.Dtok, self.Doff, cand_ids, cand_len, id_base=self.id_base, max_doc_len=self.max_doc_len)
 
-    def pair_scores(self, Qtok: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
-        """[Q, W] float32: local_scores for the whole corpus -- the shards' planes under one all_reduce(MAX), as inside rerank."""
-        return _reduce_max(self.local_scores(Qtok, cand_ids, cand_len), self.group)
 
-    def rerank(self, Qtok: torch.Tensor, candidates, k: int | None = None):
-        """candidates: a planes.RankedTopk (its ids and lens are used) or a [Q, k0] int64 id tensor (negative ids = padding) -> RankedTopk of
-        the candidates in descending exact-MaxSim order, cut to the first k (default: all k0).  lens[q] = the slots some shard owned:
-        they come first (a NaN score first of all, as in every ranking sort here), the others hold (-inf, -1).  A score of -inf itself --
-        possible only with non-finite token values -- is indistinguishable from "owned by no shard" after the reduction and counts as
-        such."""
-        from .planes import RankedTopk
-        import torch.distributed as dist
-        ids, cand_len = (candidates.ids, candidates.lens) if isinstance(candidates, RankedTopk) else (candidates, None)
-        if ids.numel() == 0:
-            return RankedTopk(ids=ids.clone(), scores=torch.empty(ids.shape, dtype=torch.float32, device=ids.device),
-                              lens=torch.zeros(ids.shape[0], dtype=torch.int32, device=ids.device))
-        scores = self.local_scores(Qtok, ids, cand_len)
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
-            scores = scores.contiguous()      # the collective takes the [Q, k] block, not the padded plane
-            dist.all_reduce(scores, op=dist.ReduceOp.MAX, group=self.group)
-        order, _, _ = ops.sort_rows_desc(scores, want_keys=False)
-        k0 = ids.shape[1]
-        k = k0 if k is None else min(int(k), k0)
-        order = order[:, :k].long()
-        sorted_scores = torch.gather(scores, 1, order)      # the scores' own bits (the sort's key plane canonicalises -0.0 and NaN)
-        owned = sorted_scores != float("-inf")
-        out_ids = torch.where(owned, torch.gather(ids, 1, order), torch.full_like(order, -1))
-        return RankedTopk(ids=out_ids, scores=sorted_scores, lens=owned.sum(1, dtype=torch.int32))
-
-
-class ShardedTextIndex:
+class ShardedTextIndex(_PairScores):
     """One rank's shard of the corpus as TOKEN IDS, for the cross-encoder rerank of top-k lists (hybrid.py:139-163): tok [sumL] int32,
     Doff [N + 1] int64, documents 0 .. N-1 = global ids id_base ..; the pattern of ShardedTokenIndex.  A document holds the first
     min(len, max_length - (2 + nsep)) plain tokens of its text, no specials -- the most any pair can keep of it, since pair truncation
@@ -708,6 +721,9 @@ class ShardedTextIndex:
     (fz_pair_plan / fz_pair_fill): no string is built, no document re-tokenised, no padded id matrix uploaded.  A slot this shard does not
     own gets -inf, so the shards' [Q, W] planes combine by ONE all_reduce(MAX) and every rank forwards only the pairs whose documents it
     holds: the forward is split across the ranks by the sharding alone."""
+
+    TIES = "list"           # rerank keeps candidate-list order among equal scores, as ShardedTokenIndex
+    EMPTY_REDUCES = False   # an empty batch returns before the forward and the all_reduce
 
     def __init__(self, tok: torch.Tensor, Doff: torch.Tensor, id_base: int, group=None, full_len: torch.Tensor | None = None):
         ops._pair_store("ShardedTextIndex", tok, Doff, full_len)
@@ -736,35 +752,16 @@ class ShardedTextIndex:
         return self.Doff.numel() - 1
 
     def local_scores(self, model, qtok: torch.Tensor, qlen: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
-        """[Q, W] float32: model.score_candidates over this shard; -inf for a slot it does not own."""
+        """[Q, W] float32: model.score_candidates over this shard; -inf for a slot it does not own.  (pair_scores as an
+        Aggregator.complete_topk scorer: lambda ids, lens: index.pair_scores(model, qtok, qlen, ids, lens).)"""
         return model.score_candidates(self, qtok, qlen, cand_ids, cand_len)
 
-    def pair_scores(self, model, qtok: torch.Tensor, qlen: torch.Tensor, cand_ids: torch.Tensor, cand_len: torch.Tensor | None = None) -> torch.Tensor:
-        """[Q, W] float32: local_scores for the whole corpus -- the shards' planes under one all_reduce(MAX).  As an Aggregator.complete_topk
-        scorer: lambda ids, lens: index.pair_scores(model, qtok, qlen, ids, lens)."""
-        return _reduce_max(self.local_scores(model, qtok, qlen, cand_ids, cand_len), self.group)
-
     def rerank(self, model, qtok: torch.Tensor, qlen: torch.Tensor, candidates, k: int | None = None, depth: int | None = None):
-        """candidates: a planes.RankedTopk / FusedTopk (its ids and lens are used) or a [Q, k0] int64 id tensor (negative ids = padding) ->
-        RankedTopk of the candidates in descending cross-encoder score, cut to the first k (default: all), built as ShardedTokenIndex.rerank
-        builds its own: one stable descending row sort, ties keep candidate order, a slot no shard owns ends as (-inf, -1), lens counts the
-        rest.  depth: only the first `depth` slots of every list are scored (and returned)."""
-        from .planes import RankedTopk
+        """_PairScores.rerank by the cross-encoder's scores.  depth: only the first `depth` slots of every list are scored (and returned)."""
         ids, cand_len = _candidates(candidates)
         ops._dev(ids, torch.int64, "ShardedTextIndex.rerank(candidates)")
         if depth is not None:
             if int(depth) < 1:
                 raise ValueError(f"ShardedTextIndex.rerank: depth = {depth} must be at least 1")
             ids = ids[:, : int(depth)]
-        if ids.numel() == 0:
-            return RankedTopk(ids=ids.clone(), scores=torch.empty(ids.shape, dtype=torch.float32, device=ids.device),
-                              lens=torch.zeros(ids.shape[0], dtype=torch.int32, device=ids.device))
-        scores = self.pair_scores(model, qtok, qlen, ids, cand_len)
-        order, _, _ = ops.sort_rows_desc(scores, want_keys=False)
-        k0 = ids.shape[1]
-        k = k0 if k is None else max(0, min(int(k), k0))
-        order = order[:, :k].long()
-        sorted_scores = torch.gather(scores, 1, order)      # the scores' own bits (the sort's key plane canonicalises -0.0 and NaN)
-        owned = sorted_scores != float("-inf")
-        out_ids = torch.where(owned, torch.gather(ids, 1, order), torch.full_like(order, -1))
-        return RankedTopk(ids=out_ids, scores=sorted_scores, lens=owned.sum(1, dtype=torch.int32))
+        return self._rerank((model, qtok, qlen), ids, cand_len, k)

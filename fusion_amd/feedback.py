@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import torch
 
+from .distributed import reduce_max
 from .planes import RankedTopk
 
 WEIGHTINGS = ("uniform", "score")
@@ -50,19 +51,6 @@ def coefficients(topk: RankedTopk, fb_docs: int, beta: float = 1.0, weighting: s
     return fb_ids, fb_len, coef.contiguous()
 
 
-def _world(group) -> int:
-    import torch.distributed as dist
-    return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
-
-
-def _reduce_max_(t: torch.Tensor, group) -> torch.Tensor:
-    """The tree's convention for slots a shard does not own: they hold the type's lowest value, all_reduce(MAX) leaves the owner's."""
-    if _world(group) > 1 and t.numel() > 0:
-        import torch.distributed as dist
-        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
-    return t
-
-
 def pack_rows(source, fb_ids: torch.Tensor, id_base: int = 0, group=None):
     """The rows of the feedback slots, padded and combined over the group's shards.  source: this rank's ops.SparseForward, or its [N, dim]
     float32 row matrix; its document d has the global id id_base + d.
@@ -81,13 +69,13 @@ def pack_rows(source, fb_ids: torch.Tensor, id_base: int = 0, group=None):
         rows = torch.full((Q, F, int(source.shape[1])), float("-inf"), dtype=torch.float32, device=dev)
         if N > 0 and own.any():
             rows[own] = source[d[own]]
-        return _reduce_max_(rows, group)
+        return reduce_max(rows, group, skip_empty=True)
     if N > 0:
         start = source.foff[d]
         lens = torch.where(own, source.foff[d + 1] - start, torch.zeros_like(d))
     else:
         start, lens = torch.zeros_like(d), torch.zeros_like(d)
-    L = _reduce_max_(lens.max().reshape(1) if lens.numel() else torch.zeros(1, dtype=torch.int64, device=dev), group)
+    L = reduce_max(lens.max().reshape(1) if lens.numel() else torch.zeros(1, dtype=torch.int64, device=dev), group)
     L = int(L.item())
     terms = torch.full((Q, F, L), -1, dtype=torch.int32, device=dev)
     weights = torch.full((Q, F, L), float("-inf"), dtype=torch.float32, device=dev)
@@ -97,7 +85,7 @@ def pack_rows(source, fb_ids: torch.Tensor, id_base: int = 0, group=None):
         src = (start[:, :, None] + at[None, None, :])[live]
         terms[live] = source.rows[src, 0]
         weights[live] = source.rows[src, 1].view(torch.float32)
-    return _reduce_max_(terms, group), _reduce_max_(weights, group)
+    return reduce_max(terms, group, skip_empty=True), reduce_max(weights, group, skip_empty=True)
 
 
 def gather_rows(source, fb_ids: torch.Tensor, id_base: int = 0, group=None):
@@ -112,7 +100,7 @@ def gather_rows(source, fb_ids: torch.Tensor, id_base: int = 0, group=None):
     none = torch.full_like(pseudo, -1)
     if isinstance(source, torch.Tensor):
         rows = pack_rows(source, fb_ids, id_base, group)
-        filled = rows[:, :, 0] != float("-inf") if rows.shape[2] > 0 else torch.zeros((Q, F), dtype=torch.bool, device=fb_ids.device)
+        filled = ~torch.isneginf(rows[:, :, 0]) if rows.shape[2] > 0 else torch.zeros((Q, F), dtype=torch.bool, device=fb_ids.device)
         return rows.view(Q * F, rows.shape[2]), torch.where(filled, pseudo, none)
     terms, weights = pack_rows(source, fb_ids, id_base, group)
     live = terms >= 0

@@ -71,6 +71,16 @@ def _need(cond: bool, msg: str):
         raise ValueError(msg)
 
 
+def check_pair_plane(P, Q: int, W: int, who: str) -> torch.Tensor:
+    """The contract of a pair scorer's result for ids [Q, W] -- a float32 or float64 tensor of shape (Q, W) -- under the caller's name for
+    the scorer (`who`: the start of the message)."""
+    if not isinstance(P, torch.Tensor) or P.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{who} must return a float32 or float64 tensor")
+    if tuple(P.shape) != (Q, W):
+        raise ValueError(f"{who} returned {tuple(P.shape)} for ids {(Q, W)}")
+    return P
+
+
 MAX_SYSTEMS = 8   # FZ_MAX_SYSTEMS (csrc/common.h): every fusion kernel's argument block holds this many systems
 
 
@@ -1317,6 +1327,11 @@ def fold_max_k(unordered: bool) -> int:
     """The largest k fz_topk_fold_f32 takes (fz_topk_fold_max_k): 5,056 for candidates in arrival order, 35,839 for ordered ones.  A constant
     of the library: asked once."""
     return int(_lib.lib().fz_topk_fold_max_k(1 if unordered else 0))
+
+
+def tune_max_gold() -> int:
+    """The gold ids per query one launch of the weight sweep's counting kernel takes (fz_tune_max_gold)."""
+    return int(_lib.lib().fz_tune_max_gold())
 
 
 def stream_window(seen: int, k: int, cap: int) -> int:

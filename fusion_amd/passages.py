@@ -116,10 +116,7 @@ class PassageGroups:
             blens = torch.clamp(lens - w0, min=0, max=w1 - w0).to(torch.int32)
             pcand, seg, plen = ops.group_expand(doc_ids[:, w0:w1], blens, self.poff, ldp, id_base=self.id_base, doc_id_base=self.doc_id_base)
             P = passage_scorer(pcand, plen) if ldp > 0 else torch.empty((Q, 0), dtype=torch.float32, device=dev)   # no passage at all
-            if not isinstance(P, torch.Tensor) or P.dtype not in (torch.float32, torch.float64):
-                raise TypeError("PassageGroups.pair_scores: the passage scorer must return a float32 or float64 tensor")
-            if tuple(P.shape) != (Q, ldp):
-                raise ValueError(f"PassageGroups.pair_scores: the passage scorer returned {tuple(P.shape)} for ids {(Q, ldp)}")
+            ops.check_pair_plane(P, Q, ldp, "PassageGroups.pair_scores: the passage scorer")
             if out is None:
                 out = ops.alloc_plane(Q, W, P.dtype, dev)
                 best = ops.alloc_plane(Q, W, torch.int64, dev)

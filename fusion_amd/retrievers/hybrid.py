@@ -619,7 +619,7 @@ class Aggregator:
                 raise TypeError(f"Aggregator.complete_topk: the scorer of {n!r} is not callable")
         if depth is not None and int(depth) < 1:
             raise ValueError(f"Aggregator.complete_topk: depth = {depth} must be at least 1")
-        from ..distributed import rank_order
+        from ..distributed import rank_pairs
         S = [systems[n] for n in names]
         Q = cls._same_queries(s.Q for s in S)
         U, _, _, ulen, _ = ops.lists_columns([s.ids for s in S], [s.lens for s in S], None)
@@ -630,22 +630,9 @@ class Aggregator:
             if n not in scorers:
                 out[n] = s
                 continue
-            P = scorers[n](U, ulen)
-            if not isinstance(P, torch.Tensor) or P.dtype not in (torch.float32, torch.float64):
-                raise TypeError(f"Aggregator.complete_topk: the scorer of {n!r} must return a float32 or float64 tensor")
-            if tuple(P.shape) != (Q, W):
-                raise ValueError(f"Aggregator.complete_topk: the scorer of {n!r} returned {tuple(P.shape)} for ids {(Q, W)}")
-            lens = torch.clamp(ulen, max=keep)
-            if Q == 0 or W == 0:
-                out[n] = RankedTopk(ids=U[:, :keep], scores=P[:, :keep].to(torch.float32), lens=lens,
-                                    scores64=P[:, :keep] if P.dtype == torch.float64 else None)
-                continue
-            order = rank_order(U, P, ulen)[:, :keep]
-            listed = order >= 0
-            at = order.clamp(min=0)
-            sc = torch.gather(P, 1, at).masked_fill_(~listed, float("-inf"))      # the scorer's own bits
-            ids = torch.gather(U, 1, at).masked_fill_(~listed, -1)
-            out[n] = RankedTopk(ids=ids, scores=sc.to(torch.float32), lens=lens, scores64=sc if P.dtype == torch.float64 else None)
+            P = ops.check_pair_plane(scorers[n](U, ulen), Q, W, f"Aggregator.complete_topk: the scorer of {n!r}")
+            out[n] = rank_pairs(U, P, keep, row_len=ulen)
+            out[n].lens = torch.clamp(ulen, max=keep)      # the union's size, whatever the scores
         return out
 
     # -- N1: the whole weight grid in one pass (hybrid.py:404-426) ----------------------------------
@@ -678,7 +665,7 @@ class Aggregator:
             ins, U, pos = ops.insertion_order([s.order for s in S], lens, N, want_pos=True)
         id2pos = {cid: j for j, cid in enumerate(S[0].ids.tolist())}
         gold_pos = [[id2pos.get(g, -1) for g in dict.fromkeys(gl)] for gl in labels]   # unique, order kept
-        G = int(ops._lib.lib().fz_tune_max_gold())
+        G = ops.tune_max_gold()
         Gmax = max((len(g) for g in gold_pos), default=0)
         n_gold = np.array([len(gl) for gl in labels], dtype=np.int64)          # the reference divides by len(ground_truths)
         if Gmax <= G:
@@ -734,7 +721,7 @@ class Aggregator:
         """Labels (global ids) -> per query its distinct gold ids in order, as a [Q, G'] int64 device tensor padded with -1 to a multiple
         of fz_tune_max_gold(); the largest gold count; len(ground_truths) per query, the reference's divisor."""
         ops._need(len(labels) == Q, f"labels for {len(labels)} queries, ranked lists for {Q}")
-        G = int(ops._lib.lib().fz_tune_max_gold())
+        G = ops.tune_max_gold()
         gold_lists = [list(dict.fromkeys(gl)) for gl in labels]   # unique, order kept
         Gmax = max((len(g) for g in gold_lists), default=0)
         gold = np.full((Q, max(ops.round_up(Gmax, G), G)), -1, dtype=np.int64)
@@ -780,7 +767,7 @@ class Aggregator:
         Tn =cls._normalised_lists(names, S, normalization, percentile_distributions)
         gold_dev, Gmax, n_gold = cls._gold_ids(labels, Q, dev)
         _, T, pos, out_len, gold_col = ops.lists_columns([s.ids for s in S], [s.lens for s in S], Tn, gold_dev)
-        G = int(ops._lib.lib().fz_tune_max_gold())
+        G = ops.tune_max_gold()
         if Gmax <= G:   # ranks -> metrics stay on the device: [W, 15] float64 come back
             return cls._metrics_of_gold_ranks(ops.gold_ranks(T, pos, weights, gold_col), gold_col, pos, n_gold, dev)
         INF = np.iinfo(np.int64).max
@@ -803,7 +790,7 @@ class Aggregator:
         Q, dev = ids.shape[0], ids.device
         gold_dev, Gmax, n_gold = cls._gold_ids(labels, Q, dev)
         _, _, pos, out_len, gold_col = ops.lists_columns([ids], [lens], None, gold_dev)
-        if Gmax <= gold_col.shape[1] == int(ops._lib.lib().fz_tune_max_gold()):
+        if Gmax <= gold_col.shape[1] == ops.tune_max_gold():
             return cls._metrics_of_gold_ranks(gold_col.clamp(min=0)[None].contiguous(), gold_col, ops.as_plane(pos), n_gold, dev)[0]
         col = gold_col.cpu().numpy().astype(np.int64)[:, :Gmax]
         return metrics_from_gold_ranks(np.where(col >= 0, col, np.iinfo(np.int64).max)[None], n_gold, out_len.cpu().numpy())[0]

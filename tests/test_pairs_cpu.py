@@ -3,6 +3,7 @@ HIP call), the type and shape errors of ops.dot_pairs / ops.sparse_dot_pairs, th
 hand-checked cases, Aggregator.complete_topk's argument errors, and the shipped build's resource report for the new kernels."""
 import ctypes as C
 import os
+import re
 import sys
 
 import numpy as np
@@ -182,6 +183,25 @@ def test_complete_topk_argument_errors():
         Aggregator.complete_topk({str(i): lst for i in range(9)}, {})
     with pytest.raises(TypeError, match="GPU"):      # the join itself has no CPU path
         Aggregator.complete_topk({"a": lst}, {"a": score})
+
+
+def test_complete_topk_holds_a_scorer_to_its_contract(monkeypatch):
+    """With the join stood in for (it has no CPU path), what a scorer returns is checked before anything is ranked: a float32 or float64
+    tensor of the union's shape (ops.check_pair_plane, under complete_topk's name for the scorer)."""
+    from fusion_amd import ops
+    from fusion_amd.planes import RankedTopk
+    from fusion_amd.retrievers.hybrid import Aggregator
+    ids = torch.tensor([[3, 1, -1]], dtype=torch.int64)
+    lst = RankedTopk.from_search(torch.tensor([[2.0, 1.0, float("-inf")]]), ids)
+    monkeypatch.setattr(ops, "lists_columns", lambda ids, lens, planes: (ids[0], None, None, lens[0], None))
+    for bad in (lambda U, n: torch.zeros(U.shape, dtype=torch.float16), lambda U, n: torch.zeros(U.shape, dtype=torch.int64), lambda U, n: [0.0] * 3):
+        with pytest.raises(TypeError, match=r"^Aggregator\.complete_topk: the scorer of 'a' must return a float32 or float64 tensor$"):
+            Aggregator.complete_topk({"a": lst}, {"a": bad})
+    for bad, shape in ((lambda U, n: torch.zeros((1, 2)), (1, 2)), (lambda U, n: torch.zeros(3, dtype=torch.float64), (3,))):
+        with pytest.raises(ValueError, match=rf"^Aggregator\.complete_topk: the scorer of 'a' returned {re.escape(str(shape))} for ids \(1, 3\)$"):
+            Aggregator.complete_topk({"a": lst}, {"a": bad})
+    for good in (torch.zeros((1, 3)), torch.zeros((1, 3), dtype=torch.float64)):
+        assert ops.check_pair_plane(good, 1, 3, "x") is good
 
 
 # ---- the shipped build ---------------------------------------------------------------------------------------------------------------

@@ -156,6 +156,23 @@ def test_passage_groups_validates_poff():
         PassageGroups(np.zeros((2, 2), np.int64), device="cpu")
 
 
+def test_pair_scores_holds_the_passage_scorer_to_its_contract(monkeypatch):
+    """With the device steps stood in for, what the passage scorer returns is checked before the maximum is taken: a float32 or float64
+    tensor of the expanded ids' shape (ops.check_pair_plane, under pair_scores' name for the scorer)."""
+    import torch
+    from fusion_amd import ops
+    from fusion_amd.passages import PassageGroups
+    g = PassageGroups(np.array([0, 2, 2, 5], np.int64), device="cpu")
+    docs = torch.tensor([[0, 2], [1, -1]], dtype=torch.int64)                   # ldp = min(W * pmax, P) = 5 passage slots per query
+    monkeypatch.setattr(ops, "_dev", lambda t, *a, **k: t)
+    monkeypatch.setattr(ops, "group_expand", lambda ids, lens, poff, ldp, **k: (torch.zeros((2, ldp), dtype=torch.int64), None, lens))
+    for bad in (lambda ids, lens: torch.zeros(ids.shape, dtype=torch.float16), lambda ids, lens: np.zeros((2, 5), np.float32)):
+        with pytest.raises(TypeError, match=r"^PassageGroups\.pair_scores: the passage scorer must return a float32 or float64 tensor$"):
+            g.pair_scores(bad, docs)
+    with pytest.raises(ValueError, match=r"^PassageGroups\.pair_scores: the passage scorer returned \(2, 4\) for ids \(2, 5\)$"):
+        g.pair_scores(lambda ids, lens: torch.zeros((2, 4)), docs)
+
+
 @pytest.mark.parametrize("run", [1, 5])
 def test_restatement_equals_brute_force_maximum(run):
     """collapse_ref (first occurrence in list order) == the per-document maximum ranked by (score desc, position asc) on ranked
