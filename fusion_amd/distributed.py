@@ -437,6 +437,80 @@ class ShardedLexicalIndex(_PairScores):
             mine &= torch.arange(ci.shape[1], device=m.device)[None, :] < cand_len.to(m.device)[:, None]
         return m.doc_scores(queries, torch.where(mine, local, -1))
 
+    # -- pseudo-relevance feedback: the rows of the feedback documents in the corpus's common term space (feedback.global_term_table) --
+    def _term_space(self):
+        """(words of the global ids, local -> global [V_local] int64 device, global -> local [n_global] int64 device), built once."""
+        if getattr(self, "_terms", None) is None:
+            from . import feedback as fb
+            words, l2g = fb.global_term_table(self.model)
+            g2l = fb.global_to_local(l2g, len(words))
+            dev = self.model.device
+            self._terms = (words, torch.from_numpy(l2g).to(dev), torch.from_numpy(g2l).to(dev), {w: i for i, w in enumerate(words)})
+        return self._terms
+
+    def global_feedback(self, queries: list[str], topk, *, fb_docs: int = 10, fb_terms: int = 10, alpha: float = 1.0, beta: float = 0.5,
+                        weighting: str = "uniform"):
+        """The expanded queries over the GLOBAL term ids (a retrievers.bm25.WeightedQueries; feedback.global_term_table's words name the
+        ids): every rank packs the rows of the feedback documents it owns (feedback.pack_lexical_rows), one all_reduce(MAX) per tensor
+        (and one for the row width) leaves every slot its owner's row on every rank, and the rows kernel (ops.lexical_feedback_rows) runs
+        on the queries' terms mapped to global ids.  Ties are broken on the global id: the expansions do not depend on the number of
+        shards.  The arithmetic and the keywords are TFIDF.feedback's."""
+        from . import feedback as fb
+        from .retrievers.bm25 import WeightedQueries
+        import numpy as np
+        m = self.model
+        words, l2g, _, gid = self._term_space()
+        fb_ids, fb_len, coef = fb.coefficients(topk, fb_docs, 1.0, weighting)
+        walks = m.lexical_mode() is not None                           # (a shard without postings owns no row)
+        if walks and m.forward is None:
+            m.build_forward()
+        lens = fb.lexical_row_lengths(m, fb_ids) if walks else torch.zeros_like(fb_ids)
+        L = int(reduce_max(lens.max().reshape(1) if lens.numel() else torch.zeros(1, dtype=torch.int64, device=m.device), self.group).item())
+        if walks:
+            terms, values = fb.pack_lexical_rows(m, l2g, fb_ids, L)
+        else:
+            terms = torch.full(tuple(fb_ids.shape) + (L,), -1, dtype=torch.int32, device=m.device)
+            values = torch.full(tuple(fb_ids.shape) + (L,), float("-inf"), dtype=torch.float64, device=m.device)
+        foff, fterm, fval, slots = fb.lexical_rows(reduce_max(terms, self.group, skip_empty=True), reduce_max(values, self.group, skip_empty=True))
+        qt = [[gid.get(w, -1) for w in q.split()] for q in queries]
+        qoff = np.zeros(len(qt) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in qt], out=qoff[1:])
+        flat = np.array([t for x in qt for t in x] or [0], dtype=np.int32)
+        return WeightedQueries(*ops.lexical_feedback_rows(foff, fterm, fval, torch.from_numpy(qoff).to(m.device), torch.from_numpy(flat).to(m.device),
+                                                          slots, fb_len, coef, alpha, beta, fb_terms))
+
+    def localize(self, wq):
+        """Global-id weighted queries -> this shard's: every term mapped to the shard's own id, -1 (adds nothing) where it lacks the word."""
+        from .retrievers.bm25 import WeightedQueries
+        g2l = self._term_space()[2]
+        t = wq.qterms.long()
+        local = torch.where(t >= 0, g2l[t.clamp(min=0)], torch.full_like(t, -1)) if g2l.numel() else torch.full_like(t, -1)
+        return WeightedQueries(wq.qoff, local.to(torch.int32), wq.qw, wq.flags)
+
+    def expansion_words(self, wq) -> list[list[tuple]]:
+        """(word, weight) per entry of global_feedback's queries."""
+        from .retrievers.bm25 import expansion_words
+        return expansion_words(wq, self._term_space()[0])
+
+    def feedback(self, queries: list[str], topk, **feedback):
+        """global_feedback mapped to this shard's term ids: what the model's weighted walks take (model.search_topk_weighted)."""
+        return self.localize(self.global_feedback(queries, topk, **feedback))
+
+    def search_feedback(self, queries: list[str], k: int = 1000, *, mark=None, **feedback):
+        """search -> feedback -> the weighted search over every shard, merged as search() merges -> planes.RankedTopk of the second pass."""
+        from .planes import RankedTopk
+        wq = self.feedback(queries, self.search(queries, k, mark=mark), **feedback)
+        second = self.model.search_topk_weighted(wq, k, streaming=True, mark=mark)
+        self.last_overflow = self.model.last_overflow
+        s, i = second.scores64, second.ids
+        if s.shape[1] < k:     # a shard smaller than k: pad to the common width of the collective
+            pad = k - s.shape[1]
+            s = torch.cat([s, torch.full((s.shape[0], pad), float("-inf"), dtype=s.dtype, device=s.device)], 1)
+            i = torch.cat([i, torch.full((i.shape[0], pad), -1, dtype=i.dtype, device=i.device)], 1)
+        s, i = allgather_topk(s, i, group=self.group, merge_fn=ops.topk_merge64)
+        if mark: mark("allgather_merge")
+        return RankedTopk.from_search(s.to(torch.float32), i, scores64=s)
+
     def gold_ranks(self, queries: list[str], gold_ids) -> torch.Tensor:
         """[Q, G] int64: the rank of global id gold_ids[q, g] in query q's ranking of the WHOLE corpus (what the grid search needs of it),
         the same on every rank; an id < 0 gives -1.  Every shard scores the golds it holds (-inf for the others: all_reduce(MAX) leaves each

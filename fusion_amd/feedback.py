@@ -10,7 +10,11 @@ module holds what sits around them:
                  owner's row on every rank, and the rows become a batch-local index of Q * F pseudo-documents the same kernels read --
                  so the expanded queries do not depend on the number of shards.
 
-distributed.ShardedSparseIndex / ShardedDenseIndex .feedback and .search_feedback are built from these.
+  pack_lexical_rows / lexical_rows   the same for the lexical models (BM25 / TF-IDF, float64, csrc/feedback_lexical.hip): a shard's rows
+                 as (term id in the COMMON term space, the model's weight of the term in the document), combined by MAX, then the rows
+                 the rows kernel (ops.lexical_feedback_rows) reads.
+
+distributed.ShardedSparseIndex / ShardedDenseIndex / ShardedLexicalIndex .feedback and .search_feedback are built from these.
 """
 from __future__ import annotations
 
@@ -111,3 +115,88 @@ def gather_rows(source, fb_ids: torch.Tensor, id_base: int = 0, group=None):
     rows[:, 0] = terms[live]
     rows[:, 1] = weights[live].view(torch.int32)
     return ops.SparseForward(foff, rows, Q * F, source.V), torch.where(lens > 0, pseudo, none)
+
+
+def global_term_table(model):
+    """The common term space of the shards of one lexical corpus: a word's id is its position in the merged statistics' df table
+    (LexicalStats.merge: Counter.update keeps first-occurrence order, so the table is the same on every rank, and for contiguous shards
+    it is the whole corpus's own term numbering); a model built without `stats` is the whole corpus: its own vocabulary.
+    -> (words: list, the word of every global id; local_to_global [V_local] int64 host array)."""
+    import numpy as np
+    if model.global_stats is None:
+        return list(model.vocab), np.arange(len(model.vocab), dtype=np.int64)
+    words = list(model.global_stats.df)
+    gid = {w: i for i, w in enumerate(words)}
+    return words, np.fromiter((gid[w] for w in model.vocab), dtype=np.int64, count=len(model.vocab))
+
+
+def global_to_local(local_to_global, n_global: int):
+    """[n_global] int64 host array: the local term id of every global id, -1 where the shard lacks the word."""
+    import numpy as np
+    g2l = np.full(int(n_global), -1, dtype=np.int64)
+    g2l[local_to_global] = np.arange(len(local_to_global), dtype=np.int64)
+    return g2l
+
+
+def lexical_row_lengths(model, fb_ids: torch.Tensor) -> torch.Tensor:
+    """[Q, F] int64: the number of distinct terms of the document each feedback slot names, 0 for a slot this shard does not own
+    (model: a retrievers.bm25 model with a forward index; its document d has the global id model.id_base + d)."""
+    fwd, N = model.forward, int(model.corpus_size)
+    d = fb_ids - int(model.id_base)
+    own = (fb_ids >= int(model.id_base)) & (d >= 0) & (d < N)
+    d = torch.where(own, d, torch.zeros_like(d))
+    if N == 0:
+        return torch.zeros_like(d)
+    return torch.where(own, fwd.foff[d + 1] - fwd.foff[d], torch.zeros_like(d))
+
+
+def pack_lexical_rows(model, local_to_global: torch.Tensor, fb_ids: torch.Tensor, width: int | None = None):
+    """ONE shard's part of the feedback rows, a pure function of the shard: -> (terms [Q, F, L] int32 in the common term space, fill -1;
+    values [Q, F, L] float64, fill -inf).  values = the model's weight of the term in the document, exactly what its posting walk adds:
+    pval[p] (BM25 / AtireBM25) or float64(ptf[p]) * idf[t] (TF-IDF; one rounding).  local_to_global: [V_local] int64 device tensor
+    (global_term_table).  width L: at least the longest row of the batch on ANY shard (None: this shard's own longest).  A slot's owner
+    fills it, every other shard leaves the fill: an element-wise MAX over the shards (torch.maximum, or one all_reduce(MAX) per tensor)
+    gives every slot its owner's row."""
+    mode = model.lexical_mode()
+    if mode is None:
+        raise ValueError("pack_lexical_rows: this model's scoring has no range walk (no postings, or BM25.USE_POSTING_VALUES = False)")
+    if model.forward is None:
+        model.build_forward()
+    fwd = model.forward
+    vals, idf = model.lexical_tables()
+    Q, F = int(fb_ids.shape[0]), int(fb_ids.shape[1])
+    dev = fb_ids.device
+    lens = lexical_row_lengths(model, fb_ids)
+    own_L = int(lens.max().item()) if lens.numel() else 0
+    L = own_L if width is None else int(width)
+    if L < own_L:
+        raise ValueError(f"pack_lexical_rows: width = {L} is below this shard's longest row ({own_L})")
+    terms = torch.full((Q, F, L), -1, dtype=torch.int32, device=dev)
+    values = torch.full((Q, F, L), float("-inf"), dtype=torch.float64, device=dev)
+    at = torch.arange(L, device=dev)
+    live = at[None, None, :] < lens[:, :, None]
+    if L > 0 and bool(live.any()):
+        d = (fb_ids - int(model.id_base)).clamp(min=0, max=max(int(model.corpus_size) - 1, 0))
+        src = (fwd.foff[d][:, :, None] + at[None, None, :])[live]
+        t_local = fwd.fterm[src].long()
+        p = fwd.fpos[src].long()
+        terms[live] = local_to_global[t_local].to(torch.int32)
+        values[live] = vals[p] if mode == "pv" else vals[p].to(torch.float64) * idf[t_local]
+        # a row in ascending GLOBAL term order (the local order is the shard's own numbering), the fill last: the same pack from any sharding
+        order = torch.argsort(torch.where(live, terms, torch.iinfo(torch.int32).max), dim=2, stable=True)
+        terms, values = torch.gather(terms, 2, order), torch.gather(values, 2, order)
+    return terms, values
+
+
+def lexical_rows(terms: torch.Tensor, values: torch.Tensor):
+    """The combined pack as the rows ops.lexical_feedback_rows reads: slot (q, r) is pseudo-document q * F + r.
+    -> (foff [Q * F + 1] int64, fterm int32, fval float64, fb_ids' [Q, F] int64): fb_ids' holds q * F + r where some shard filled the
+    slot and -1 elsewhere, so the kernel's slot rules skip what nobody owns (a document without terms fills nothing: it adds nothing)."""
+    Q, F = int(terms.shape[0]), int(terms.shape[1])
+    dev = terms.device
+    live = terms >= 0
+    lens = live.sum(2)
+    foff = torch.zeros(Q * F + 1, dtype=torch.int64, device=dev)
+    foff[1:] = torch.cumsum(lens.reshape(-1), 0)
+    pseudo = torch.arange(Q * F, dtype=torch.int64, device=dev).view(Q, F)
+    return foff, terms[live].contiguous(), values[live].contiguous(), torch.where(lens > 0, pseudo, torch.full_like(pseudo, -1))

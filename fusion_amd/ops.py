@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import math
 
 import numpy as np
 import torch
@@ -1758,15 +1759,36 @@ def _lexical_call(mode: str, stem: str, toff, pdoc, vals, idf, *rest) -> None:
     check(getattr(_lib.lib(), name)(_ptr(toff), _ptr(pdoc), *values, *rest, _stream(toff)), name)
 
 
+def lexical_weighted_terms(mode: str) -> int:
+    """Query entries the weighted walks resolve per batch: 256 for 'pv', 128 for 'tfidf' (the batch groups the entries; no bit depends on it)."""
+    _need(mode in LEXICAL_MODES, f"lexical_weighted_terms: mode must be one of {sorted(LEXICAL_MODES)}")
+    return int(_lib.lib().fz_lexical_weighted_terms(LEXICAL_MODES[mode]))
+
+
+def _lexical_weights(what: str, qterms, qw) -> torch.Tensor:
+    """The weights of a weighted lexical query: float64, contiguous, one per entry of qterms, all finite (one host read)."""
+    _need(_dev(qw, torch.float64, f"{what}(qw)").is_contiguous() and qw.dim() == 1, f"{what}(qw) must be a contiguous 1-d tensor")
+    _need(qw.numel() == qterms.numel(), f"{what}(qw): {qw.numel()} weights for {qterms.numel()} entries of qterms")
+    _need(bool(torch.isfinite(qw).all().item()), f"{what}(qw): every weight must be finite")
+    return qw
+
+
 def lexical_scores_range(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int, doc_lo: int = 0, doc_hi: int | None = None,
-                         slice_off: torch.Tensor | None = None) -> torch.Tensor:
+                         slice_off: torch.Tensor | None = None, qw: torch.Tensor | None = None) -> torch.Tensor:
     """Columns [doc_lo, doc_hi) of the full float64 plane, bit for bit, without the rest of it (fz_bm25_scores_range_pv_f64 /
     fz_tfidf_scores_range_f64): [Q, doc_hi - doc_lo], column j = document doc_lo + j.  doc_lo a multiple of lexical_slice_docs(mode), doc_hi
-    a multiple of it or N.  vals: pval ('pv') or ptf ('tfidf', with idf)."""
+    a multiple of it or N.  vals: pval ('pv') or ptf ('tfidf', with idf).  qw (float64, one weight per entry of qterms): the weighted walk
+    (fz_bm25_scores_range_w_pv_f64 / fz_tfidf_scores_range_w_f64): entry j adds qw[j] * the unweighted walk's term, in entry order."""
     what = ("bm25" if mode == "pv" else "tfidf") + "_scores_range"      # the public wrappers' names: what a caller reads in an error
     doc_lo, doc_hi = _lexical_args(what, mode, toff, pdoc, vals, idf, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
+    if qw is not None:
+        _lexical_weights(what, qterms, qw)
     out = alloc_plane(Q, doc_hi - doc_lo, torch.float64, toff.device)
-    _lexical_call(mode, "scores_range", toff, pdoc, vals, idf, _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi, _ptr(out), _ld(out))
+    if qw is None:
+        _lexical_call(mode, "scores_range", toff, pdoc, vals, idf, _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi, _ptr(out), _ld(out))
+    else:
+        _lexical_call(mode, "scores_range_w", toff, pdoc, vals, idf, _ptr(slice_off), _ptr(qoff), _ptr(qterms), _ptr(qw), Q, N, doc_lo, doc_hi,
+                      _ptr(out), _ld(out))
     return out
 
 
@@ -1783,15 +1805,21 @@ def tfidf_scores_range(toff, pdoc, ptf, idf, qoff, qterms, Q: int, N: int, doc_l
 
 
 def lexical_filter(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int, doc_lo: int, doc_hi: int, id_base: int, tau, cand_s, cand_i,
-                   cand_len, overflow, slice_off: torch.Tensor | None = None) -> None:
+                   cand_len, overflow, slice_off: torch.Tensor | None = None, qw: torch.Tensor | None = None) -> None:
     """The range walk with the threshold filter as its epilogue (fz_bm25_filter_pv_f64 / fz_tfidf_filter_f64): document d of [doc_lo, doc_hi)
     is appended to row q of cand_s / cand_i [Q, cap] as (float64 score, id_base + d) iff !(score <= tau[q]); cand_len [Q] int32 counts on
-    past cap, nothing is stored there, `overflow` (int32 [1]) is set.  vals: pval ('pv') or ptf ('tfidf', with idf)."""
+    past cap, nothing is stored there, `overflow` (int32 [1]) is set.  vals: pval ('pv') or ptf ('tfidf', with idf).  qw: the weighted walk
+    (fz_bm25_filter_w_pv_f64 / fz_tfidf_filter_w_f64), as lexical_scores_range takes it."""
     what = "lexical_filter"
     doc_lo, doc_hi = _lexical_args(what, mode, toff, pdoc, vals, idf, qoff, qterms, Q, N, doc_lo, doc_hi, slice_off)
     cap = _cand_buffers(what, torch.float64, Q, tau, cand_s, cand_i, cand_len, overflow)
-    _lexical_call(mode, "filter", toff, pdoc, vals, idf, _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi, int(id_base), _ptr(tau),
-                  _ptr(cand_s), _ptr(cand_i), _ptr(cand_len), cap, _ptr(overflow))
+    if qw is None:
+        _lexical_call(mode, "filter", toff, pdoc, vals, idf, _ptr(slice_off), _ptr(qoff), _ptr(qterms), Q, N, doc_lo, doc_hi, int(id_base), _ptr(tau),
+                      _ptr(cand_s), _ptr(cand_i), _ptr(cand_len), cap, _ptr(overflow))
+    else:
+        _lexical_weights(what, qterms, qw)
+        _lexical_call(mode, "filter_w", toff, pdoc, vals, idf, _ptr(slice_off), _ptr(qoff), _ptr(qterms), _ptr(qw), Q, N, doc_lo, doc_hi,
+                      int(id_base), _ptr(tau), _ptr(cand_s), _ptr(cand_i), _ptr(cand_len), cap, _ptr(overflow))
 
 
 def _query_blocks(Q: int, block: int):
@@ -1850,9 +1878,10 @@ def lexical_count(mode: str, toff, pdoc, vals, idf, qoff, qterms, Q: int, N: int
                       _ptr(gold_scores[lo:]), _ptr(gold_ids[lo:]), G, _ptr(counts[lo:]))
 
 
-def _lexical_source(model, qoff, qterms, id_base: int) -> _Source:
+def _lexical_source(model, qoff, qterms, id_base: int, qw: torch.Tensor | None = None) -> _Source:
     """The lexical posting walk whose epilogue is the filter (TopkStream64): document d of the model's index = id id_base + d.  model: a
-    retrievers.bm25 TFIDF / BM25 / AtireBM25 whose lexical_mode() is 'pv' or 'tfidf' (lexical_tables(): the walk's per-posting values and idf)."""
+    retrievers.bm25 TFIDF / BM25 / AtireBM25 whose lexical_mode() is 'pv' or 'tfidf' (lexical_tables(): the walk's per-posting values and idf).
+    qw: the entries' float64 weights (the weighted walks); None: the unweighted ones."""
     mode = model.lexical_mode()
     _need(mode in LEXICAL_MODES, "_lexical_source: the model's scoring mode has no range walk (BM25.USE_POSTING_VALUES = False)")
     vals, idf = model.lexical_tables()
@@ -1860,10 +1889,10 @@ def _lexical_source(model, qoff, qterms, id_base: int) -> _Source:
 
     def filter(st, lo, hi):
         lexical_filter(mode, model.toff, model.pdoc, vals, idf, qoff, qterms, Q, N, lo, hi, id_base, st.tau, st.cand_s, st.cand_i, st.cand_len,
-                       st.overflow, slice_off=so)
+                       st.overflow, slice_off=so, qw=qw)
 
     def plane(lo, hi):
-        return lexical_scores_range(mode, model.toff, model.pdoc, vals, idf, qoff, qterms, Q, N, lo, hi, slice_off=so), id_base + lo
+        return lexical_scores_range(mode, model.toff, model.pdoc, vals, idf, qoff, qterms, Q, N, lo, hi, slice_off=so, qw=qw), id_base + lo
     return _Source(N, filter, plane, grain=lexical_slice_docs(mode), unordered=True, mark="shard_lexical_filter")
 
 
@@ -2259,6 +2288,87 @@ def sparse_feedback(forward: SparseForward, V: int, qoff: torch.Tensor, qterms: 
     noff = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
     noff[1:] = torch.cumsum(out_len, 0)
     return noff, out_terms[kept].contiguous(), out_w[kept].contiguous()
+
+
+def lexical_feedback_max_entries() -> int:
+    """The sum of the counted feedback rows' lengths, per query, that the lexical feedback kernels hold (4,096)."""
+    return int(_lib.lib().fz_lexical_feedback_max_entries())
+
+
+LEXICAL_FEEDBACK_CUT = 1     # bit 0 of the flags lexical_feedback returns: the capacity rule skipped slots of some query
+
+
+def _lexical_feedback_run(what: str, entry: str, rows: tuple, foff, N: int, qoff, qterms, fb_ids, fb_len, coef, alpha: float, beta: float, m: int,
+                          id_base: int):
+    """What the three lexical feedback entries share: the checks on queries and slots, the output rows, the call, and the expanded
+    queries as a CSR -> (qoff', qterms', qw', flags)."""
+    _contiguous(what, (qoff, torch.int64, "qoff"), (qterms, torch.int32, "qterms"), (foff, torch.int64, "foff"))
+    Q, m, N = qoff.numel() - 1, int(m), int(N)
+    _need(Q >= 0 and qoff.dim() == 1 and qterms.dim() == 1, f"{what}: qoff must hold Q + 1 offsets, qterms the queries' entries")
+    _need(m >= 0, f"{what}: fb_terms = {m} must not be negative")
+    _need(N >= 0 and foff.numel() == N + 1, f"{what}: foff must hold N + 1 = {N + 1} row offsets, got {foff.numel()}")
+    _need(math.isfinite(alpha) and math.isfinite(beta), f"{what}: alpha and beta must be finite")
+    fb_len, F = _feedback_args(what, Q, fb_ids, fb_len, coef)
+    dev = qoff.device
+    lens = qoff[1:] - qoff[:-1]
+    nq_max = int(lens.max().item()) if Q > 0 else 0                        # the one host read of the plan
+    _need(Q == 0 or int(qoff[-1].item()) <= qterms.numel(), f"{what}: qoff runs past qterms")
+    width = nq_max + m
+    out_terms = alloc_plane(Q, width, torch.int32, dev)
+    out_w = alloc_plane(Q, width, torch.float64, dev)
+    ldo = max(_ld(out_terms), width)
+    if Q > 1:
+        _need(_ld(out_w) == ldo, f"{what}: the output planes differ in row stride")
+    out_len = torch.zeros(Q, dtype=torch.int32, device=dev)
+    flags = 0
+    if Q > 0:
+        flag = torch.empty(4, dtype=torch.uint8, device=dev)
+        check(getattr(_lib.lib(), entry)(_ptr(foff), *rows, N, int(id_base), _ptr(qoff), _ptr(qterms), Q, _ptr(fb_ids), max(_ld(fb_ids), F),
+                                         _ptr(fb_len), _ptr(coef), max(_ld(coef), F), F, float(alpha), float(beta), m, _ptr(out_terms),
+                                         _ptr(out_w), ldo, width, _ptr(out_len), _ptr(flag), _stream(qoff)), entry)
+        flags = _flag_word(flag)
+        if flags & 2:
+            raise RuntimeError(f"{what}: an expanded query did not fit its row of {width} entries")
+    kept = torch.arange(width, device=dev)[None, :] < out_len[:, None]
+    noff = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+    noff[1:] = torch.cumsum(out_len, 0)
+    nterms, nw = out_terms[kept].contiguous(), out_w[kept].contiguous()
+    if nterms.numel() == 0:                                                # (the walks take a non-empty qterms: TFIDF._query_csr's padding)
+        nterms, nw = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)
+    return noff, nterms, nw, flags
+
+
+def lexical_feedback(mode: str, forward: "ForwardIndex", vals, idf, qoff, qterms, fb_ids, fb_len, coef, alpha: float, beta: float, m: int, *,
+                     id_base: int = 0):
+    """Expansion terms for lexical queries from their feedback documents (fz_bm25_feedback_pv_f64 / fz_tfidf_feedback_f64; the arithmetic:
+    include/fusion_hip.h and DESIGN.md, 'Lexical feedback').  forward: the index's ops.ForwardIndex (fpos kept); vals: pval ('pv') or ptf
+    ('tfidf', with idf); the queries as TFIDF._query_csr gives them (repetitions and -1 kept); fb_ids [Q, F] int64, fb_len [Q] int32 or
+    None, coef [Q, F] float32 (feedback.coefficients).  w[t] = sum in slot order of coef * val(t, d); of the terms with w > 0 that are not
+    the query's the m of largest w (ties: the lower term) follow the query's own entries:
+    -> (qoff', qterms', qw' float64, flags): the original entries at alpha, then the selected terms at beta * (w / w_max); flags & 1
+    (LEXICAL_FEEDBACK_CUT): some query's rows passed lexical_feedback_max_entries() and its later slots were skipped."""
+    what = "lexical_feedback"
+    _need(mode in LEXICAL_MODES, f"{what}: mode must be one of {sorted(LEXICAL_MODES)}")
+    if not isinstance(forward, ForwardIndex):
+        raise TypeError(f"{what}(forward): expected an ops.ForwardIndex, got {type(forward).__name__}")
+    _contiguous(what, (forward.fterm, torch.int32, "forward.fterm"), (forward.fpos, torch.int32, "forward.fpos"),
+                (vals, torch.float64 if mode == "pv" else torch.int32, "pval" if mode == "pv" else "ptf"))
+    _need(forward.fpos.numel() == forward.nnz == vals.numel(), f"{what}: the forward index must be the one built from these postings")
+    if mode == "tfidf":
+        _need(_dev(idf, torch.float64, f"{what}(idf)").is_contiguous() and idf.numel() >= forward.V, f"{what}: idf must hold one value per term")
+    rows = (_ptr(forward.fterm), _ptr(forward.fpos), _ptr(vals)) + ((_ptr(idf),) if mode == "tfidf" else ())
+    entry = "fz_bm25_feedback_pv_f64" if mode == "pv" else "fz_tfidf_feedback_f64"
+    return _lexical_feedback_run(what, entry, rows, forward.foff, forward.N, qoff, qterms, fb_ids, fb_len, coef, alpha, beta, m, id_base)
+
+
+def lexical_feedback_rows(foff, fterm, fval, qoff, qterms, fb_ids, fb_len, coef, alpha: float, beta: float, m: int, *, id_base: int = 0):
+    """lexical_feedback over rows given directly (fz_lexical_feedback_rows_f64): row d = entries [foff[d], foff[d+1]) of (fterm int32,
+    fval float64 = val(t, d)), terms unique inside a row; the term space is the caller's (the sharded route: global term ids)."""
+    what = "lexical_feedback_rows"
+    _contiguous(what, (fterm, torch.int32, "fterm"), (fval, torch.float64, "fval"), (foff, torch.int64, "foff"))
+    _need(fterm.numel() == fval.numel() and foff.numel() >= 1, f"{what}: one value per row entry and N + 1 row offsets expected")
+    return _lexical_feedback_run(what, "fz_lexical_feedback_rows_f64", (_ptr(fterm), _ptr(fval)), foff, foff.numel() - 1, qoff, qterms, fb_ids,
+                                 fb_len, coef, alpha, beta, m, id_base)
 
 
 def dense_feedback(Qn: torch.Tensor, Dn: torch.Tensor, fb_ids: torch.Tensor, fb_len: torch.Tensor | None, coef: torch.Tensor, alpha: float, *,

@@ -84,6 +84,12 @@ def expected_zero_share(df: np.ndarray, n_docs: int, query_terms: list[list[int]
     return float(per_query.mean())
 
 
+def expansion_words(wq, words: list) -> list[list[tuple]]:
+    """(word, weight) per entry of every weighted query, words[t] the word of term id t (None for -1)."""
+    off, terms, w = wq.qoff.cpu().tolist(), wq.qterms.cpu().tolist(), wq.qw.cpu().tolist()
+    return [[(words[terms[j]] if terms[j] >= 0 else None, w[j]) for j in range(off[q], off[q + 1])] for q in range(len(off) - 1)]
+
+
 class LexicalStats:
     """The collection statistics a lexical model's idf table and BM25's avgdl are made from: number of documents, document frequency of
     every word, total length in words.  Those of a whole corpus are the sums of its shards' (`merge`), so a shard's model built with the
@@ -109,6 +115,30 @@ class LexicalStats:
 
     def __repr__(self):
         return f"LexicalStats(n_docs={self.n_docs}, words={len(self.df)}, total_len={self.total_len})"
+
+
+class WeightedQueries:
+    """Lexical queries whose entries carry a float64 weight, as the weighted posting walks take them (csrc/bm25_weighted.hip): qoff
+    [Q + 1] int64, qterms int32 term ids of ONE model's vocabulary (repetitions and -1 kept), qw float64 one weight per entry.  What
+    TFIDF.feedback returns: the original entries at alpha, then the expansion terms.  flags: ops.lexical_feedback's (bit 0: the capacity
+    rule skipped feedback slots of some query)."""
+
+    def __init__(self, qoff: torch.Tensor, qterms: torch.Tensor, qw: torch.Tensor, flags: int = 0):
+        if qoff.dtype != torch.int64 or qterms.dtype != torch.int32 or qw.dtype != torch.float64:
+            raise TypeError(f"WeightedQueries: expected int64 offsets, int32 terms and float64 weights, got {qoff.dtype} / {qterms.dtype} / {qw.dtype}")
+        if qoff.dim() != 1 or qoff.numel() < 1 or qterms.dim() != 1 or tuple(qw.shape) != tuple(qterms.shape):
+            raise ValueError("WeightedQueries: qoff [Q + 1], and qterms and qw with one entry each per query entry expected")
+        self.qoff, self.qterms, self.qw, self.flags = qoff, qterms, qw, int(flags)
+
+    @property
+    def Q(self) -> int:
+        return self.qoff.numel() - 1
+
+    def __repr__(self):
+        return f"WeightedQueries(Q={self.Q}, entries={int(self.qoff[-1])}, flags={self.flags})"
+
+
+FEEDBACK_DEFAULTS = dict(fb_docs=10, fb_terms=10, alpha=1.0, beta=0.5, weighting="uniform")   # the usual RM3 settings; tuned on nothing
 
 
 class TFIDF:
@@ -309,6 +339,107 @@ class TFIDF:
                 src, k, head, chunk, self.CAP, "shard_lexical", mark, ops.TopkStream64, top_positions=self._top_positions)
             self.last_overflow += redone
         return sc64, ids
+
+    # -- pseudo-relevance feedback (csrc/feedback_lexical.hip) and the weighted walks (csrc/bm25_weighted.hip); DESIGN.md, 'Lexical feedback' --
+    def feedback(self, queries: list[str], topk: RankedTopk, *, fb_docs: int = 10, fb_terms: int = 10, alpha: float = 1.0, beta: float = 0.5,
+                 weighting: str = "uniform") -> WeightedQueries:
+        """The queries expanded from the first fb_docs documents of their own lists (topk: the RankedTopk of a first search_topk; ids
+        outside this index are skipped).  w[t] = sum over the feedback documents, in list order, of coef * (the model's weight of t in the
+        document: exactly what the walk adds for that posting), coef from feedback.coefficients(topk, fb_docs, 1.0, weighting); of the terms
+        with w > 0 that the query does not hold, the fb_terms of largest w (ties: the lower term id) are appended at beta * (w / w_max),
+        the original entries keep their order at weight alpha.  The defaults are the usual RM3 settings, tuned on nothing.  The forward
+        index is built on first use.  ValueError for a model without a range walk (BM25.USE_POSTING_VALUES = False)."""
+        from .. import feedback as fb
+        mode, vals, idf = self._walk_tables("feedback")
+        if self.forward is None:
+            self.build_forward()
+        qoff, flat = self._query_csr(queries)
+        fb_ids, fb_len, coef = fb.coefficients(topk, fb_docs, 1.0, weighting)
+        if fb_ids.shape[0] != len(queries):
+            raise ValueError(f"feedback: {len(queries)} queries but lists for {fb_ids.shape[0]}")
+        return WeightedQueries(*ops.lexical_feedback(mode, self.forward, vals, idf, qoff, flat, fb_ids, fb_len, coef, alpha, beta, fb_terms,
+                                                     id_base=self.id_base))
+
+    def _weighted_plane(self, wq: WeightedQueries, lo: int, hi: int, tables) -> torch.Tensor:
+        mode, vals, idf = tables
+        return ops.lexical_scores_range(mode, self.toff, self.pdoc, vals, idf, wq.qoff[lo:hi + 1], wq.qterms, hi - lo, self.corpus_size, 0,
+                                        self.corpus_size, slice_off=self.slice_off, qw=wq.qw)
+
+    def scores_weighted(self, wq: WeightedQueries, budget_bytes: int = DEVICE_BUDGET_BYTES) -> torch.Tensor:
+        """[Q, N] float64: score(q', d) = the chain, in entry order, of acc + qw[j] * (the walk's term of entry j's posting in d) -- the
+        weighted range walk over [0, N), the queries in chunks whose planes fit budget_bytes.  With every weight 1.0: scores()'s plane."""
+        tables = self._walk_tables("scores_weighted")
+        Q, N = wq.Q, self.corpus_size
+        step = min(32768, max(1, int(budget_bytes // (8 * ops.round_up(max(N, 1), 64)))))
+        if Q <= step:
+            return self._weighted_plane(wq, 0, Q, tables)
+        out = ops.alloc_plane(Q, N, torch.float64, self.device)
+        for lo in range(0, Q, step):
+            hi = min(Q, lo + step)
+            out[lo:hi] = self._weighted_plane(wq, lo, hi, tables)
+        return out
+
+    def search_device_weighted(self, wq: WeightedQueries, ids: np.ndarray | None = None) -> RankedSystem:
+        """search_device for weighted queries: the full ranking of the weighted plane (float32 plane = its rounding), ties -> ascending index."""
+        sc64 = self.scores_weighted(wq)
+        Q, N = sc64.shape
+        sc32 = ops.as_plane(sc64.to(torch.float32))
+        stats4 = None
+        if N <= ops.sort_max_n(torch.float64) and Q > 0:
+            stats4 = torch.empty((4, Q), dtype=torch.float32, device=self.device)
+        order, _, rank = ops.sort_rows_desc(sc64, want_keys=False, want_rank=True, stats_out=stats4)
+        lens = torch.full((Q,), N, dtype=torch.int32, device=self.device)
+        return RankedSystem(scores=sc32, order=order, rank=rank, lens=lens, ids=np.arange(N, dtype=np.int64) if ids is None else ids,
+                            full=True, scores64=sc64, score_sorted=True, stats4=stats4)
+
+    def search_topk_weighted(self, wq: WeightedQueries, k: int, budget_bytes: int = DEVICE_BUDGET_BYTES, streaming: bool | None = None,
+                             mark=None) -> RankedTopk:
+        """search_topk for weighted queries, by the same two routes (streaming as there: the weighted filter walk under ops.TopkStream64,
+        or the weighted plane ranked / cut) -- the same lists either way; last_path / last_overflow record what ran."""
+        tables = self._walk_tables("search_topk_weighted")
+        mark = mark or (lambda name: None)
+        N, k, Q = self.corpus_size, max(0, min(k, self.corpus_size)), wq.Q
+        if streaming is None:
+            streaming = N > ops.sort_max_n(torch.float64)
+        self.last_overflow = 0
+        ids = torch.empty((Q, k), dtype=torch.int64, device=self.device)
+        sc64 = torch.empty((Q, k), dtype=torch.float64, device=self.device)
+        if streaming and Q > 0 and self._streams(k):
+            self.last_path = "stream"
+            head, chunk = self.head_docs(k), ops.stream_chunk(self.CHUNK, ops.lexical_slice_docs(tables[0]))
+            for lo in range(0, Q, self.STREAM_QUERIES):
+                hi = min(Q, lo + self.STREAM_QUERIES)
+                src = ops._lexical_source(self, wq.qoff[lo:hi + 1], wq.qterms, self.id_base, qw=wq.qw)
+                sc64[lo:hi], ids[lo:hi], redone = ops.stream_search(src, k, head, chunk, self.CAP, "shard_lexical", mark, ops.TopkStream64,
+                                                                    top_positions=self._top_positions)
+                self.last_overflow += redone
+        else:
+            self.last_path = "plane"
+            W = ops.sort_max_n(torch.float64)
+            step = min(32768, self._query_step(k, budget_bytes))
+            for lo in range(0, Q if k else 0, step):
+                hi = min(Q, lo + step)
+                plane = self._weighted_plane(wq, lo, hi, tables); mark("shard_lexical")
+                if N <= W:
+                    p = ops.sort_rows_desc(plane, want_keys=False)[0][:, :k].long()
+                else:
+                    p = self._top_positions(plane, k)
+                sc64[lo:hi] = torch.gather(plane, 1, p); mark("shard_topk_exact")
+                ids[lo:hi] = p + self.id_base
+        lens = torch.full((Q,), k, dtype=torch.int32, device=self.device)
+        return RankedTopk(ids=ids, scores=sc64.to(torch.float32), lens=lens, scores64=sc64)
+
+    def search_feedback(self, queries: list[str], k: int, budget_bytes: int = DEVICE_BUDGET_BYTES, streaming: bool | None = None,
+                        **feedback) -> RankedTopk:
+        """search_topk -> feedback -> search_topk_weighted: the top-k lists of the expanded queries (**feedback: feedback()'s keywords).
+        alpha = 1, fb_terms = 0 gives search_topk's lists."""
+        first = self.search_topk(queries, k, budget_bytes, streaming)
+        return self.search_topk_weighted(self.feedback(queries, first, **feedback), k, budget_bytes, streaming)
+
+    def expansion_words(self, wq: WeightedQueries) -> list[list[tuple]]:
+        """Host lists, one per query, of (word, weight) for every entry of the weighted queries in order (None for an entry outside the
+        vocabulary): what feedback() made of the queries, for inspection."""
+        return expansion_words(wq, list(self.vocab))
 
     # -- ranks of listed documents as counts on the posting walk (csrc/bm25_count.hip): no plane, no list, no sort --
     def _walk_tables(self, what: str):

@@ -75,10 +75,13 @@ class Ranker:
 
     @staticmethod
     def bm25_search(queries: list[str], corpus: dict[int, str], do_preprocessing: bool, k1: float, b: float, return_topk: int = None,
-                    *, as_device: bool = False):
+                    *, as_device: bool = False, feedback: dict | None = None):
         """hybrid.py:49-75. `do_preprocessing=True` runs the reference's TextPreprocessor recipe (src/data/preprocessor.py: spaCy
         fr_core_news_md -- punctuation, numbers and stop words dropped, lemmas, lower case) when that third-party model is installed and
-        raises RuntimeError when it is not (offline: pass lemmatised whitespace text with do_preprocessing=False); never a silent no-op."""
+        raises RuntimeError when it is not (offline: pass lemmatised whitespace text with do_preprocessing=False); never a silent no-op.
+        `feedback` (a dict of TFIDF.feedback's keywords, {} for its defaults; None: off): pseudo-relevance feedback -- the first pass as
+        above, the queries expanded from the first fb_docs documents of their lists, and the ranking of the weighted plane of the
+        expanded queries in its place ('Lexical feedback')."""
         from .bm25 import BM25, preprocess
         documents = list(corpus.values())
         if do_preprocessing:
@@ -86,6 +89,12 @@ class Ranker:
         ids = np.array(list(corpus.keys()))
         retriever = BM25(corpus=documents, k1=k1, b=b, device=_device())
         rs = retriever.search_device(queries, ids=ids)
+        if feedback is not None:
+            F = min(int(feedback.get("fb_docs", 10)), rs.N)
+            pos = rs.order[:, :F].long()
+            sc = torch.gather(rs.scores64, 1, pos)
+            first = RankedTopk(ids=pos, scores=sc.to(torch.float32), lens=torch.full_like(rs.lens, F), scores64=sc)
+            rs = retriever.search_device_weighted(retriever.feedback(queries, first, **feedback), ids=ids)
         if return_topk is not None and return_topk < rs.N:
             k = return_topk
             rs.rank.masked_fill_(rs.rank >= k, -1)          # in place: the planes keep their padded, 16-byte aligned rows

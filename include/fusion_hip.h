@@ -807,6 +807,59 @@ int fz_dense_feedback_f32(const float* Qn, int ldq, const float* Dn, int ldd, in
                           const int64_t* fb_ids, int ldf, const int32_t* fb_len, const float* coef, int ldc, int F, float alpha, float* out,
                           int ldo, void* stream);
 
+/* ---- lexical feedback: weighted posting walks and expansion terms in float64 (csrc/bm25_weighted.hip, csrc/feedback_lexical.hip; ABI 20, additive) ----
+ * The weighted walks: the four range entries above (plane and filter, both modes) for queries whose every entry carries a float64 weight,
+ * qw [one per entry of qterms] after qterms, every other argument and check as in the unweighted entry (qw among the pointers).  Per
+ * document the chain, in entry order j, of acc = acc + qw[j] * val(t_j, d) from +0.0, val(t, d) the unweighted walk's own term for that
+ * posting (pval[p], or (double)ptf[p] * idf[t], rounded before the product with qw[j]); an entry with t_j < 0 adds nothing.  With qw all
+ * 1.0 the results are the unweighted entries', bit for bit.  fz_lexical_weighted_terms(tfidf): the entries resolved per batch (256 / 128);
+ * the batch only groups the entries, the bits do not depend on it. */
+int fz_lexical_weighted_terms(int tfidf);
+int fz_bm25_scores_range_w_pv_f64(const int64_t* toff, const int32_t* pdoc, const double* pval, const int64_t* slice_off, const int64_t* qoff,
+                                  const int32_t* qterms, const double* qw, int Q, int N, int doc_lo, int doc_hi, double* scores, int lds,
+                                  void* stream);
+int fz_tfidf_scores_range_w_f64(const int64_t* toff, const int32_t* pdoc, const int32_t* ptf, const double* idf, const int64_t* slice_off,
+                                const int64_t* qoff, const int32_t* qterms, const double* qw, int Q, int N, int doc_lo, int doc_hi,
+                                double* scores, int lds, void* stream);
+int fz_bm25_filter_w_pv_f64(const int64_t* toff, const int32_t* pdoc, const double* pval, const int64_t* slice_off, const int64_t* qoff,
+                            const int32_t* qterms, const double* qw, int Q, int N, int doc_lo, int doc_hi, int64_t id_base, const double* tau,
+                            double* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow, void* stream);
+int fz_tfidf_filter_w_f64(const int64_t* toff, const int32_t* pdoc, const int32_t* ptf, const double* idf, const int64_t* slice_off,
+                          const int64_t* qoff, const int32_t* qterms, const double* qw, int Q, int N, int doc_lo, int doc_hi, int64_t id_base,
+                          const double* tau, double* cand_scores, int64_t* cand_ids, int32_t* cand_len, int cap, int32_t* overflow,
+                          void* stream);
+/* Expansion terms from feedback lists (fb_ids / fb_len / coef / N / id_base and the slot rules as for fz_sparse_feedback_f32; coef is
+ * widened exactly to float64).  Rows: document d's entries [foff[d], foff[d+1]) of fterm (int32, unique inside a row) with the value
+ * val(t, d) = pval[fpos[e]] (fz_bm25_feedback_pv_f64), (double)ptf[fpos[e]] * idf[fterm[e]] (fz_tfidf_feedback_f64) or fval[e]
+ * (fz_lexical_feedback_rows_f64).  Queries: qoff [Q + 1] int64, qterms int32 with repetitions and -1 entries.
+ *   1. capacity: slots are counted in order while the running sum of their row lengths stays within fz_lexical_feedback_max_entries()
+ *      (4,096); the first slot that would pass it is skipped with every later slot of the query, and bit 0 of *flag is raised;
+ *   2. per counted slot r in order, per entry (t, val) of its row: w[t] = w[t] + coef[q][r] * val, from +0.0; product and add are rounded
+ *      once each; a term's additions are made in slot order;
+ *   3. candidates: w[t] > 0 and t not among the query's terms; selected: the min(m, #candidates) of largest w, ties to the lower term;
+ *   4. out_terms [Q][ldo] int32 / out_w [Q][ldo] float64: the query's entries in their order (repetitions and -1 kept) at weight alpha,
+ *      then the selected terms in selection order at beta * (w[t] / w_max), w_max the first selected term's w (the division is rounded,
+ *      then the product); out_len[q] entries, columns out_len[q] .. width-1 hold (-1, +0.0).  The kernel writes all `width` columns of
+ *      every row and nothing else.  width >= longest query + m by contract; a row that does not fit is cut and raises bit 1 of *flag
+ *      (a device int32 the call zeroes first).
+ * One workgroup per query; the sums live in an LDS hash table keyed by term, so the vocabulary's size does not matter.  No float atomics:
+ * two calls give the same bytes.  Checks, before the first HIP call: a negative Q / N / F / m / width, ldf < F, ldc < F, ldo < width ->
+ * FZ_ERR_ARG; Q == 0 -> FZ_OK, nothing launched; then a null pointer among qoff, out_len, flag, fb_ids / coef (F > 0), out_terms / out_w
+ * (width > 0), foff (F > 0 and N > 0) -> FZ_ERR_ARG. */
+int fz_lexical_feedback_max_entries(void);
+int fz_bm25_feedback_pv_f64(const int64_t* foff, const int32_t* fterm, const int32_t* fpos, const double* pval, int64_t N, int64_t id_base,
+                            const int64_t* qoff, const int32_t* qterms, int Q, const int64_t* fb_ids, int ldf, const int32_t* fb_len,
+                            const float* coef, int ldc, int F, double alpha, double beta, int m, int32_t* out_terms, double* out_w, int ldo,
+                            int width, int32_t* out_len, int32_t* flag, void* stream);
+int fz_tfidf_feedback_f64(const int64_t* foff, const int32_t* fterm, const int32_t* fpos, const int32_t* ptf, const double* idf, int64_t N,
+                          int64_t id_base, const int64_t* qoff, const int32_t* qterms, int Q, const int64_t* fb_ids, int ldf,
+                          const int32_t* fb_len, const float* coef, int ldc, int F, double alpha, double beta, int m, int32_t* out_terms,
+                          double* out_w, int ldo, int width, int32_t* out_len, int32_t* flag, void* stream);
+int fz_lexical_feedback_rows_f64(const int64_t* foff, const int32_t* fterm, const double* fval, int64_t N, int64_t id_base,
+                                 const int64_t* qoff, const int32_t* qterms, int Q, const int64_t* fb_ids, int ldf, const int32_t* fb_len,
+                                 const float* coef, int ldc, int F, double alpha, double beta, int m, int32_t* out_terms, double* out_w,
+                                 int ldo, int width, int32_t* out_len, int32_t* flag, void* stream);
+
 /* ---- cross-encoder pairs assembled from token ids (csrc/crosspack.hip; ABI 20, additive) ---------------------------------------------------
  * The monoBERT rerank (hybrid.py:139-163) over top-k lists: the pair rows "<s> q </s></s> d </s>" of the packed forward are built on the
  * device from the queries' token ids and a token store of the corpus, sharded by document: tok [sumL] int32, Doff [N + 1] int64 (document d
